@@ -4,6 +4,15 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {0,1,2,3,4,d4}]   # N > 1: starts its own ranks as a child process
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W    # N > 1, one rank per GPU (RCCL): the driver's form
+    python bench.py --full ...                  # + every section below the headline (profiled pass, rooflines, ILT, CPU baseline, ...)
+    python bench.py --dump-outputs DIR ...      # + what the last timed step computed, as DIR/<name>.npy
+
+A plain run does only what the headline figure needs: set-up (planner construction, first command, `--preheat-ms` of untimed
+commands), W warm-up steps, K timed steps, the `--dump-outputs` files if asked for, and the result line.  Everything else it
+measures -- the profiled pass and the rooflines, the collective timed by itself, the stand-alone ILT kernels, the CPU baseline,
+the other BASELINE configs, the int8-sliced encoder, ``also_collective`` -- runs only with ``--full``; in a plain line those
+fields are null.  The warm-up and timed steps always start from the planner's initial state (U = 0, a zero action buffer,
+Philox command counter 0) whatever the time-boxed pre-heat did, so the same arguments give the timed path the same inputs.
 
 A "step" is one ``MPPIDelay.command()`` -- the region the reference times at mppi_with_model.py:257-259 -- by default
 on BASELINE configs[1]: oderl-cartpole (nx=5, nu=1), K=16384 samples, horizon T=40, action_buffer_size 4,
@@ -19,15 +28,15 @@ outcome through the launcher's TCP store, and
   * a child that fails or stops making progress with ``--collective auto`` (the library-owned RCCL communicator inside
     nlc_mppi_finish) is killed on every rank and a second fresh child measures with ``--collective torch``; the line then
     carries ``config.collective_fallback_reason``;
-  * when the first child succeeds with the library's collective, a second child measures torch.distributed's all-gather
-    too and the line carries it under ``also_collective`` -- one record, both modes;
+  * with ``--full``, when the first child succeeds with the library's collective, a second child measures torch.distributed's
+    all-gather too and the line carries it under ``also_collective`` -- one record, both modes;
   * ``config.ranks_seen`` holds the group size torch.distributed and the library's communicator report, and per rank the
     device, the rollout body, the kernel averages (``rccl_all_gather`` among them) and the collective's own timing.
 
-The K timed steps run WITHOUT the library's per-launch event profiling; a second, untimed pass of the same steps
-with profiling on gives the per-kernel averages the roofline uses (hipEvent pairs on the launch stream).
+The K timed steps run WITHOUT the library's per-launch event profiling; with ``--full`` a second, untimed pass of the same
+steps with profiling on gives the per-kernel averages the roofline uses (hipEvent pairs on the launch stream).
 
-Prints ONE JSON line on rank 0 with the contract fields plus ``roofline`` (dominant kernel: the FP64-MFMA GRU
+Prints ONE JSON line on rank 0 with the contract fields plus, with ``--full``, ``roofline`` (dominant kernel: the FP64-MFMA GRU
 encoder at the headline size, the fused one-launch planner body on a small shard), ``roofline_ilt`` (stand-alone
 Fourier ILT kernel, HBM-bound; ``dehoog33`` / ``backward`` inside it) and ``cpu_baseline`` (the CPU oracle =
 reference op sequence, timed on this host's cores; rank 0, N=1 only).
@@ -49,6 +58,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 ENV, K_SAMPLES, HORIZON, ABUF, S_TERMS, HIDDEN, A_HIGH = "oderl-cartpole", 16384, 40, 4, 17, 128, 3.0
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix (= FP64 vector) dense peak, AMD datasheet; the guide lists no f64 row
 # newest committed PMC summary (separate rocprofv3 --pmc passes: tools/collect_profiles.sh + tools/pmc_summarize.py)
@@ -429,19 +439,81 @@ def preheat(one_step, ms, group=None, device="cpu", chunk=16):
             return n
 
 
+def timed_path_outputs(planner, action):
+    """What a caller of command() holds after the last timed step: the action it returned, U, and the planner's per-sample
+    results (noise, perturbed actions, stored rollouts, costs, weights), as float64 host arrays.  name -> (array, per_sample)."""
+    out = {"action": (action, False), "U": (planner.U, False)}
+    for name in ("noise", "perturbed_action", "states", "actions", "cost_total", "cost_total_non_zero", "omega"):
+        t = getattr(planner, name)
+        if t is not None:
+            out[name] = (t, True)
+    return {k: (np.asarray(v.detach().cpu().numpy(), dtype=np.float64), per) for k, (v, per) in out.items()}
+
+
+def write_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: each array of `arrays` (name -> (array, per_sample)) as out_dir/<name>.npy.  When they would pass
+    `limit_bytes` together, every per-sample array keeps the same fixed, seeded subset of its rows (leading dimension), in
+    ascending order; their indices go to sample_index.npy.  Returns what the result line says about it."""
+    os.makedirs(out_dir, exist_ok=True)
+    fixed = sum(a.nbytes for a, per in arrays.values() if not per) + 1024 * (len(arrays) + 1)  # (+ a .npy header per file)
+    rows = {a.shape[0] for a, per in arrays.values() if per}
+    if len(rows) > 1:
+        raise ValueError(f"per-sample arrays disagree on their sample count: {sorted(rows)}")
+    n = rows.pop() if rows else 0
+    row_bytes = sum(a.nbytes // max(n, 1) for a, per in arrays.values() if per)
+    idx = None
+    index_path = os.path.join(out_dir, "sample_index.npy")
+    if fixed + n * row_bytes > limit_bytes:
+        keep = max((limit_bytes - fixed) // (row_bytes + 8), 1)
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.remove(index_path)  # (left by an earlier, sampled run into the same directory)
+    for name, (a, per) in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[idx] if per and idx is not None else a))
+    return dict(dir=out_dir, arrays=sorted(arrays), samples=n, samples_written=n if idx is None else len(idx))
+
+
+def source_tree_sha():
+    """Content hash of what a run executes: bench.py, bench_supervisor.py, the package's Python files and the kernel sources
+    (__graft_entry__.csrc_sha).  Names the tree where no git metadata names its commit."""
+    import hashlib
+
+    import __graft_entry__
+
+    pkg = os.path.join(REPO, "neurallaplacecontrol_amd")
+    files = [os.path.join(REPO, "bench.py"), os.path.join(REPO, "bench_supervisor.py")]
+    for root, dirs, names in os.walk(pkg):
+        dirs[:] = sorted(d for d in dirs if d != "__pycache__" and d != "csrc")
+        files += [os.path.join(root, n) for n in sorted(names) if n.endswith(".py") and n != "_build_info.py"]
+    h = hashlib.sha256(__graft_entry__.csrc_sha().encode())
+    for f in files:
+        h.update(os.path.relpath(f, REPO).encode() + b"\0")
+        h.update(open(f, "rb").read())
+    return h.hexdigest()[:16]
+
+
 def git_commit():
     try:
         return subprocess.check_output(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
     except Exception:
-        # the GPU box gets a snapshot without .git: the commit __graft_entry__.build() recorded next to the library
-        return build_info().get("commit") or os.environ.get("NLC_COMMIT")
+        # a checkout without .git: the commit __graft_entry__.build() recorded next to the library, else the sources by content
+        return build_info().get("commit") or os.environ.get("NLC_COMMIT") or f"unknown (no git metadata; sources {source_tree_sha()})"
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (one command() each)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every section beside the headline figure: the profiled pass (kernels_avg_ms, roofline), the "
+                         "collective timed by itself, the stand-alone ILT kernels, the CPU baseline, the other BASELINE configs, "
+                         "the int8-sliced encoder and, N > 1, also_collective (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the action, U and the planner's per-sample "
+                         f"arrays (rank 0's shard when N > 1) -- as DIR/<name>.npy in float64, at most {DUMP_LIMIT_BYTES >> 20} MiB "
+                         "in all (beyond that a fixed, seeded subset of the samples, listed in DIR/sample_index.npy)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="1",
                     help="BASELINE.json configs[i] (default 1 = the headline metric's config) or d4 = north_star's literal "
                          "state_dim=4 cartpole; each at its whole population, sharded over --gpus")
@@ -488,7 +560,10 @@ def parse_args(argv=None):
     ap.add_argument("--test-hang-rank", type=int, default=-1, help=argparse.SUPPRESS)  # this rank's worker sleeps forever ...
     ap.add_argument("--test-hang-attempts", type=int, default=99, help=argparse.SUPPRESS)  # ... in attempts < this
     ap.add_argument("--dry-launch-no-fallback", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -624,8 +699,13 @@ def worker(args, result_fd):
     first_command_ms = (time.perf_counter() - t_first) * 1e3  # construction -> first action on the host (mppi_with_model.py:250-259)
     mark("first_command")
     preheat(one_step, args.preheat_ms, pg, coll_dev)
-    abuf = holder[0]
     mark("preheat_done")
+    # how many commands the time-boxed pre-heat took varies from run to run: the warm-up and timed steps start again from the
+    # planner's initial state (U = 0, zero action buffer, Philox command counter 0), so that the same arguments give the timed
+    # path the same inputs in every run (--dump-outputs compares two builds output for output)
+    planner.U = torch.zeros(T, nu, dtype=torch.float64)
+    planner._commands = 0
+    abuf = torch.zeros(B, nu, dtype=torch.float64)
     for _ in range(args.warmup):
         abuf = step(abuf)
     fence()
@@ -641,22 +721,29 @@ def worker(args, result_fd):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     mark("timed_done")
-    # second, untimed pass: the same steps with hipEvent pairs around every launch (on the launch stream)
-    planner.ctx.profile_reset()
-    planner.ctx.profile(True)
-    for _ in range(args.steps):
-        abuf = step(abuf)
-    fence()
-    planner.ctx.profile(False)
-    prof = planner.ctx.profile_read()
-    mark("profile_done")
-    kernels = {k: dict(avg_ms=v["total_ms"] / max(v["launches"], 1), launches=v["launches"],
-                       per_command_ms=v["total_ms"] / max(args.steps, 1)) for k, v in prof.items()}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed, read before anything else runs on the planner
+        dumped = write_outputs(args.dump_outputs, timed_path_outputs(planner, last_action[0]))
+        mark("outputs_written")
+    kernels = None
+    if args.full:
+        # second, untimed pass: the same steps with hipEvent pairs around every launch (on the launch stream)
+        planner.ctx.profile_reset()
+        planner.ctx.profile(True)
+        for _ in range(args.steps):
+            abuf = step(abuf)
+        fence()
+        planner.ctx.profile(False)
+        prof = planner.ctx.profile_read()
+        mark("profile_done")
+        kernels = {k: dict(avg_ms=v["total_ms"] / max(v["launches"], 1), launches=v["launches"],
+                           per_command_ms=v["total_ms"] / max(args.steps, 1)) for k, v in prof.items()}
 
     # the collective by itself (N > 1): the all-gather of 2 + T*nu doubles per rank exactly as a command issues it, timed
     # over 50 calls between fences -- torch.distributed's here; the library's own appears as kernels["rccl_all_gather"]
     coll_timing = None
-    if pg is not None:
+    if pg is not None and args.full:
         part = torch.zeros(2 + T * nu, dtype=torch.float64, device=f"cuda:{local}")
         gath = torch.empty(world * (2 + T * nu), dtype=torch.float64, device=f"cuda:{local}")
         from neurallaplacecontrol_amd.sharding import gather_partials
@@ -677,7 +764,7 @@ def worker(args, result_fd):
     mine = dict(rank=rank, local_rank=local, device=info["name"], torch_world=(dist.get_world_size(pg) if pg is not None else 1),
                 library_comm_world=int(planner.ctx.get_stat("comm_world")), native_collective=bool(planner.native_collective),
                 rollout_body=planner.rollout_body, fused_timeouts=planner.fused_timeouts, fused_fallbacks=planner.fused_fallbacks,
-                timed_s=elapsed_local, kernels_avg_ms={k: v["avg_ms"] for k, v in kernels.items()},
+                timed_s=elapsed_local, kernels_avg_ms=None if kernels is None else {k: v["avg_ms"] for k, v in kernels.items()},
                 collective_timing=coll_timing)
     per_rank = [mine]
     if pg is not None:
@@ -688,16 +775,16 @@ def worker(args, result_fd):
     # EXPERIMENTAL, reported beside the headline and never as `value`: the same steps with the encoder's hidden-state GEMMs as
     # int8-sliced fixed-point products on the INT8 matrix pipe (planner option gru_gemm = 1, csrc/kernels_gru_i8.hip)
     sliced = None
-    if world == 1 and headline and args.samples is None and not args.no_sliced_encoder:
+    if args.full and world == 1 and headline and args.samples is None and not args.no_sliced_encoder:
         sliced = sliced_encoder_child(args, local)
         mark("sliced_encoder_done")
     # (measured right behind the headline's own steps: the same thermal state, before the long stand-alone sections)
 
-    pmc_name, pj = load_pmc()
+    pmc_name, pj = load_pmc() if args.full else (None, None)
 
     # ---- stand-alone ILT kernel at N = K*T points (the BASELINE 'ILT GB/s vs HBM peak' figure; headline shape d=5)
     ilt = None
-    if rank == 0 and not args.no_ilt:
+    if args.full and rank == 0 and not args.no_ilt:
         ilt = standalone_ilt_section(nlc, local, pmc_name, pj)
         mark("ilt_done")
 
@@ -715,56 +802,58 @@ def worker(args, result_fd):
         return 0
 
     k_local = K_total // world
-    windows = k_local * T
-    g_hidden = HIDDEN // 2
-    nt3 = int(planner.ctx.get_stat("model_nt3"))
-    gru_need = flops_gru_needed_per_window(g_hidden, nu, B) * windows
-    gru_iss = flops_gru_issued_per_window(g_hidden, B) * windows
-    roll_need = flops_rollout_needed_per_sample_step(HIDDEN, d, S) * windows
-    roll_iss = flops_rollout_issued_per_sample_step(HIDDEN, nt3) * windows
+    roofline = None
+    if args.full:
+        windows = k_local * T
+        g_hidden = HIDDEN // 2
+        nt3 = int(planner.ctx.get_stat("model_nt3"))
+        gru_need = flops_gru_needed_per_window(g_hidden, nu, B) * windows
+        gru_iss = flops_gru_issued_per_window(g_hidden, B) * windows
+        roll_need = flops_rollout_needed_per_sample_step(HIDDEN, d, S) * windows
+        roll_iss = flops_rollout_issued_per_sample_step(HIDDEN, nt3) * windows
 
-    def mfma_entry(kernel, need, issued, alg_bytes, launches_per_command=1):
-        k = kernels[kernel]
-        sec = k["avg_ms"] * 1e-3
-        need, issued, alg_bytes = need / launches_per_command, issued / launches_per_command, alg_bytes / launches_per_command
-        traffic, src = (pmc_traffic(pmc_name, pj, kernel) if headline and k_local == K_SAMPLES and kernel in PMC_KEYS else (None, None))
-        return dict(bound="mfma", achieved=need / sec / 1e12, peak=FP64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
-                    frac=need / sec / 1e12 / FP64_MFMA_PEAK_TFLOPS, traffic=traffic, traffic_source=src,
-                    kernel=kernel, avg_launch_ms=k["avg_ms"], flops_per_launch=need,
-                    issued_flops_per_launch=issued, frac_issued=issued / sec / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-                    algorithmic_hbm_bytes=alg_bytes,
-                    note="achieved/frac count the algorithm's flops (SURVEY 8d, W_hh h0 = 0 products skipped); "
-                         "frac_issued counts the MFMAs the kernel executes (16-wide tile padding included)")
+        def mfma_entry(kernel, need, issued, alg_bytes, launches_per_command=1):
+            k = kernels[kernel]
+            sec = k["avg_ms"] * 1e-3
+            need, issued, alg_bytes = need / launches_per_command, issued / launches_per_command, alg_bytes / launches_per_command
+            traffic, src = (pmc_traffic(pmc_name, pj, kernel) if headline and k_local == K_SAMPLES and kernel in PMC_KEYS else (None, None))
+            return dict(bound="mfma", achieved=need / sec / 1e12, peak=FP64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
+                        frac=need / sec / 1e12 / FP64_MFMA_PEAK_TFLOPS, traffic=traffic, traffic_source=src,
+                        kernel=kernel, avg_launch_ms=k["avg_ms"], flops_per_launch=need,
+                        issued_flops_per_launch=issued, frac_issued=issued / sec / 1e12 / FP64_MFMA_PEAK_TFLOPS,
+                        algorithmic_hbm_bytes=alg_bytes,
+                        note="achieved/frac count the algorithm's flops (SURVEY 8d, W_hh h0 = 0 products skipped); "
+                             "frac_issued counts the MFMAs the kernel executes (16-wide tile padding included)")
 
-    if "nl_plan_fused_kernel" in kernels:
-        # small shard: GRU encode and split rollout are roles of ONE launch (kernels_fused.hip)
-        roofline = mfma_entry("nl_plan_fused_kernel", gru_need + roll_need, gru_iss + roll_iss,
-                              (8 * nu + 16 + 16 + 8 * (2 * nu + d)) * windows)
-    else:
-        roofline = mfma_entry("gru_encode_kernel", gru_need, gru_iss, (8 * nu + 16) * windows)
-        if "nl_rollout_kernel" in kernels:
-            roofline["also"] = mfma_entry("nl_rollout_kernel", roll_need, roll_iss, (16 + 8 * (2 * nu + d)) * windows)
-        elif "nl_repfunc_kernel" in kernels:
-            # staged step chain (de Hoog): the representation MLP is one launch per horizon step and stream part; F_k leaves
-            # the launch (2 d S doubles per sample-step written, read again by the de Hoog kernel)
-            n_launch = max(kernels["nl_repfunc_kernel"]["launches"] // max(args.steps, 1), 1)
-            roofline["also"] = mfma_entry("nl_repfunc_kernel", roll_need - 2 * d * S * windows, roll_iss - 2 * nt3 * 128 * windows,
-                                          (16 + 8 * d + 16 * d * S) * windows, launches_per_command=n_launch)
-    # whole step against the same roof: every algorithmic flop of one command() (GRU encode + rollout, all ranks) over the
-    # measured wall time per step -- the sampling / weighting / merge kernels add time but no matrix flops (nor does the
-    # de Hoog recurrence: FP64 VALU work, not counted)
-    step_flops = (gru_need + roll_need) * world
-    roofline["step"] = dict(flops=step_flops, achieved=step_flops / (elapsed / args.steps) / 1e12, peak=FP64_MFMA_PEAK_TFLOPS * world,
-                            unit="TFLOP/s", frac=step_flops / (elapsed / args.steps) / 1e12 / (FP64_MFMA_PEAK_TFLOPS * world),
-                            note="algorithmic flops of one command() (GRU encode + rollout; SURVEY 8d) / ms_per_step / FP64-MFMA peak")
+        if "nl_plan_fused_kernel" in kernels:
+            # small shard: GRU encode and split rollout are roles of ONE launch (kernels_fused.hip)
+            roofline = mfma_entry("nl_plan_fused_kernel", gru_need + roll_need, gru_iss + roll_iss,
+                                  (8 * nu + 16 + 16 + 8 * (2 * nu + d)) * windows)
+        else:
+            roofline = mfma_entry("gru_encode_kernel", gru_need, gru_iss, (8 * nu + 16) * windows)
+            if "nl_rollout_kernel" in kernels:
+                roofline["also"] = mfma_entry("nl_rollout_kernel", roll_need, roll_iss, (16 + 8 * (2 * nu + d)) * windows)
+            elif "nl_repfunc_kernel" in kernels:
+                # staged step chain (de Hoog): the representation MLP is one launch per horizon step and stream part; F_k leaves
+                # the launch (2 d S doubles per sample-step written, read again by the de Hoog kernel)
+                n_launch = max(kernels["nl_repfunc_kernel"]["launches"] // max(args.steps, 1), 1)
+                roofline["also"] = mfma_entry("nl_repfunc_kernel", roll_need - 2 * d * S * windows, roll_iss - 2 * nt3 * 128 * windows,
+                                              (16 + 8 * d + 16 * d * S) * windows, launches_per_command=n_launch)
+        # whole step against the same roof: every algorithmic flop of one command() (GRU encode + rollout, all ranks) over the
+        # measured wall time per step -- the sampling / weighting / merge kernels add time but no matrix flops (nor does the
+        # de Hoog recurrence: FP64 VALU work, not counted)
+        step_flops = (gru_need + roll_need) * world
+        roofline["step"] = dict(flops=step_flops, achieved=step_flops / (elapsed / args.steps) / 1e12, peak=FP64_MFMA_PEAK_TFLOPS * world,
+                                unit="TFLOP/s", frac=step_flops / (elapsed / args.steps) / 1e12 / (FP64_MFMA_PEAK_TFLOPS * world),
+                                note="algorithmic flops of one command() (GRU encode + rollout; SURVEY 8d) / ms_per_step / FP64-MFMA peak")
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(sd_cpu, cfg, args.cpu_budget)
         mark("cpu_baseline_done")
     # the other BASELINE configs, each at its whole population on this GPU, in the SAME driver-run line (VERDICT r4 missing 3):
     # short fenced loops, no profiling pass, no CPU baseline -- `bench.py --config k` gives each one's full line
     others = None
-    if world == 1 and headline and args.samples is None and not args.no_other_configs:
+    if args.full and world == 1 and headline and args.samples is None and not args.no_other_configs:
         others = other_configs_section(nlc, local)
         mark("other_configs_done")
     workload = (f"{env_name} (nx={d}, nu={nu}), K={K_total} MPPI samples sharded over the ranks, H={T}, "
@@ -791,7 +880,7 @@ def worker(args, result_fd):
         config=dict(workload=workload, baseline_config=args.config, samples_per_gpu=k_local, noise="device Philox4x32-10",
                     device=info["name"], commit=git_commit(), library_build=bi or None, preheat_ms=args.preheat_ms,
                     store_rollouts=bool(planner.store_rollouts), first_command_ms=first_command_ms,
-                    last_action=action_after_timed,
+                    last_action=action_after_timed, full=args.full, dump_outputs=dumped,
                     planner_options=(args.planner_opt or None),
                     attempt=args.attempt, native_collective=bool(planner.native_collective),
                     collective=None if pg is None else ("rccl all-gather inside nlc_mppi_finish (library communicator)"
@@ -804,7 +893,8 @@ def worker(args, result_fd):
         roofline_ilt=ilt,
         cpu_baseline=cpu,
         kernels_avg_ms=kernels,
-        kernels_note="per-launch hipEvent averages from a second, untimed pass of the same steps",
+        kernels_note=("per-launch hipEvent averages from a second, untimed pass of the same steps" if args.full else
+                      "the profiled pass and every section beside the headline run with --full"),
         other_configs=others,
         encoder_int8_sliced=sliced,
     )

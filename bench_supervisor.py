@@ -218,11 +218,13 @@ def supervise(args, argv, result_fd):
         want_also = False
         if rank == 0:
             native = bool((final.get("config") or {}).get("native_collective"))
-            want_also = bool(native and world > 1 and first == "auto" and not args.no_also_collective and not args.dry_launch)
+            want_also = bool(native and world > 1 and first == "auto" and args.full and not args.no_also_collective
+                             and not args.dry_launch)
             sup.set("also", int(want_also))
         want_also = sup.get("also", 120.0) == "1"
         if want_also:
-            ok2, line2, results2 = attempt(1, "torch", ("--no-ilt", "--no-cpu-baseline"))
+            # (the outputs of the timed steps are the first attempt's: this one writes none)
+            ok2, line2, results2 = attempt(1, "torch", ("--no-ilt", "--no-cpu-baseline", "--dump-outputs", ""))
             if rank == 0:
                 if ok2:
                     l2 = json.loads(line2)

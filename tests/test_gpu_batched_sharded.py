@@ -568,7 +568,7 @@ def test_bench_ranks_rehearsed_on_one_gpu(ranks, samples):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(ranks), "--rehearse-on-one-gpu", "--steps", "12",
-                          "--warmup", "2", "--preheat-ms", "40", "--no-ilt", "--no-cpu-baseline", "--samples", str(samples)],
+                          "--warmup", "2", "--preheat-ms", "40", "--full", "--no-ilt", "--no-cpu-baseline", "--samples", str(samples)],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
@@ -613,7 +613,8 @@ def test_bench_config3_shards_rehearsed_on_one_gpu():
     shard SIZE, body and payload of the 8-GPU run); the eight-shard merge itself is test_config3_eight_shards_merge_equals_the_
     whole_population below.  Same command count on both runs (no time-boxed pre-heat), device Philox noise (G-invariant):
     the sharded run's action equals the one-GPU whole-population action."""
-    common = ["--config", "3", "--samples", "131072", "--steps", "3", "--warmup", "1", "--preheat-ms", "0", "--no-ilt", "--no-cpu-baseline"]
+    common = ["--config", "3", "--samples", "131072", "--steps", "3", "--warmup", "1", "--preheat-ms", "0", "--full", "--no-ilt",
+              "--no-cpu-baseline"]
     rec = _bench_line(["--gpus", "4", "--rehearse-on-one-gpu"] + common)
     assert rec["n_gpus"] == 4 and rec["steps"] == 3 and rec["value"] > 0 and rec["config"]["samples_per_gpu"] == 32768
     assert "acrobot" in rec["config"]["workload"] and "H=60" in rec["config"]["workload"] and rec["config"]["baseline_config"] == "3"

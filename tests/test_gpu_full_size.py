@@ -389,17 +389,18 @@ def test_untamed_random_weights_short_horizon(nlc, env):
 
 @pytest.mark.parametrize("key", ["0", "d4"])
 def test_bench_other_configs_emit_a_complete_line(key):
-    """`bench.py --config k` measures the other BASELINE configs at their own population with the same contract
-    fields, its own roofline (dominant kernel + whole step) and a CPU baseline on a budget; `config.commit` is never null and the
-    library's source hash travels with the line."""
+    """`bench.py --config k --full` measures the other BASELINE configs at their own population with the same
+    contract fields, its own roofline (dominant kernel + whole step) and a CPU baseline on a budget; `config.commit` is never null
+    and the library's source hash travels with the line."""
     import json
     import subprocess
     import sys
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--config", key, "--steps", "10", "--warmup", "2", "--no-ilt",
-                          "--cpu-budget", "8", "--preheat-ms", "50"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--config", key, "--steps", "10", "--warmup", "2", "--full",
+                          "--no-ilt", "--cpu-budget", "8", "--preheat-ms", "50"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -414,3 +415,40 @@ def test_bench_other_configs_emit_a_complete_line(key):
     cpu = rec["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["cores"] >= 1 and (cpu["value"] or cpu["value_extrapolated"]) and "sample" in cpu
     assert rec["config"]["ranks_seen"]["per_rank"][0]["rollout_body"] == ("fused" if key == "0" else "wave-per-tile")
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py` without --full times the headline steps and nothing else: the contract fields, null for every other section.
+    `--dump-outputs DIR` writes what the last timed step computed; two runs with the same arguments (time-boxed pre-heat
+    included) write the same arrays, so that two builds can be compared output for output."""
+    import json
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    recs = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--config", "0", "--steps", "6", "--warmup", "2",
+                              "--preheat-ms", "30" if run == "a" else "120", "--dump-outputs", str(tmp_path / run)], env=env,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert out.returncode == 0, out.stderr.decode()[-3000:]
+        lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec["steps"] == 6 and rec["value"] > 0 and rec["unit"] == "planning steps/s" and rec["higher_is_better"] is True
+        assert rec["dtype"] == "f64" and abs(rec["ms_per_step"] * rec["value"] - 1e3) < 1e-6 * 1e3
+        for key in ("roofline", "roofline_ilt", "cpu_baseline", "kernels_avg_ms", "other_configs", "encoder_int8_sliced"):
+            assert rec[key] is None, key
+        assert rec["config"]["full"] is False and rec["config"]["dump_outputs"]["samples_written"] == 1024
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert {"action.npy", "U.npy", "states.npy", "actions.npy", "cost_total.npy", "omega.npy", "noise.npy"} <= set(names)
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == names
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64 and np.all(np.isfinite(a)), name
+        np.testing.assert_allclose(a, b, rtol=1e-12, atol=0, err_msg=name)
+    np.testing.assert_allclose(np.load(tmp_path / "a" / "action.npy"), recs[0]["config"]["last_action"], rtol=0, atol=0)
+    assert np.load(tmp_path / "a" / "states.npy").shape == (1024, 20, 5)

@@ -341,3 +341,72 @@ def test_bench_sliced_encoder_section_failure_does_not_cost_the_line():
     args = bench.parse_args(["--steps", "2", "--warmup", "1"])
     rec = bench.sliced_encoder_child(args, 0, timeout_s=300)
     assert isinstance(rec, dict) and "error" in rec and "value" not in rec
+
+
+def test_bench_options_plain_by_default():
+    """A plain `bench.py` run is the headline alone: --full (every other section) is off unless asked for, --dump-outputs is
+    off, and --steps sets the number of timed steps (at least one)."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_bench_write_outputs_sizes_and_sampling(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; past the byte limit every per-sample array keeps the SAME fixed,
+    seeded rows (sample_index.npy), the whole directory stays under the limit, and a later unsampled run removes the index."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    K, T = 4096, 8
+    g = np.random.default_rng(3)
+    arrays = {"action": (np.array([0.25]), False), "U": (g.standard_normal((T, 1)), False),
+              "states": (g.standard_normal((K, T, 5)), True), "cost_total": (np.arange(K, dtype=np.float64), True)}
+    limit = 256 << 10
+    info = bench.write_outputs(str(tmp_path / "a"), arrays, limit_bytes=limit)
+    assert info["samples"] == K and 0 < info["samples_written"] < K
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["U.npy", "action.npy", "cost_total.npy", "sample_index.npy", "states.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= limit
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    rows = idx.astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "cost_total.npy"), arrays["cost_total"][0][rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "states.npy"), arrays["states"][0][rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "U.npy"), arrays["U"][0])
+    # the same arrays again: the same rows (fixed seed), byte for byte
+    bench.write_outputs(str(tmp_path / "b"), arrays, limit_bytes=limit)
+    for name in files:
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes(), name
+    # under the limit: everything, and no index left behind from the sampled run
+    info = bench.write_outputs(str(tmp_path / "a"), arrays)
+    assert info["samples_written"] == K and not (tmp_path / "a" / "sample_index.npy").exists()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "states.npy"), arrays["states"][0])
+
+
+def test_bench_commit_is_never_null_without_git(monkeypatch):
+    """`config.commit` in a checkout without git metadata and without a commit recorded at build time: the sources by content."""
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    def no_git(*a, **kw):
+        raise FileNotFoundError("git")
+
+    monkeypatch.setattr(bench.subprocess, "check_output", no_git)
+    monkeypatch.setattr(bench, "build_info", lambda: {})
+    monkeypatch.delenv("NLC_COMMIT", raising=False)
+    c = bench.git_commit()
+    assert c and "no git metadata" in c
+    monkeypatch.undo()
+    assert bench.source_tree_sha() == bench.source_tree_sha() and len(bench.source_tree_sha()) == 16
