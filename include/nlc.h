@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 9
+#define NLC_ABI_VERSION 10
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -270,6 +270,34 @@ int nlc_model_forward_const_t(nlc_ctx* ctx, const double* obs_dev, const double*
  * supplies, as torchlaplace hands them to the module -- -> theta_dev, phi_dev (N, d, S) with theta = pi tanh(.),
  * phi = (pi/2) tanh(.) (:59-62).  Same MFMA kernel as the de Hoog path's representation stage. */
 int nlc_rep_func(nlc_ctx* ctx, const double* rep_in_dev, int64_t N, double* theta_dev, double* phi_dev);
+
+/* ---- training: one iteration of the reference's loop over a NeuralLaplaceModel (train_utils.py:388-408, float64 as
+ *      model.double() at :267): pred = model(bs0, ba0, bts); loss = MSELoss(pred.squeeze(), bsd.squeeze()); backward;
+ *      clip_grad_norm_(params, max_grad_norm); Adam.step().  The shape comes from nlc_set_model on the same ctx; the kernels
+ *      take what it takes with the Fourier ILT (any other algorithm, or B > 16: NLC_ERR_UNSUPPORTED).
+ *   params_dev, grad_dev, m_dev, v_dev: flat device arrays of nlc_model_blob_size doubles in nlc_set_model's blob order.
+ *   obs_dev (M, d), window_dev (M, B, nin) raw actions, ts_dev (M) raw ts_pred, target_dev (M, d) = bsn - bs0 of the dataset;
+ *   idx_dev (N) int64 row indices into them (the reference's permutation[iter*bs : iter*bs+bs], no gather copy).
+ *   ws_dev: scratch of nlc_train_workspace_bytes(ctx, N).  Asynchronous on the ctx's stream; bit-reproducible (no
+ *   floating-point atomics). */
+typedef struct {
+  double lr;            /* Adam lr (train_utils.py:281: config.learning_rate) */
+  double beta1, beta2;  /* Adam betas (0.9, 0.999) */
+  double eps;           /* Adam eps (1e-8) */
+  double weight_decay;  /* L2 added to the clipped gradient inside the step, as torch.optim.Adam (0) */
+  double max_grad_norm; /* clip_grad_norm_'s max_norm (config.clip_grad_norm = 0.1); <= 0: no clipping */
+} nlc_train_desc;
+int64_t nlc_train_workspace_bytes(nlc_ctx* ctx, int64_t N);
+/* loss and gradient only (train_utils.py:391-402): grad_dev (blob order) = d loss / d params, loss_dev (0-dim) = the MSE */
+int nlc_train_loss_grad(nlc_ctx* ctx, const double* params_dev, const double* obs_dev, const double* window_dev,
+                        const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
+                        double* grad_dev, double* loss_dev, void* ws_dev);
+/* the whole iteration (train_utils.py:391-404): params_dev, m_dev (exp_avg), v_dev (exp_avg_sq) updated in place; step = the
+ * Adam step count of this update (1 for the first); loss_dev the MSE before the update, gradnorm_dev (may be NULL) the total
+ * gradient norm before clipping (clip_grad_norm_'s return value). */
+int nlc_train_step(nlc_ctx* ctx, const nlc_train_desc* desc, double* params_dev, double* m_dev, double* v_dev, int64_t step,
+                   const double* obs_dev, const double* window_dev, const double* ts_dev, const double* target_dev,
+                   const int64_t* idx_dev, int64_t N, int B, double* loss_dev, double* gradnorm_dev, void* ws_dev);
 
 /* ---- baseline models: DeltaTRNN (train_utils.py:589-631; factory :56-74) and RNN (:550-586; factory :77-98);
  *      rnn_hidden_units config.py:43 ------

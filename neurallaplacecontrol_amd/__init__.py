@@ -5,6 +5,7 @@ Drop-in mirrors of the reference's Python interfaces for this path (SURVEY.md §
     from neurallaplacecontrol_amd import MPPIDelay              # planners/mppi_delay.py:54
     from neurallaplacecontrol_amd import NeuralLaplaceModel     # w_nl.py:66
     from neurallaplacecontrol_amd import laplace_reconstruct    # torchlaplace (external)
+    from neurallaplacecontrol_amd import NLTrainer              # train_utils.py:388-408 (fused training step)
     from neurallaplacecontrol_amd import DeltaTRNN, NODE        # train_utils.py:589, :664 (baseline models)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of ``libnlc_hip.so``
@@ -18,6 +19,7 @@ from .laplace import ilt_reconstruct, laplace_reconstruct, rep_func_inputs  # no
 from .nl_model import LaplaceRepresentationFunc, NeuralLaplaceModel, ReverseGRUEncoder  # noqa: F401
 from .node_model import NODE, xOdeFuncInXAndU  # noqa: F401
 from .rnn_model import RNN, DeltaTRNN  # noqa: F401
+from .training import NLTrainer  # noqa: F401
 from .planners.mppi_batch import BatchedMPPIDelay  # noqa: F401
 from .planners.mppi_delay import MPPIDelay  # noqa: F401
 
@@ -26,6 +28,7 @@ __all__ = [
     "BatchedMPPIDelay",
     "BatchedEnv",
     "NeuralLaplaceModel",
+    "NLTrainer",
     "DeltaTRNN",
     "RNN",
     "NODE",

@@ -57,6 +57,9 @@ SYMBOLS = [
     "nlc_model_forward",
     "nlc_model_forward_const_t",
     "nlc_rep_func",
+    "nlc_train_workspace_bytes",
+    "nlc_train_loss_grad",
+    "nlc_train_step",
     "nlc_rnn_blob_size",
     "nlc_set_rnn_model",
     "nlc_rnn_forward",
@@ -126,6 +129,11 @@ class ModelDesc(C.Structure):
         ("action_mean", C.c_double * NLC_MAX_NIN),
         ("action_std", C.c_double * NLC_MAX_NIN),
     ]
+
+
+class TrainDesc(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("max_grad_norm", C.c_double)]
 
 
 class MppiDesc(C.Structure):
@@ -214,6 +222,10 @@ def load_library():
         lib.nlc_model_workspace_bytes.restype = i64
         lib.nlc_model_forward.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp]
         lib.nlc_model_forward_const_t.argtypes = [vp, vp, vp, dbl, i64, i32, vp, vp]
+        lib.nlc_train_workspace_bytes.argtypes = [vp, i64]
+        lib.nlc_train_workspace_bytes.restype = i64
+        lib.nlc_train_loss_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
+        lib.nlc_train_step.argtypes = [vp, P(TrainDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]
         lib.nlc_rnn_blob_size.restype = i64
         lib.nlc_set_rnn_model.argtypes = [vp, P(RnnDesc), vp, i64]

@@ -1,0 +1,486 @@
+// Fused training step of NeuralLaplaceModel with the Fourier ILT: one iteration of the reference's training loop
+// (train_utils.py:388-408: model(bs0, ba0, bts), MSELoss, backward, clip_grad_norm_, Adam.step), float64 throughout
+// (model.double(), train_utils.py:267).  Three launches, no host synchronisation:
+//
+//   train_fwd_bwd_kernel  one workgroup per 16-row tile (a workgroup walks tiles b, b + G, ... when N needs more than
+//                         kMaxBlocks tiles): rows gathered through the int64 index array, normalisation as
+//                         nlc_model_forward, 2-layer reverse GRU with its gates taped, linear_out, per-row query points,
+//                         representation MLP, sphere map, Fourier line integral at the row's own t, squared error; then
+//                         the backward in reverse order: ILT, sphere map, MLP, linear_out, GRU backprop through time over
+//                         both layers.  Weight gradients are sums over the tile's samples (rows; rows x window steps for the
+//                         GRU) on the FP64 matrix cores (v_mfma_f64_16x16x4_f64), accumulated onto the workgroup's partial
+//                         in state_dict blob order.
+//   train_reduce_kernel   partials summed in workgroup order (no atomics: bit-reproducible), per-chunk sums of squares,
+//                         the loss.
+//   train_adam_kernel     per-tensor norms, their norm, clip_grad_norm_'s coefficient, torch.optim.Adam's update.
+//
+// Elementary functions: gates and hidden activations use nlc_math.h's sigmoid_d / tanh_d (<= 4 ulp against libm on the
+// whole line, tests/test_math_host.py); the sphere map's tanh is tanh_d; tan / sin / cos / exp / atan2 / asin of the query
+// points and the line integral are the device library's.  tests/test_gpu_train.py holds the loss to 1e-12 relative and every
+// gradient to 1e-9 of its tensor's max |grad| against float64 autograd on the CPU.
+//
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage): train_fwd_bwd_kernel 256 VGPRs + AGPRs and 68 B/lane of scratch,
+// not yet traced to its source; one wave per SIMD.  The kernel is latency-bound at 2.3 ms per batch-16 iteration
+// (docs/training.md): the next step is LDS-resident activations and MFMA forward products, not this scratch.
+#include "nlc_device.h"
+#include "nlc_train.h"
+
+namespace nlc {
+namespace train {
+
+namespace {
+
+constexpr int kWaves = kThreads / 64;
+
+// out[m][k] (+)= sum_s D[s * ldD + m] * X[s * ldX + k]  (m < M, k < K, s < ns) on v_mfma_f64_16x16x4_f64: samples are the
+// k dimension of the MFMA (4 per instruction), 16 x 16 output tiles dealt round-robin to the workgroup's waves.  first: the
+// accumulator starts at 0, else at the values already in out (the workgroup's earlier tiles).
+__device__ void wgrad_mfma(double* __restrict__ out, int M, int K, int ns, const double* __restrict__ D, int ldD,
+                           const double* __restrict__ X, int ldX, bool first) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = lane >> 4, c = lane & 15;
+  const int mt = (M + 15) >> 4, kt = (K + 15) >> 4;
+  for (int tile = wave; tile < mt * kt; tile += kWaves) {
+    const int m0 = (tile / kt) << 4, k0 = (tile % kt) << 4;
+    v4d acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + q + 4 * r, col = k0 + c;
+      acc[r] = (!first && row < M && col < K) ? out[(int64_t)row * K + col] : 0.0;
+    }
+    const bool am = m0 + c < M, bk = k0 + c < K;
+#pragma unroll 4
+    for (int s0 = 0; s0 < ns; s0 += 4) {
+      const int s = s0 + q;
+      const double a = (s < ns && am) ? D[(int64_t)s * ldD + m0 + c] : 0.0;
+      const double b = (s < ns && bk) ? X[(int64_t)s * ldX + k0 + c] : 0.0;
+      acc = mfma(a, b, acc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + q + 4 * r, col = k0 + c;
+      if (row < M && col < K) out[(int64_t)row * K + col] = acc[r];
+    }
+  }
+}
+
+// out[m] (+)= sum_s D[s * ldD + m], samples in order
+__device__ void bgrad(double* __restrict__ out, int M, int ns, const double* __restrict__ D, int ldD, bool first) {
+  for (int m = threadIdx.x; m < M; m += kThreads) {
+    double acc = first ? 0.0 : out[m];
+#pragma unroll 8
+    for (int s = 0; s < ns; ++s) acc += D[(int64_t)s * ldD + m];
+    out[m] = acc;
+  }
+}
+
+// one GRU layer forward over the B window steps of the tile: X [s][r][din] inputs, H [s][r][g] states (H[0] = 0 on entry),
+// G [s][r][4g] tape
+__device__ void gru_layer_fwd(const TrainArgs& a, const double* __restrict__ W, const double* X, int din, double* H, double* G) {
+  const int g = a.g;
+  const double* Wih = W;
+  const double* Whh = W + (int64_t)3 * g * din;
+  const double* bih = Whh + (int64_t)3 * g * g;
+  const double* bhh = bih + 3 * g;
+  for (int s = 0; s < a.B; ++s) {
+    for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
+      const int r = p & (kRows - 1), j = p >> 4;
+      const double* x = X + ((int64_t)s * kRows + r) * din;
+      const double* hp = H + ((int64_t)s * kRows + r) * g;
+      double ir = 0.0, iz = 0.0, in_ = 0.0, hr = 0.0, hz = 0.0, hn = 0.0;
+      for (int c = 0; c < din; ++c) {
+        const double xc = x[c];
+        ir += Wih[(int64_t)j * din + c] * xc;
+        iz += Wih[(int64_t)(g + j) * din + c] * xc;
+        in_ += Wih[(int64_t)(2 * g + j) * din + c] * xc;
+      }
+#pragma unroll 8
+      for (int c = 0; c < g; ++c) {
+        const double hc = hp[c];
+        hr += Whh[(int64_t)j * g + c] * hc;
+        hz += Whh[(int64_t)(g + j) * g + c] * hc;
+        hn += Whh[(int64_t)(2 * g + j) * g + c] * hc;
+      }
+      ir += bih[j];
+      iz += bih[g + j];
+      in_ += bih[2 * g + j];
+      hr += bhh[j];
+      hz += bhh[g + j];
+      hn += bhh[2 * g + j];
+      const double rr = m::sigmoid_d(ir + hr);
+      const double zz = m::sigmoid_d(iz + hz);
+      const double nn = m::tanh_d(in_ + rr * hn);
+      const double hnew = (1.0 - zz) * nn + zz * hp[j];
+      double* tape = G + ((int64_t)s * kRows + r) * 4 * g;
+      tape[j] = rr;
+      tape[g + j] = zz;
+      tape[2 * g + j] = nn;
+      tape[3 * g + j] = hn;
+      H[((int64_t)(s + 1) * kRows + r) * g + j] = hnew;
+    }
+    __syncthreads();
+  }
+}
+
+// backprop through time of one GRU layer: dhA [r][g] holds dL/dh_B on entry (layer 1; 0 for layer 0), DXin [s][r][g] the
+// gradient reaching the layer's OUTPUT at step s from above (layer 0: layer 1's input gradient; NULL for layer 1).
+// Writes the gate gradients DI / DH [s][r][3g] and, if DXout != NULL, the gradient of the layer's INPUT at every step.
+__device__ void gru_layer_bwd(const TrainArgs& a, const double* __restrict__ W, int din, const double* H, const double* G,
+                              double* DI, double* DH, const double* DXin, double* DXout, double* dhA, double* dD) {
+  const int g = a.g, g3 = 3 * g;
+  const double* Wih = W;
+  const double* Whh = W + (int64_t)3 * g * din;
+  for (int s = a.B - 1; s >= 0; --s) {
+    for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
+      const int r = p & (kRows - 1), j = p >> 4;
+      const int64_t sr = (int64_t)s * kRows + r;
+      double dh = dhA[r * g + j];
+      if (DXin) dh += DXin[sr * g + j];
+      const double* tape = G + sr * 4 * g;
+      double gr, gz, gn, ghn, dd;
+      gru_cell_bwd(dh, tape[j], tape[g + j], tape[2 * g + j], tape[3 * g + j], H[sr * g + j], &gr, &gz, &gn, &ghn, &dd);
+      DI[sr * g3 + j] = gr;
+      DI[sr * g3 + g + j] = gz;
+      DI[sr * g3 + 2 * g + j] = gn;
+      DH[sr * g3 + j] = gr;
+      DH[sr * g3 + g + j] = gz;
+      DH[sr * g3 + 2 * g + j] = ghn;
+      dD[r * g + j] = dd;
+    }
+    __syncthreads();
+    if (s > 0) {
+      for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
+        const int r = p & (kRows - 1), i = p >> 4;
+        const double* dgh = DH + ((int64_t)s * kRows + r) * g3;
+        double acc = 0.0;
+#pragma unroll 8
+        for (int j = 0; j < g3; ++j) acc += Whh[(int64_t)j * g + i] * dgh[j];
+        dhA[r * g + i] = dD[r * g + i] + acc;
+      }
+    }
+    if (DXout) {
+      for (int p = threadIdx.x; p < kRows * din; p += kThreads) {
+        const int r = p & (kRows - 1), i = p >> 4;
+        const double* dgi = DI + ((int64_t)s * kRows + r) * g3;
+        double acc = 0.0;
+#pragma unroll 8
+        for (int j = 0; j < g3; ++j) acc += Wih[(int64_t)j * din + i] * dgi[j];
+        DXout[((int64_t)s * kRows + r) * din + i] = acc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// out[r][j] = tanh(sum_i W[j][i] in[r][i] + b[j])  (j < M, i < K)
+__device__ void dense_tanh(const double* __restrict__ W, const double* __restrict__ b, const double* in, int K, int M, double* out) {
+  for (int p = threadIdx.x; p < kRows * M; p += kThreads) {
+    const int r = p & (kRows - 1), j = p >> 4;
+    const double* x = in + (int64_t)r * K;
+    const double* w = W + (int64_t)j * K;
+    double acc = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < K; ++i) acc += w[i] * x[i];
+    out[(int64_t)r * M + j] = m::tanh_d(acc + b[j]);
+  }
+}
+
+// delta[r][i] = (sum_j W[j][i] dout[r][j]) * (1 - y[r][i]^2)  (W is M x K, i < K)
+__device__ void dense_tanh_bwd(const double* __restrict__ W, const double* dout, int K, int M, const double* y, double* delta) {
+  for (int p = threadIdx.x; p < kRows * K; p += kThreads) {
+    const int r = p & (kRows - 1), i = p >> 4;
+    const double* dz = dout + (int64_t)r * M;
+    double acc = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < M; ++j) acc += W[(int64_t)j * K + i] * dz[j];
+    const double yy = y[(int64_t)r * K + i];
+    delta[(int64_t)r * K + i] = acc * (1.0 - yy * yy);
+  }
+}
+
+// c_k = cos(theta + k pi/2) and its theta derivative, from one sincos (exact quarter turns: ILT scale 2)
+__device__ __forceinline__ void quarter(double th, int k, double* c, double* cp) {
+  double sn, cs;
+  sincos(th, &sn, &cs);
+  switch (k & 3) {
+    case 0: *c = cs; *cp = -sn; break;
+    case 1: *c = -sn; *cp = -cs; break;
+    case 2: *c = -cs; *cp = sn; break;
+    default: *c = sn; *cp = cs; break;
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs a) {
+  const int d = a.d, nin = a.nin, g = a.g, h = a.h, S = a.S, B = a.B;
+  const int K0 = 2 * S + d + 2, O = 2 * d * S;
+  const ActLayout& L = a.L;
+  double* ws = a.act + (int64_t)blockIdx.x * a.A;
+  double* X0 = ws + L.X0;
+  double* H0 = ws + L.H0;
+  double* G0 = ws + L.G0;
+  double* H1 = ws + L.H1;
+  double* G1 = ws + L.G1;
+  double* a0 = ws + L.a0;
+  double* a1 = ws + L.a1;
+  double* a2 = ws + L.a2;
+  double* u = ws + L.u;
+  double* d3 = ws + L.d3;
+  double* d2 = ws + L.d2;
+  double* d1 = ws + L.d1;
+  double* denc = ws + L.denc;
+  double* tn = ws + L.tn;
+  double* tgt = ws + L.tgt;
+  double* sq = ws + L.sq;
+  double* DI0 = ws + L.DI0;
+  double* DH0 = ws + L.DH0;
+  double* DI1 = ws + L.DI1;
+  double* DH1 = ws + L.DH1;
+  double* DX1 = ws + L.DX1;
+  double* dhA = ws + L.dhA;
+  double* dD = ws + L.dD;
+  const double* prm = a.params;
+  const int64_t* off = a.off;
+  double* part = a.partial + (int64_t)blockIdx.x * a.P;
+  const double loss_norm = 2.0 / ((double)a.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
+  const double scale = 2.0;
+
+  for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const bool first = tile == (int)blockIdx.x;
+    const int64_t row0 = (int64_t)tile * kRows;
+    // ---- inputs: gathered rows, normalised as nlc_model_forward (w_nl.py:120-131); rows past N are zeros at t = 1 (finite
+    // everywhere, and their loss gradient is 0)
+    for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
+      const int r = p & (kRows - 1), e = p >> 4;
+      const bool valid = row0 + r < a.N;
+      const int64_t src = valid ? a.idx[row0 + r] : 0;
+      if (e < B * nin) {
+        const int s = e / nin, c = e - s * nin;  // step s of the reversed window = window row B - 1 - s
+        X0[((int64_t)s * kRows + r) * nin + c] =
+            valid ? (a.window[(src * B + (B - 1 - s)) * nin + c] - a.am[c]) / a.as[c] : 0.0;
+      } else if (e < B * nin + d) {
+        const int c = e - B * nin;
+        a0[(int64_t)r * K0 + 2 * S + c] = valid ? (a.obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
+        tgt[r * d + c] = valid ? a.target[src * d + c] : 0.0;
+      } else {
+        tn[r] = valid ? a.ts[src] / a.time_div : 1.0;
+      }
+    }
+    for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
+      H0[p] = 0.0;
+      H1[p] = 0.0;
+      dhA[p] = 0.0;
+    }
+    __syncthreads();
+    // ---- query points s_k = gamma + i pi k / T of the row's t on the Riemann sphere (as rep_inputs_kernel)
+    for (int p = threadIdx.x; p < kRows * S; p += kThreads) {
+      const int r = p & (kRows - 1), k = p >> 4;
+      const double t = tn[r], Tt = scale * t;
+      const double gamma = a.alpha - a.log_tol / (scale * Tt);
+      const double im = kPi * (double)k / Tt;
+      const double a2v = gamma * gamma + im * im;
+      a0[(int64_t)r * K0 + k] = atan2(im, gamma);
+      a0[(int64_t)r * K0 + S + k] = asin((a2v - 1.0) / (a2v + 1.0));
+    }
+    // ---- reverse GRU encoder (w_nl.py:25-29), two layers
+    gru_layer_fwd(a, prm + off[0], X0, nin, H0, G0);
+    gru_layer_fwd(a, prm + off[4], H0 + (int64_t)kRows * g, g, H1, G1);
+    // ---- linear_out -> enc, the last two latent columns
+    {
+      const double* Wlo = prm + off[8];
+      const double* blo = prm + off[9];
+      const double* hB = H1 + (int64_t)B * kRows * g;
+      if (threadIdx.x < 2 * kRows) {
+        const int r = threadIdx.x & (kRows - 1), c = threadIdx.x >> 4;
+        double acc = 0.0;
+        for (int i = 0; i < g; ++i) acc += Wlo[c * g + i] * hB[(int64_t)r * g + i];
+        a0[(int64_t)r * K0 + 2 * S + d + c] = acc + blo[c];
+      }
+    }
+    __syncthreads();
+    // ---- representation MLP (w_nl.py:55-58)
+    dense_tanh(prm + off[10], prm + off[11], a0, K0, h, a1);
+    __syncthreads();
+    dense_tanh(prm + off[12], prm + off[13], a1, h, h, a2);
+    __syncthreads();
+    dense_tanh(prm + off[14], prm + off[15], a2, h, O, u);
+    __syncthreads();
+    // ---- sphere map + Fourier line integral at the row's own t, squared error, and their backward down to the last layer's
+    // pre-activations: x = e^{gamma t} / T * sum_k w_k R_k c_k
+    for (int p = threadIdx.x; p < kRows * d; p += kThreads) {
+      const int r = p & (kRows - 1), c = p >> 4;
+      const double t = tn[r], Tt = scale * t;
+      const double gamma = a.alpha - a.log_tol / (scale * Tt);
+      const double srow = exp(gamma * t) / Tt;
+      const double* yt = u + (int64_t)r * O + c * S;
+      const double* yp = u + (int64_t)r * O + (d + c) * S;
+      double acc = 0.0;
+      for (int k = 0; k < S; ++k) {
+        double cv, cp;
+        quarter(sphere_theta(yt[k]), k, &cv, &cp);
+        const double R = tan(sphere_phi(yp[k]) / 2.0 + kPi / 4.0);
+        acc += (k == 0 ? 0.5 : 1.0) * R * cv;
+      }
+      const double pred = srow * acc;
+      const bool valid = row0 + r < a.N;
+      const double diff = pred - tgt[r * d + c];
+      sq[r * d + c] = valid ? diff * diff : 0.0;
+      const double gs = valid ? (loss_norm * diff) * srow : 0.0;
+      double* dt = d3 + (int64_t)r * O + c * S;
+      double* dp = d3 + (int64_t)r * O + (d + c) * S;
+      for (int k = 0; k < S; ++k) {
+        double cv, cp, gth, gph;
+        quarter(sphere_theta(yt[k]), k, &cv, &cp);
+        const double R = tan(sphere_phi(yp[k]) / 2.0 + kPi / 4.0);
+        ilt_term_bwd(gs, k == 0 ? 0.5 : 1.0, R, cv, cp, &gth, &gph);
+        dt[k] = sphere_theta_bwd(gth, yt[k]);
+        dp[k] = sphere_phi_bwd(gph, yp[k]);
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double s = first ? 0.0 : a.tile_loss[blockIdx.x];
+      for (int i = 0; i < kRows * d; ++i) s += sq[i];
+      a.tile_loss[blockIdx.x] = s;
+    }
+    // ---- MLP backward
+    dense_tanh_bwd(prm + off[14], d3, h, O, a2, d2);
+    __syncthreads();
+    dense_tanh_bwd(prm + off[12], d2, h, h, a1, d1);
+    __syncthreads();
+    // the latent enc columns of layer 0's input: the only input gradient that flows on (into the encoder)
+    if (threadIdx.x < 2 * kRows) {
+      const int r = threadIdx.x & (kRows - 1), c = threadIdx.x >> 4;
+      const double* W0 = prm + off[10];
+      double acc = 0.0;
+      for (int j = 0; j < h; ++j) acc += W0[(int64_t)j * K0 + 2 * S + d + c] * d1[(int64_t)r * h + j];
+      denc[r * 2 + c] = acc;
+    }
+    // MLP weight / bias gradients (independent of the encoder's backward)
+    wgrad_mfma(part + off[14], O, h, kRows, d3, O, a2, h, first);
+    wgrad_mfma(part + off[12], h, h, kRows, d2, h, a1, h, first);
+    wgrad_mfma(part + off[10], h, K0, kRows, d1, h, a0, K0, first);
+    bgrad(part + off[15], O, kRows, d3, O, first);
+    bgrad(part + off[13], h, kRows, d2, h, first);
+    bgrad(part + off[11], h, kRows, d1, h, first);
+    __syncthreads();
+    // ---- linear_out backward
+    {
+      const double* Wlo = prm + off[8];
+      const double* hB = H1 + (int64_t)B * kRows * g;
+      for (int p = threadIdx.x; p < 2 * g; p += kThreads) {
+        const int c = p / g, i = p - c * g;
+        double acc = first ? 0.0 : part[off[8] + p];
+        for (int r = 0; r < kRows; ++r) acc += denc[r * 2 + c] * hB[(int64_t)r * g + i];
+        part[off[8] + p] = acc;
+      }
+      if (threadIdx.x < 2) {
+        const int c = threadIdx.x;
+        double acc = first ? 0.0 : part[off[9] + c];
+        for (int r = 0; r < kRows; ++r) acc += denc[r * 2 + c];
+        part[off[9] + c] = acc;
+      }
+      for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
+        const int r = p & (kRows - 1), i = p >> 4;
+        dhA[r * g + i] = Wlo[i] * denc[r * 2] + Wlo[g + i] * denc[r * 2 + 1];
+      }
+    }
+    __syncthreads();
+    // ---- GRU backprop through time: layer 1 (its input gradient -> DX1), then layer 0
+    gru_layer_bwd(a, prm + off[4], g, H1, G1, DI1, DH1, nullptr, DX1, dhA, dD);
+    for (int p = threadIdx.x; p < kRows * g; p += kThreads) dhA[p] = 0.0;
+    __syncthreads();
+    gru_layer_bwd(a, prm + off[0], nin, H0, G0, DI0, DH0, DX1, nullptr, dhA, dD);
+    // ---- GRU weight / bias gradients: sums over the B * 16 (step, row) samples
+    const int ns = B * kRows, g3 = 3 * g;
+    wgrad_mfma(part + off[0], g3, nin, ns, DI0, g3, X0, nin, first);
+    wgrad_mfma(part + off[1], g3, g, ns, DH0, g3, H0, g, first);
+    wgrad_mfma(part + off[4], g3, g, ns, DI1, g3, H0 + (int64_t)kRows * g, g, first);
+    wgrad_mfma(part + off[5], g3, g, ns, DH1, g3, H1, g, first);
+    bgrad(part + off[2], g3, ns, DI0, g3, first);
+    bgrad(part + off[3], g3, ns, DH0, g3, first);
+    bgrad(part + off[6], g3, ns, DI1, g3, first);
+    bgrad(part + off[7], g3, ns, DH1, g3, first);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs a) {
+  __shared__ double red[kThreads];
+  const int b = blockIdx.x;
+  int t = 0;
+  while (t + 1 < kTensors && a.cstart[t + 1] <= b) ++t;
+  const int64_t e0 = a.off[t] + (int64_t)(b - a.cstart[t]) * kChunk;
+  const int64_t e1 = e0 + kChunk < a.off[t + 1] ? e0 + kChunk : a.off[t + 1];
+  double s = 0.0;
+  for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
+    double gsum = 0.0;
+    for (int k = 0; k < a.nblk; ++k) gsum += a.partial[(int64_t)k * a.P + e];
+    a.grad[e] = gsum;
+    s += gsum * gsum;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    a.sq[b] = red[0];
+    if (b == 0) {
+      double l = 0.0;
+      for (int k = 0; k < a.nblk; ++k) l += a.tile_loss[k];
+      *a.loss = l / ((double)a.N * (double)a.d);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void train_adam_kernel(const AdamArgs a) {
+  __shared__ double coef_s;
+  const int b = blockIdx.x;
+  int t = 0;
+  while (t + 1 < kTensors && a.cstart[t + 1] <= b) ++t;
+  if (threadIdx.x == 0) {
+    // clip_grad_norm_: total = || (||g_0||, ..., ||g_15||) ||, every workgroup from the same sums in the same order
+    double tot2 = 0.0;
+    for (int i = 0; i < kTensors; ++i) {
+      double s = 0.0;
+      for (int c = a.cstart[i]; c < a.cstart[i + 1]; ++c) s += a.sq[c];
+      const double n = sqrt(s);
+      tot2 += n * n;
+    }
+    const double total = sqrt(tot2);
+    coef_s = a.max_norm > 0.0 ? clip_coef(a.max_norm, total) : 1.0;
+    if (b == 0 && a.gradnorm) *a.gradnorm = total;
+  }
+  __syncthreads();
+  const double coef = coef_s;
+  const int64_t e0 = a.off[t] + (int64_t)(b - a.cstart[t]) * kChunk;
+  const int64_t e1 = e0 + kChunk < a.off[t + 1] ? e0 + kChunk : a.off[t + 1];
+  for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
+    double gv = a.grad[e];
+    if (a.max_norm > 0.0) gv = gv * coef;
+    double p = a.params[e], mm = a.m[e], vv = a.v[e];
+    adam_element(&p, &mm, &vv, gv, a.k);
+    a.params[e] = p;
+    a.m[e] = mm;
+    a.v[e] = vv;
+  }
+}
+
+hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, hipStream_t s) {
+  hipLaunchKernelGGL(train_fwd_bwd_kernel, dim3(nblk), dim3(kThreads), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_train_reduce(const ReduceArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(train_reduce_kernel, dim3(a.cstart[kTensors]), dim3(kThreads), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_train_adam(const AdamArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(train_adam_kernel, dim3(a.cstart[kTensors]), dim3(kThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace train
+}  // namespace nlc

@@ -1,0 +1,193 @@
+// Per-element math of the fused training step (kernels_train.hip): NeuralLaplaceModel's loss / gradient / clip / Adam
+// iteration of the reference's training loop (train_utils.py:388-408).  Everything here is __host__ __device__ so that
+// tests/helpers/train_host.cpp compiles the same functions with g++ and tests/test_train_host.py checks them against
+// torch's autograd / clip_grad_norm_ / Adam on the CPU.
+//
+// Operation order follows the torch kernels the reference runs, so the host build agrees with them to a few ulp:
+//   tanh backward        g * (1 - y*y)                                     (aten tanh_backward)
+//   sigmoid backward     g * ((1 - y) * y)                                 (aten sigmoid_backward)
+//   clip_grad_norm_      coef = max_norm / (total + 1e-6), clamped to 1, always multiplied (torch/nn/utils/clip_grad.py)
+//   Adam (foreach)       g += wd p;  m.lerp_(g, 1 - b1);  v = v*b2 + (1 - b2)*(g*g);  p += -(lr/bc1) * (m / (sqrt(v)/sqrt(bc2) + eps))
+#pragma once
+#include <math.h>
+
+#include "nlc_math.h"
+
+namespace nlc {
+namespace train {
+
+constexpr double kPiT = 3.14159265358979323846;
+
+// ---- GRU cell backward (torch.nn.GRU gate order [r; z; n]):
+//   r = sig(gi_r + gh_r), z = sig(gi_z + gh_z), n = tanh(gi_n + r * hn), hn = W_hn h + b_hn, h' = (1 - z) n + z h.
+// Given the saved r, z, n, hn and the previous hidden state, dh' -> the gradients of the input-side pre-activations
+// (gi_r, gi_z, gi_n: also those of b_ih and, times x, of W_ih), of the hidden-side n pre-activation gh_n = dn_pre * r (the
+// hidden side's r / z gradients equal the input side's) and the direct part z * dh' of dh (the rest is W_hh^T (gh)).
+NLC_HD void gru_cell_bwd(double dh, double r, double z, double n, double hn, double h_prev, double* gi_r, double* gi_z,
+                         double* gi_n, double* gh_n, double* dh_direct) {
+  const double dn = dh * (1.0 - z);
+  const double dz = dh * (h_prev - n);
+  const double dn_pre = dn * (1.0 - n * n);
+  const double dr = dn_pre * hn;
+  *gi_r = dr * ((1.0 - r) * r);
+  *gi_z = dz * ((1.0 - z) * z);
+  *gi_n = dn_pre;
+  *gh_n = dn_pre * r;
+  *dh_direct = dh * z;
+}
+
+// ---- sphere map of LaplaceRepresentationFunc.forward (w_nl.py:59-62), y = tanh(out):
+//   theta = y * pi                      -> d out = (g * pi) * (1 - y^2)
+//   phi = y * pi / 2 - pi/2 + pi/2      -> d out = ((g / 2) * pi) * (1 - y^2)
+NLC_HD double sphere_theta_bwd(double g, double y) { return (g * kPiT) * (1.0 - y * y); }
+NLC_HD double sphere_phi_bwd(double g, double y) { return ((g / 2.0) * kPiT) * (1.0 - y * y); }
+// forward values, in the reference's operation order
+NLC_HD double sphere_theta(double y) { return y * kPiT; }
+NLC_HD double sphere_phi(double y) { return y * kPiT / 2.0 - kPiT / 2.0 + kPiT / 2.0; }
+
+// ---- one term of the Fourier line integral, x = s(t) sum_k w_k R_k c_k with R = tan(phi/2 + pi/4), c_k = cos(theta + k pi/2)
+// (scale 2), c'_k = d c_k / d theta:  dx/dtheta_k = w_k R_k c'_k,  dx/dphi_k = w_k c_k (1 + R_k^2) / 2.  g = dL/dx * s(t).
+NLC_HD void ilt_term_bwd(double g, double wk, double R, double c, double c_prime, double* d_theta, double* d_phi) {
+  *d_theta = (g * wk) * R * c_prime;
+  *d_phi = (g * wk) * c * (0.5 * (1.0 + R * R));
+}
+
+// ---- clip_grad_norm_: coefficient the gradients are multiplied by (NaN total -> NaN, as torch.clamp propagates it)
+NLC_HD double clip_coef(double max_norm, double total_norm) {
+  const double c = max_norm / (total_norm + 1e-6);
+  return c > 1.0 ? 1.0 : c;
+}
+
+// ---- torch.optim.Adam (foreach, non-capturable, amsgrad off), one element; g is the (clipped) gradient.
+// Host-side scalars of the step: omb1 = 1 - beta1 (lerp weight), omb2 = 1 - beta2, step_size = -(lr / bc1),
+// bc2_sqrt = bc2 ** 0.5 with bc_i = 1 - beta_i ** step.
+struct AdamScalars {
+  double wd, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
+};
+NLC_HD void adam_element(double* p, double* m, double* v, double g, const AdamScalars& k) {
+  if (k.wd != 0.0) g = g + k.wd * *p;  // torch._foreach_add(grads, params, alpha=weight_decay)
+  // torch.lerp: weight < 0.5 -> self + w (end - self), else end - (end - self)(1 - w)
+  const double diff = g - *m;
+  *m = fabs(k.omb1) < 0.5 ? *m + k.omb1 * diff : g - diff * (1.0 - k.omb1);
+  *v = *v * k.beta2;
+  *v = *v + k.omb2 * (g * g);
+  const double denom = sqrt(*v) / k.bc2_sqrt + k.eps;
+  *p = *p + k.step_size * (*m / denom);
+}
+
+}  // namespace train
+}  // namespace nlc
+
+// ---- shapes and buffers of the fused training step (shared by kernels_train.hip and abi_train.hip; plain C++ so the host
+// test can include this header too)
+namespace nlc {
+namespace train {
+
+constexpr int kRows = 16;      // rows per tile: one workgroup, and the k = 4 x 4 sample steps of the MFMA weight gradients
+constexpr int kThreads = 256;  // threads per training workgroup
+constexpr int kMaxB = 16;      // longest action window (action_buffer_size, config.py:58: 4)
+constexpr int kMaxBlocks = 128;
+constexpr int kChunk = 1024;   // parameters per reduce / Adam workgroup (never straddles two tensors)
+constexpr int kTensors = 16;   // blob tensors (include/nlc.h, nlc_set_model)
+
+// per-tile activations, tapes and deltas in one workgroup's slab (doubles, each array 64-byte aligned)
+struct ActLayout {
+  int64_t X0, H0, G0, H1, G1, a0, a1, a2, u, d3, d2, d1, denc, tn, tgt, sq, DI0, DH0, DI1, DH1, DX1, dhA, dD, total;
+};
+NLC_HD int64_t act_take(int64_t* o, int64_t n) {
+  const int64_t r = *o;
+  *o += (n + 7) & ~(int64_t)7;
+  return r;
+}
+NLC_HD ActLayout act_layout(int d, int nin, int g, int h, int S, int B) {
+  const int64_t R = kRows, K0 = 2 * S + d + 2, O = 2 * d * S;
+  ActLayout L;
+  int64_t o = 0;
+  L.X0 = act_take(&o, B * R * nin);         // layer-0 inputs, flipped window, normalised: [s][r][nin]
+  L.H0 = act_take(&o, (B + 1) * R * g);     // layer-0 hidden states h_0 = 0 .. h_B: [s][r][g]
+  L.G0 = act_take(&o, B * R * 4 * g);       // layer-0 tape [r | z | n | W_hn h + b_hn]: [s][r][4g]
+  L.H1 = act_take(&o, (B + 1) * R * g);
+  L.G1 = act_take(&o, B * R * 4 * g);
+  L.a0 = act_take(&o, R * K0);              // MLP input [theta_s | phi_s | obs_n | enc]
+  L.a1 = act_take(&o, R * h);
+  L.a2 = act_take(&o, R * h);
+  L.u = act_take(&o, R * O);                // tanh of the last layer (sphere map input)
+  L.d3 = act_take(&o, R * O);
+  L.d2 = act_take(&o, R * h);
+  L.d1 = act_take(&o, R * h);
+  L.denc = act_take(&o, R * 2);
+  L.tn = act_take(&o, R);
+  L.tgt = act_take(&o, R * d);
+  L.sq = act_take(&o, R * d);
+  L.DI0 = act_take(&o, B * R * 3 * g);      // input-side gate gradients [s][r][3g]
+  L.DH0 = act_take(&o, B * R * 3 * g);      // hidden-side gate gradients [s][r][3g]
+  L.DI1 = act_take(&o, B * R * 3 * g);
+  L.DH1 = act_take(&o, B * R * 3 * g);
+  L.DX1 = act_take(&o, B * R * g);          // gradient reaching layer 0's outputs through layer 1's inputs
+  L.dhA = act_take(&o, R * g);
+  L.dD = act_take(&o, R * g);
+  L.total = o;
+  return L;
+}
+
+// blob offsets (nlc_set_model's state_dict order): off[i] .. off[i + 1] is tensor i
+inline void blob_offsets(int d, int nin, int g, int h, int S, int64_t off[kTensors + 1]) {
+  const int64_t g3 = 3 * g, K0 = 2 * S + d + 2, O = 2 * d * S;
+  const int64_t n[kTensors] = {g3 * nin, g3 * g, g3, g3, g3 * g, g3 * g, g3, g3, 2 * g, 2, h * K0, h, (int64_t)h * h, h, O * h, O};
+  off[0] = 0;
+  for (int i = 0; i < kTensors; ++i) off[i + 1] = off[i] + n[i];
+}
+
+struct TrainArgs {
+  int d, nin, g, h, S, B;
+  double time_div, alpha, log_tol;
+  double sm[8], ss[8], am[3], as[3];
+  const double* params;
+  const double *obs, *window, *ts, *target;
+  const int64_t* idx;
+  int64_t N;
+  int ntiles;
+  int64_t P, A;
+  ActLayout L;        // offsets into a workgroup's slab for this call's B
+  double* partial;    // [gridDim.x][P] per-workgroup gradient sums
+  double* tile_loss;  // [gridDim.x] per-workgroup sums of squared errors
+  double* act;        // [gridDim.x][A]
+  int64_t off[kTensors + 1];
+};
+
+struct ReduceArgs {
+  const double* partial;
+  const double* tile_loss;
+  int nblk, d;
+  int64_t P, N;
+  double* grad;  // (P) summed gradient
+  double* sq;    // (chunks) sum of squares of each chunk
+  double* loss;  // 0-dim
+  int64_t off[kTensors + 1];
+  int cstart[kTensors + 1];  // first chunk of each tensor
+};
+
+struct AdamArgs {
+  double *params, *m, *v;
+  const double* grad;
+  const double* sq;
+  double max_norm;  // <= 0: no clipping
+  AdamScalars k;
+  double* gradnorm;  // may be NULL
+  int64_t off[kTensors + 1];
+  int cstart[kTensors + 1];
+};
+
+}  // namespace train
+}  // namespace nlc
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+namespace nlc {
+namespace train {
+hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, hipStream_t s);
+hipError_t launch_train_reduce(const ReduceArgs& a, hipStream_t s);
+hipError_t launch_train_adam(const AdamArgs& a, hipStream_t s);
+}  // namespace train
+}  // namespace nlc
+#endif
