@@ -7,8 +7,11 @@
 a fixed-order reduction of the tile gradients, clip + Adam.  No host synchronisation inside, so ``run()`` walks a whole
 permutation with the weights, Adam moments and per-iteration losses on the device.
 
-Shapes the kernels do not take (de Hoog / fixed Talbot / Stehfest, widths other than 64 / 128 / 256, ...) fall back to the
-reference's op sequence -- the model's grad-mode forward + ``clip_grad_norm_`` + ``torch.optim.Adam`` -- with one warning.
+Models the kernels do not take (de Hoog / fixed Talbot / Stehfest, widths other than 64 / 128 / 256, ...) train through
+the reference's op sequence -- the model's grad-mode forward + ``clip_grad_norm_`` + ``torch.optim.Adam`` -- from
+construction on, with one warning.  A fused trainer sends a single call the library refuses (a window longer than 16, a
+model setting changed to one the kernels do not take) through the same op sequence, on the trainer's own Adam state, also
+with one warning.
 """
 
 import ctypes as C
@@ -41,7 +44,9 @@ class NLTrainer:
     * ``tr.state_dict()`` / ``tr.load_state_dict(sd)`` -- ``torch.optim.Adam``'s format.
 
     ``tr.lr`` may change between calls (what a ``StepLR`` would do).  After ``step()`` / ``run()`` the model's parameters
-    hold the new weights, written in place (their ``_version`` moves, so ``model.forward`` and planners re-upload)."""
+    hold the new weights, written in place (their ``_version`` moves, so ``model.forward`` and planners re-upload).  The
+    model's buffers and settings (normalisation constants, ``normalize`` / ``normalize_time``, ``ilt_options``) are
+    re-read before every call: a change after construction (``model.load_state_dict(checkpoint)``, say) takes effect."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
         params = list(model.parameters())
@@ -64,12 +69,8 @@ class NLTrainer:
             why = f"ilt_algorithm {model.ilt_algorithm!r} has no fused training kernels (fourier only)"
         else:
             self._ctx = _lib.Ctx(self._dev.index)
-            try:
-                model.upload(self._ctx)
-            except _lib.NlcError as err:
-                if err.code != _lib.NLC_ERR_UNSUPPORTED:
-                    raise
-                why = str(err)
+            self._model_key = None
+            why = self._sync_model()
         if why is not None:
             warnings.warn(f"NLTrainer: {why} -- this model trains through its grad-mode forward + clip_grad_norm_ + "
                           "torch.optim.Adam instead of the fused HIP step", stacklevel=2)
@@ -82,6 +83,7 @@ class NLTrainer:
         self._step = 0
         self._ws = {}
         self._arange = {}
+        self._warned = False
 
     @property
     def fused(self):
@@ -89,6 +91,37 @@ class NLTrainer:
         return self._fallback is None
 
     # ------------------------------------------------------------------ plumbing
+    def _model_state_key(self):
+        """What the kernels read from the model descriptor besides the weights: the buffers (normalisation, dt) and the
+        settings of ``_weights_key_extra()``.  Not the parameters: the trainer's own write-back moves their versions, and
+        the kernels read the weights from ``_flat`` on every call."""
+        m = self.model
+        return (tuple((id(b), b.data_ptr(), b._version) for b in m.buffers()), m._wk_dirty, tuple(m._weights_key_extra()))
+
+    def _sync_model(self):
+        """Re-upload the model descriptor if the buffers or settings changed since the last upload.  Returns None when the
+        descriptor in the ctx is current, else the library's reason for refusing the new one (the fused kernels must not
+        run then: the ctx still holds the old constants)."""
+        key = self._model_state_key()
+        if self._model_key is not None and self._model_key[0] == key:
+            return self._model_key[1]
+        why = None
+        try:
+            self.model.upload(self._ctx)
+        except _lib.NlcError as err:
+            if err.code != _lib.NLC_ERR_UNSUPPORTED:
+                raise
+            why = str(err)
+        self._model_key = (key, why)
+        return why
+
+    def _host_path(self, why):
+        """A call the fused kernels do not take: warn once per trainer."""
+        if not self._warned:
+            self._warned = True
+            warnings.warn(f"NLTrainer: {why} -- calls the library refuses run the grad-mode forward + clip_grad_norm_ + "
+                          "torch.optim.Adam on the trainer's optimiser state instead of the fused HIP step", stacklevel=3)
+
     def _views(self, flat):
         out, o = [], 0
         for p, n in zip(self._params, self._sizes):
@@ -139,11 +172,11 @@ class NLTrainer:
     # ------------------------------------------------------------------ API
     def loss_and_grad(self, bs0, ba0, bts, bsd):
         """Loss of the batch and ``p.grad`` of every parameter (train_utils.py:391-402); no update."""
-        if not self.fused:
-            self.model.zero_grad()
-            loss = self._ref_loss(bs0, ba0, bts, bsd)
-            loss.backward()
-            return loss.detach()
+        why = None if not self.fused else self._sync_model()
+        if not self.fused or why is not None:
+            if why is not None:
+                self._host_path(why)
+            return self._host_loss_and_grad(bs0, ba0, bts, bsd)
         obs, win, ts, tgt = self._data(bs0, ba0, bts, bsd)
         N = obs.shape[0]
         self._gather()
@@ -152,9 +185,13 @@ class NLTrainer:
         ctx = self._ctx
         with torch.cuda.device(self._dev):
             ctx.use_torch_stream()
-            ctx.check(ctx.lib.nlc_train_loss_grad(
+            rc = ctx.lib.nlc_train_loss_grad(
                 ctx.h, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), _i64_ptr(self._idx(N)),
-                N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N))))
+                N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)))
+        why = self._refused(rc)
+        if why is not None:
+            self._host_path(why)
+            return self._host_loss_and_grad(bs0, ba0, bts, bsd)
         for p, g in zip(self._params, self._views(grad)):
             p.grad = g
         return loss
@@ -163,6 +200,9 @@ class NLTrainer:
         """One iteration of the reference's loop (train_utils.py:391-404); returns the loss before the update."""
         if not self.fused:
             return self._fallback_step(bs0, ba0, bts, bsd)
+        why = self._sync_model()
+        if why is not None:
+            return self._host_steps(why, [(bs0, ba0, bts, bsd)])[0]
         obs, win, ts, tgt = self._data(bs0, ba0, bts, bsd)
         N = obs.shape[0]
         self._gather()
@@ -170,20 +210,56 @@ class NLTrainer:
         ctx = self._ctx
         with torch.cuda.device(self._dev):
             ctx.use_torch_stream()
-            self._launch_step(_i64_ptr(self._idx(N)), obs, win, ts, tgt, N, _f64_ptr(loss), self._workspace(N))
+            try:
+                self._launch_step(_i64_ptr(self._idx(N)), obs, win, ts, tgt, N, _f64_ptr(loss), self._workspace(N))
+            except _lib.NlcError as err:
+                if err.code != _lib.NLC_ERR_UNSUPPORTED:
+                    raise
+                return self._host_steps(str(err), [(bs0, ba0, bts, bsd)])[0]
         self._scatter()
         return loss
 
     def _launch_step(self, idx_ptr, obs, win, ts, tgt, N, loss_ptr, ws, desc=None):
+        """One ``nlc_train_step``; the Adam step count moves only once the library has accepted the call (it checks
+        everything on the host before the first launch)."""
         ctx = self._ctx
-        self._step += 1
         ctx.check(ctx.lib.nlc_train_step(
             ctx.h, C.byref(desc if desc is not None else self._desc()), _f64_ptr(self._flat), _f64_ptr(self._m),
-            _f64_ptr(self._v), self._step, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), idx_ptr, N, win.shape[1],
-            loss_ptr, None, _f64_ptr(ws)))
+            _f64_ptr(self._v), self._step + 1, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), idx_ptr, N,
+            win.shape[1], loss_ptr, None, _f64_ptr(ws)))
+        self._step += 1
 
-    def _fallback_step(self, bs0, ba0, bts, bsd):
-        opt = self._fallback
+    def _refused(self, rc):
+        """None if the library took the call, its reason if it refused the shape (NLC_ERR_UNSUPPORTED); raises otherwise."""
+        if rc == _lib.NLC_ERR_UNSUPPORTED:
+            return (self._ctx.lib.nlc_last_error(self._ctx.h) or b"").decode()
+        self._ctx.check(rc)
+        return None
+
+    def _host_loss_and_grad(self, bs0, ba0, bts, bsd):
+        self.model.zero_grad()
+        loss = self._ref_loss(bs0, ba0, bts, bsd)
+        loss.backward()
+        return loss.detach()
+
+    def _host_steps(self, why, batches):
+        """Iterations the fused kernels refused, on the grad-mode path with a transient torch.optim.Adam that starts from
+        the trainer's step count and moments and hands them back: the trainer keeps one optimiser state."""
+        self._host_path(why)
+        opt = self._adam()
+        self._export_state(opt)
+        out = [self._fallback_step(*b, opt=opt) for b in batches]
+        st = opt.state.get(self._params[0])
+        if st is not None:
+            with torch.no_grad():
+                for p, m, v in zip(self._params, self._views(self._m), self._views(self._v)):
+                    m.copy_(opt.state[p]["exp_avg"])
+                    v.copy_(opt.state[p]["exp_avg_sq"])
+            self._step = int(st["step"])
+        return out
+
+    def _fallback_step(self, bs0, ba0, bts, bsd, opt=None):
+        opt = self._fallback if opt is None else opt
         for grp in opt.param_groups:
             grp["lr"] = self.lr
         opt.zero_grad()
@@ -200,14 +276,22 @@ class NLTrainer:
         permutation, nothing crosses to the host until the end."""
         bs = int(batch_size)
         iters = int(permutation.shape[0]) // bs
-        if not self.fused:
-            s0, a0, sn, ts = (torch.as_tensor(t).to(self._dev) for t in (s0, a0, sn, ts))
+
+        def host(why=None):
+            s0_, a0_, sn_, ts_ = (torch.as_tensor(t).to(self._dev) for t in (s0, a0, sn, ts))
             perm = torch.as_tensor(permutation).to(self._dev)
-            out = []
+            batches = []
             for i in range(iters):
                 ind = perm[i * bs : i * bs + bs]
-                out.append(self._fallback_step(s0[ind], a0[ind], ts[ind], sn[ind] - s0[ind]))
+                batches.append((s0_[ind], a0_[ind], ts_[ind], sn_[ind] - s0_[ind]))
+            out = [self._fallback_step(*b) for b in batches] if why is None else self._host_steps(why, batches)
             return torch.stack(out) if out else torch.empty(0, dtype=torch.float64, device=self._dev)
+
+        if not self.fused:
+            return host()
+        why = self._sync_model() if iters > 0 else None
+        if why is not None:
+            return host(why)
         obs, win, tsd, sn_d = self._data(s0, a0, ts, sn)
         tgt = sn_d - obs
         perm = torch.as_tensor(permutation).to(self._dev, torch.int64).contiguous()
@@ -221,7 +305,14 @@ class NLTrainer:
         with torch.cuda.device(self._dev):
             ctx.use_torch_stream()
             for i in range(iters):
-                self._launch_step(_i64_ptr(perm, i * bs), obs, win, tsd, tgt, bs, _f64_ptr(losses, i), ws, desc)
+                try:
+                    self._launch_step(_i64_ptr(perm, i * bs), obs, win, tsd, tgt, bs, _f64_ptr(losses, i), ws, desc)
+                except _lib.NlcError as err:
+                    # the library checks the shape on the host before any launch, and the shape is the same for every
+                    # iteration: only the first can be refused, with nothing launched
+                    if err.code != _lib.NLC_ERR_UNSUPPORTED or i > 0:
+                        raise
+                    return host(str(err))
         self._scatter()
         return losses
 
@@ -230,20 +321,30 @@ class NLTrainer:
         return torch.optim.Adam(self.model.parameters(), lr=self.lr, betas=self.betas, eps=self.eps,
                                 weight_decay=self.weight_decay)
 
-    def state_dict(self):
-        """``torch.optim.Adam(model.parameters(), ...).state_dict()`` of the same optimiser state."""
-        if not self.fused:
-            return self._fallback.state_dict()
-        opt = self._adam()
+    def _export_state(self, opt):
+        """The trainer's step count and moments as ``opt.state`` (copies)."""
         if self._step > 0:
             sdt = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32
             for p, m, v in zip(self._params, self._views(self._m), self._views(self._v)):
                 opt.state[p] = {"step": torch.tensor(float(self._step), dtype=sdt), "exp_avg": m.clone(),
                                 "exp_avg_sq": v.clone()}
+
+    def state_dict(self):
+        """``torch.optim.Adam(model.parameters(), ...).state_dict()`` of the same optimiser state."""
+        if not self.fused:
+            return self._fallback.state_dict()
+        opt = self._adam()
+        self._export_state(opt)
         return opt.state_dict()
 
     def load_state_dict(self, sd):
-        """Take over a ``torch.optim.Adam`` state (hyper-parameters of its first group, step and moments)."""
+        """Take over a ``torch.optim.Adam`` state (hyper-parameters of its first group, step and moments).  An
+        ``amsgrad`` or ``maximize`` state is refused: the trainer's update has neither."""
+        for grp in sd.get("param_groups", []):
+            for flag in ("amsgrad", "maximize"):
+                if grp.get(flag):
+                    raise ValueError(f"NLTrainer.load_state_dict: an Adam state with {flag}=True is not supported "
+                                     "(the trainer runs plain Adam)")
         if not self.fused:
             self._fallback.load_state_dict(sd)
             grp = self._fallback.param_groups[0]

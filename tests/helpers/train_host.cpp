@@ -27,3 +27,18 @@ void nlc_t_adam(double* state, const double* g, const double* k, long n) {
   for (long i = 0; i < n; ++i) adam_element(state + 3 * i, state + 3 * i + 1, state + 3 * i + 2, g[i], s);
 }
 }
+extern "C" {
+// act_layout(d, nin, g, h, S, B): the 24 fields of ActLayout in declaration order (offsets, then total)
+void nlc_t_act_layout(int d, int nin, int g, int h, int S, int B, long long* out) {
+  const ActLayout L = act_layout(d, nin, g, h, S, B);
+  const int64_t f[24] = {L.X0, L.H0, L.G0, L.H1, L.G1, L.a0, L.a1, L.a2, L.u, L.d3, L.d2, L.d1,
+                         L.denc, L.tn, L.tgt, L.sq, L.DI0, L.DH0, L.DI1, L.DH1, L.DX1, L.dhA, L.dD, L.total};
+  for (int i = 0; i < 24; ++i) out[i] = (long long)f[i];
+}
+// blob_offsets(d, nin, g, h, S): off[0..16]
+void nlc_t_blob_offsets(int d, int nin, int g, int h, int S, long long* out) {
+  int64_t off[kTensors + 1];
+  blob_offsets(d, nin, g, h, S, off);
+  for (int i = 0; i <= kTensors; ++i) out[i] = (long long)off[i];
+}
+}

@@ -132,3 +132,162 @@ def test_adam_element_vs_torch_adam(lib, wd):
     m_ref = st["exp_avg"].numpy()
     assert (np.abs(state[:, 1] - m_ref) / np.spacing(np.abs(m_ref) + np.abs(torch.stack(grads).numpy()).max(axis=0) + wd * np.abs(p0.numpy()))).max() <= 4
     assert _ulp(state[:, 2], st["exp_avg_sq"].numpy()).max() <= 4
+
+
+@pytest.mark.parametrize("foreach", [False, True])
+def test_adam_element_other_lerp_branch_and_large_eps(lib, foreach):
+    """beta1 = 0.3 makes the lerp weight 1 - beta1 = 0.7 >= 0.5, torch.lerp's other branch (end - (end - self)(1 - w)),
+    which the default betas never take; eps = 1e-2 is large against sqrt(v) for many elements; weight decay on; 10 steps of
+    torch.optim.Adam.  Each step is checked from torch's own state before it (so roundoff does not compound over the steps;
+    every step's bias corrections are exercised).  Bounds in ulp of the terms' magnitudes, not of the results, because torch's
+    CPU kernels may contract g + wd p and the lerp into FMAs and both cancel: exp_avg_sq to 8 ulp of b2 |v| + (1 - b2) G^2
+    (one ulp of G in the decayed gradient is two of G^2),
+    exp_avg to 4 ulp of |exp_avg| + G, the parameter to 4 ulp of |p| + |its update| (G = |g| + wd |p|)."""
+    torch.manual_seed(4)
+    n = 5000
+    p0 = torch.randn(n, dtype=torch.float64)
+    grads = [torch.randn(n, dtype=torch.float64) * 10.0 ** torch.randint(-7, 2, (n,)).double() for _ in range(10)]
+    lr, b1, b2, eps, wd = 1e-3, 0.3, 0.95, 1e-2, 1e-2
+    p = torch.nn.Parameter(p0.clone())
+    opt = torch.optim.Adam([p], lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd, foreach=foreach)
+    f = lib.nlc_t_adam
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long]
+    eps_dominated = 0.0
+    for step, g in enumerate(grads, start=1):
+        st = opt.state.get(p)
+        m0 = st["exp_avg"].numpy().copy() if st else np.zeros(n)
+        v0 = st["exp_avg_sq"].numpy().copy() if st else np.zeros(n)
+        pre = p.detach().numpy().copy()
+        state = np.ascontiguousarray(np.stack([pre, m0, v0], axis=1))
+        p.grad = g.clone()
+        opt.step()
+        bc1, bc2 = 1 - b1**step, 1 - b2**step
+        k = np.array([wd, 1 - b1, b2, 1 - b2, (lr / bc1) * -1, bc2**0.5, eps])
+        assert k[1] >= 0.5
+        gn = np.ascontiguousarray(g.numpy())
+        f(state.ctypes.data, gn.ctypes.data, k.ctypes.data, n)
+        st = opt.state[p]
+        p_ref, m_ref, v_ref = p.detach().numpy(), st["exp_avg"].numpy(), st["exp_avg_sq"].numpy()
+        geff = np.abs(gn) + wd * np.abs(pre)
+        assert (np.abs(state[:, 2] - v_ref) / np.spacing(b2 * v0 + (1 - b2) * geff * geff)).max() <= 8, step
+        assert (np.abs(state[:, 1] - m_ref) / np.spacing(np.abs(m_ref) + geff)).max() <= 4, step
+        assert (np.abs(state[:, 0] - p_ref) / np.spacing(np.abs(pre) + np.abs(p_ref - pre))).max() <= 4, step
+        eps_dominated = max(eps_dominated, float((np.sqrt(v_ref) / bc2**0.5 < eps).mean()))
+    # the large eps dominates the denominator for a good share of the elements: not the default regime
+    assert eps_dominated > 0.1
+
+
+# every (d, nin, h, S) nlc_set_model accepts for a Fourier model: d 1..6, nin 1..3, h 64 / 128 / 256, S 1..129 (the ILT
+# tables) with the last layer's 2 d S outputs in at most 25 output tiles (nlc_pack.h ilt_tiles_needed, nl_pick_nt3)
+def _ilt_tiles_needed(d, S):
+    n_even, n_odd = d * ((S + 1) // 2), d * (S // 2)
+    return ((n_even + 3) // 4 + (n_odd + 3) // 4 + 1) // 2
+
+
+def _accepted_shapes():
+    for d in range(1, 7):
+        for nin in (1, 2, 3):
+            for h in (64, 128, 256):
+                for S in range(1, 130):
+                    if _ilt_tiles_needed(d, S) <= 25:
+                        yield d, nin, h, S
+
+
+_FIELDS = ["X0", "H0", "G0", "H1", "G1", "a0", "a1", "a2", "u", "d3", "d2", "d1", "denc", "tn", "tgt", "sq", "DI0", "DH0",
+           "DI1", "DH1", "DX1", "dhA", "dD"]
+
+
+def _extents(d, nin, g, h, S, B):
+    """Doubles each slab array is indexed over by train_fwd_bwd_kernel (R = 16 rows, K0 = 2S + d + 2, O = 2dS)."""
+    R, K0, O = 16, 2 * S + d + 2, 2 * d * S
+    return dict(X0=B * R * nin, H0=(B + 1) * R * g, G0=B * R * 4 * g, H1=(B + 1) * R * g, G1=B * R * 4 * g, a0=R * K0,
+                a1=R * h, a2=R * h, u=R * O, d3=R * O, d2=R * h, d1=R * h, denc=R * 2, tn=R, tgt=R * d, sq=R * d,
+                DI0=B * R * 3 * g, DH0=B * R * 3 * g, DI1=B * R * 3 * g, DH1=B * R * 3 * g, DX1=B * R * g, dhA=R * g, dD=R * g)
+
+
+def test_act_layout_aligned_disjoint_and_within_the_slab(lib):
+    """The per-workgroup slab of the fused step (nlc_train.h act_layout): for every accepted (d, nin, h, S) and every window
+    B in 1..16, each array starts on an 8-double boundary, the arrays (at the extents the kernel indexes) do not overlap and
+    end inside total(B), and total(B) <= total(16) -- abi_train.hip's plan_of sizes every workgroup's slab for B = 16, so a
+    shorter window must not reach into the next workgroup's."""
+    f = lib.nlc_t_act_layout
+    f.argtypes = [ctypes.c_int] * 6 + [ctypes.c_void_p]
+    out = np.zeros(24, dtype=np.int64)
+    n_shapes = 0
+    for d, nin, h, S in _accepted_shapes():
+        g = h // 2
+        f(d, nin, g, h, S, 16, out.ctypes.data)
+        total16 = int(out[23])
+        for B in range(1, 17):
+            f(d, nin, g, h, S, B, out.ctypes.data)
+            ext = _extents(d, nin, g, h, S, B)
+            spans = sorted((int(out[i]), int(out[i]) + ext[k], k) for i, k in enumerate(_FIELDS))
+            where = f"d={d} nin={nin} h={h} S={S} B={B}"
+            assert all(o % 8 == 0 for o, _, _ in spans), where
+            assert spans[0][0] == 0, where
+            for (o0, e0, k0), (o1, _, k1) in zip(spans, spans[1:]):
+                assert e0 <= o1, f"{where}: {k0} [{o0}, {e0}) runs into {k1} at {o1}"
+            assert spans[-1][1] <= int(out[23]) <= total16, where
+        n_shapes += 1
+    assert n_shapes == 3 * 3 * (129 + 100 + 66 + 50 + 40 + 33)
+
+
+def test_blob_offsets_match_the_state_dict(lib):
+    """nlc_train.h blob_offsets (where the kernels read each weight and write each gradient) against the sizes of the
+    reference architecture's tensors in state_dict order, at a spread of accepted shapes."""
+    from oracle import nl_model as onl
+
+    f = lib.nlc_t_blob_offsets
+    f.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    out = np.zeros(17, dtype=np.int64)
+    for d, nu, enc, h, S in [(1, 1, False, 64, 129), (2, 2, True, 128, 4), (4, 3, False, 64, 13), (6, 2, False, 256, 33),
+                             (5, 1, True, 128, 17)]:
+        sd = onl.make_synthetic_state_dict(0, d, nu, h, S, encode_obs_time=enc)
+        sizes = [v.numel() for k, v in sd.items() if k.startswith(("action_encoder.", "laplace_rep_func."))]
+        f(d, nu + int(enc), h // 2, h, S, out.ctypes.data)
+        assert len(sizes) == 16
+        assert list(np.diff(out)) == sizes, (d, nu, enc, h, S)
+
+
+def test_blockwise_comparator_catches_what_the_per_tensor_scale_hides():
+    """tests/train_compare.py: an autograd gradient of the oracle's loss for a model whose layer-0 reset gate is saturated
+    (its input bias shifted by +8: r(1 - r) ~ 3e-4), so the r block of weight_ih_l0 is orders of magnitude below the n block.
+    An error of 1e-7 of that block's own max, put into one element, fails the block-wise comparison at the GPU tests' 1e-9,
+    while the earlier per-tensor scale passes it; the unperturbed gradient passes both."""
+    import train_compare as tc
+    from oracle import nl_model as onl
+
+    d, nu, h, S, B, N = 2, 1, 64, 5, 3, 8
+    g = h // 2
+    sd = onl.make_synthetic_state_dict(5, d, nu, h, S, [1.0, 2.0], [1.5], tame=True)
+    sd["action_encoder.gru.bias_ih_l0"][:g] += 8.0
+    gen = torch.Generator().manual_seed(0)
+    s0 = torch.randn(N, d, dtype=torch.float64, generator=gen)
+    a0 = torch.rand(N, B, nu, dtype=torch.float64, generator=gen) * 2 - 1
+    ts = torch.rand(N, 1, dtype=torch.float64, generator=gen) * 0.08 + 0.02
+    tgt = torch.randn(N, d, dtype=torch.float64, generator=gen) * 0.05
+    leaves = {k: (v.clone().requires_grad_() if k.startswith(("action_encoder.", "laplace_rep_func.")) else v)
+              for k, v in sd.items()}
+    ((onl.nl_forward(leaves, s0, a0, ts, S=S).reshape(N, d) - tgt) ** 2).mean().backward()
+    name = "action_encoder.gru.weight_ih_l0"
+    ref = leaves[name].grad.clone()
+    block = ref[:g]
+    ratio = float(block.abs().max()) / float(ref.abs().max())
+    assert ratio < 1e-2, f"r block is {ratio:.2e} of the tensor: not the regime this test needs"
+    bad = ref.clone()
+    i = int(block.abs().argmax())
+    bad[i] += 1e-7 * float(block.abs().max())
+    tc.assert_grad_close(name, ref.clone(), ref, 1e-9)
+    assert tc.per_tensor_close(ref.clone(), ref, 1e-9)
+    assert tc.per_tensor_close(bad, ref, 1e-9), "the per-tensor scale was expected to miss this error"
+    with pytest.raises(AssertionError, match=r"weight_ih_l0\[r\]"):
+        tc.assert_grad_close(name, bad, ref, 1e-9)
+    # the same for the phi half of the last layer when its theta half dominates
+    name = "laplace_rep_func.linear_tanh_stack.4.bias"
+    ref = leaves[name].grad.clone()
+    ref[d * S :] *= 1e-4  # a phi half four orders below the theta half
+    bad = ref.clone()
+    bad[-1] += 1e-7 * float(ref[d * S :].abs().max())
+    assert tc.per_tensor_close(bad, ref, 1e-9)
+    with pytest.raises(AssertionError, match=r"\[phi\]"):
+        tc.assert_grad_close(name, bad, ref, 1e-9)
