@@ -140,8 +140,8 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
 
 namespace nlc {
 namespace host {
-// fixed Talbot / Stehfest models whose rollout runs on the LIN instances of the rollout kernels (kernels_nl_lin*.hip) instead of
-// the staged path
+// fixed Talbot / Stehfest models whose rollout runs on the LIN instances of the rollout kernels (launch_nl_rollout_ht<HT, true>,
+// at the widths of with_width in nlc_kernels.h) instead of the staged path
 bool linear_on_rollout_kernels(const nlc_ctx* c) {
   return c->has_model && (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST) &&
          (c->md.h == 64 || c->md.h == 128 || c->md.h == 256) && c->opt_linear_fused != 0;

@@ -4,30 +4,17 @@
 
 namespace nlc {
 
-NLC_FUSED_DEFINE_LAUNCHERS(h128, 8, 64, 3, 4)
-hipError_t fused_max_resident_blocks_h64(int bpc_built, int* blocks_per_cu);
-hipError_t launch_nl_plan_fused_h64(const FusedArgs& a, unsigned grid, int bpc_built, hipStream_t s);
-hipError_t fused_max_resident_blocks_h256(int bpc_built, int* blocks_per_cu);
-hipError_t launch_nl_plan_fused_h256(const FusedArgs& a, unsigned grid, int bpc_built, hipStream_t s);
+template hipError_t launch_nl_plan_fused_ht<8>(const FusedArgs&, unsigned, int, hipStream_t);
+template hipError_t fused_max_resident_blocks_ht<8>(int, int*);
 
 hipError_t fused_max_resident_blocks(int h, int bpc_built, int* blocks_per_cu) {
-  switch (h) {
-    case 64: return fused_max_resident_blocks_h64(bpc_built, blocks_per_cu);
-    case 128: return fused_max_resident_blocks_h128(bpc_built, blocks_per_cu);
-    case 256: return fused_max_resident_blocks_h256(bpc_built, blocks_per_cu);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width(h, [&](auto ht) { return fused_max_resident_blocks_ht<ht>(bpc_built, blocks_per_cu); });
 }
 
 hipError_t launch_nl_plan_fused(const FusedArgs& a, int g, unsigned grid, int bpc_built, hipStream_t s) {
   if (a.r.K <= 0) return hipSuccess;
   if (2 * g != a.r.net.h) return hipErrorInvalidValue;
-  switch (a.r.net.h) {
-    case 64: return launch_nl_plan_fused_h64(a, grid, bpc_built, s);
-    case 128: return launch_nl_plan_fused_h128(a, grid, bpc_built, s);
-    case 256: return launch_nl_plan_fused_h256(a, grid, bpc_built, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width(a.r.net.h, [&](auto ht) { return launch_nl_plan_fused_ht<ht>(a, grid, bpc_built, s); });
 }
 
 }  // namespace nlc

@@ -3,5 +3,8 @@
 #include "nlc_fused_kernel.h"
 
 namespace nlc {
-NLC_FUSED_DEFINE_LAUNCHERS(h256, 16, 128, 2, 2)
+
+template hipError_t launch_nl_plan_fused_ht<16>(const FusedArgs&, unsigned, int, hipStream_t);
+template hipError_t fused_max_resident_blocks_ht<16>(int, int*);
+
 }  // namespace nlc

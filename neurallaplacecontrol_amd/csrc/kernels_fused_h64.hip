@@ -2,5 +2,8 @@
 #include "nlc_fused_kernel.h"
 
 namespace nlc {
-NLC_FUSED_DEFINE_LAUNCHERS(h64, 4, 32, 3, 4)
+
+template hipError_t launch_nl_plan_fused_ht<4>(const FusedArgs&, unsigned, int, hipStream_t);
+template hipError_t fused_max_resident_blocks_ht<4>(int, int*);
+
 }  // namespace nlc

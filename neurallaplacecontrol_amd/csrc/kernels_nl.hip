@@ -18,7 +18,7 @@
 // next step's layer-1 input, so x <- x + dx needs no lane movement either.
 //
 // Roofline: FP64 MFMA bound; per 16 samples and step (2 + h/4)*HT + (h/4)*nt3 + 2*nt3 MFMAs.
-#include "nlc_nl_kernels.h"
+#include "nlc_nl_launch.h"
 
 #if NLC_PHASE_CLOCKS
 namespace nlc {
@@ -35,35 +35,8 @@ extern "C" int nlc_debug_phase_clocks(unsigned long long* out16) {
 
 namespace nlc {
 
-// launchers for hidden width 16 * 8
-hipError_t launch_nl_rollout_h128(const RolloutArgs& a, hipStream_t s, bool split) {
-  if (split) {
-    const unsigned g16 = (unsigned)((a.K + 15) / 16);
-    switch (a.net.nt3) {
-#define X(N)                                                                                  \
-  case N:                                                                                     \
-    hipLaunchKernelGGL((nl_rollout_split_kernel<8, N>), dim3(g16), dim3(256), 0, s, a);   \
-    break;
-      NLC_FOR_NT3(X)
-#undef X
-      default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  const unsigned grid = (unsigned)((a.K + 63) / 64);
-  switch (a.net.nt3) {
-#define X(N)                                                                            \
-  case N:                                                                               \
-    hipLaunchKernelGGL((nl_rollout_kernel<8, N>), dim3(grid), dim3(256), 0, s, a);  \
-    break;
-    NLC_FOR_NT3(X)
-#undef X
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
+// this unit's instances: the Fourier rollout at h = 128 (the others: nlc_kernels.h)
+template hipError_t launch_nl_rollout_ht<8, false>(const RolloutArgs&, hipStream_t, bool);
 
 // ------------------------------------------------------------------ per-step tail of the staged (de Hoog) planner path
 // x <- x + dx (mppi_with_model.py:120-121), store, running cost and perturbation cost of horizon step t.  The staged path runs
@@ -100,7 +73,6 @@ hipError_t launch_step_tail(const StepTailArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-
 int nl_pick_nt3(int need) {
 #define X(N) \
   if (need <= N) return N;
@@ -109,63 +81,28 @@ int nl_pick_nt3(int need) {
   return -1;
 }
 
-// this width's forward / representation launchers: kernels_nl_fwd.hip, kernels_nl_fwdt.hip, kernels_nl_rep.hip
-hipError_t launch_nl_forward_h128_const(const ForwardArgs& a, hipStream_t s);    // kernels_nl_fwd.hip
-hipError_t launch_nl_forward_h128_general(const ForwardArgs& a, hipStream_t s);  // kernels_nl_fwdt.hip
-hipError_t launch_nl_forward_h128(const ForwardArgs& a, hipStream_t s) {
-  return a.const_t ? launch_nl_forward_h128_const(a, s) : launch_nl_forward_h128_general(a, s);
-}
-hipError_t launch_nl_repfunc_h128(const RepFuncArgs& a, hipStream_t s);
-// the other hidden widths: translation units of their own (kernels_nl_h64.hip, kernels_nl_h256*.hip)
-hipError_t launch_nl_rollout_h64(const RolloutArgs& a, hipStream_t s, bool split);
-hipError_t launch_nl_rollout_h256(const RolloutArgs& a, hipStream_t s, bool split);
-hipError_t launch_nl_forward_h64(const ForwardArgs& a, hipStream_t s);
-hipError_t launch_nl_forward_h256(const ForwardArgs& a, hipStream_t s);
-hipError_t launch_nl_repfunc_h64(const RepFuncArgs& a, hipStream_t s);
-hipError_t launch_nl_repfunc_h256(const RepFuncArgs& a, hipStream_t s);
-
-hipError_t launch_nl_rollout_lin_h64(const RolloutArgs& a, hipStream_t s, bool split);
-hipError_t launch_nl_rollout_lin_h128(const RolloutArgs& a, hipStream_t s, bool split);
-hipError_t launch_nl_rollout_lin_h256(const RolloutArgs& a, hipStream_t s, bool split);
 hipError_t launch_nl_rollout(const RolloutArgs& a, hipStream_t s, int force_variant) {
   if (a.K <= 0) return hipSuccess;
   // one wave per 16-sample tile fills the 1024 SIMDs only for K >= 16384; below that, split the tile over
   // the 4 waves of a workgroup (force_variant: 0 auto, 1 wave-per-tile, 2 split)
   const bool split = force_variant == 2 || (force_variant == 0 && a.K <= 8192);
-  if (a.net.lin) {
-    switch (a.net.h) {
-      case 64: return launch_nl_rollout_lin_h64(a, s, split);
-      case 128: return launch_nl_rollout_lin_h128(a, s, split);
-      case 256: return launch_nl_rollout_lin_h256(a, s, split);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  switch (a.net.h) {
-    case 64: return launch_nl_rollout_h64(a, s, split);
-    case 128: return launch_nl_rollout_h128(a, s, split);
-    case 256: return launch_nl_rollout_h256(a, s, split);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width(a.net.h, [&](auto ht) {
+    return a.net.lin ? launch_nl_rollout_ht<ht, true>(a, s, split) : launch_nl_rollout_ht<ht, false>(a, s, split);
+  });
 }
 
 hipError_t launch_nl_forward(const ForwardArgs& a, hipStream_t s) {
   if (a.N <= 0) return hipSuccess;
-  switch (a.net.h) {
-    case 64: return launch_nl_forward_h64(a, s);
-    case 128: return launch_nl_forward_h128(a, s);
-    case 256: return launch_nl_forward_h256(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width(a.net.h, [&](auto ht) {
+    return a.const_t ? launch_nl_forward_ht<ht, false>(a, s) : launch_nl_forward_ht<ht, true>(a, s);
+  });
 }
 
 hipError_t launch_nl_repfunc(const RepFuncArgs& a, hipStream_t s) {
   if (a.N <= 0) return hipSuccess;
-  switch (a.net.h) {
-    case 64: return launch_nl_repfunc_h64(a, s);
-    case 128: return launch_nl_repfunc_h128(a, s);
-    case 256: return launch_nl_repfunc_h256(a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_width(a.net.h, [&](auto ht) {
+    return a.general_t ? launch_nl_repfunc_ht<ht, true>(a, s) : launch_nl_repfunc_ht<ht, false>(a, s);
+  });
 }
 
 }  // namespace nlc

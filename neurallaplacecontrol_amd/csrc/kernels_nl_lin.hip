@@ -3,10 +3,10 @@
 // sum, so it rides the MFMA epilogue too -- with BOTH components of F = R e^{i theta} per term: two ILT MFMAs per slot group
 // against the coefficient fragments NlNetArgs::Cp (w_re / t) and Cp2 (-w_im / t), which nlc_mppi_configure folds for the
 // planner's constant prediction time.  A translation unit of its own: the Fourier instances keep their code and registers.
-#include "nlc_nl_lin_launch.h"
+#include "nlc_nl_launch.h"
 
 namespace nlc {
 
-NLC_DEFINE_LIN_ROLLOUT_LAUNCHER(h128, 8)
+template hipError_t launch_nl_rollout_ht<8, true>(const RolloutArgs&, hipStream_t, bool);
 
 }  // namespace nlc

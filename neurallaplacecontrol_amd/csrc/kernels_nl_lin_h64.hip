@@ -1,8 +1,8 @@
 // LIN instances of the rollout kernels (kernels_nl_lin.hip), hidden width 64.
-#include "nlc_nl_lin_launch.h"
+#include "nlc_nl_launch.h"
 
 namespace nlc {
 
-NLC_DEFINE_LIN_ROLLOUT_LAUNCHER(h64, 4)
+template hipError_t launch_nl_rollout_ht<4, true>(const RolloutArgs&, hipStream_t, bool);
 
 }  // namespace nlc

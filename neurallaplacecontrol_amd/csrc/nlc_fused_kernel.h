@@ -510,36 +510,39 @@ __global__ __launch_bounds__(256, BPC) void nl_plan_fused_kernel(const FusedArgs
   if (NLC_FUSED_TRACE && wv == 0) wave_add_one(sync + kFusedStatExited, lane);
 }
 
-}  // namespace nlc
+// Launchers of one hidden width h = 16 HT, declared in nlc_kernels.h (kernels_fused{,_h64,_h256}.hip instantiate them).  Per
+// width: the GRU hidden G = h / 2 and the two workgroups-per-CU instances BPC_LO / BPC_HI (equal: one instance).
+template <int HT>
+struct FusedWidth;
+template <>
+struct FusedWidth<4> { static constexpr int G = 32, BPC_LO = 3, BPC_HI = 4; };
+template <>
+struct FusedWidth<8> { static constexpr int G = 64, BPC_LO = 3, BPC_HI = 4; };
+template <>
+struct FusedWidth<16> { static constexpr int G = 128, BPC_LO = 2, BPC_HI = 2; };
+constexpr int kFusedMaxNt3 = 21;  // the fused body's layer-3 tile counts: NLC_FOR_NT3 up to 21
 
-// One translation unit per hidden width (kernels_fused.hip: h = 128, the harness's hidden_units; kernels_fused_h64.hip: the
-// class default w_nl.py:72; kernels_fused_h256.hip), so the instances compile in parallel.  BPC_LO / BPC_HI: the two
-// workgroups-per-CU instances of the width (equal: one instance).
-#define NLC_FUSED_DEFINE_LAUNCHERS(SUFFIX, HT_, G_, BPC_LO, BPC_HI)                                                     \
-  hipError_t fused_max_resident_blocks_##SUFFIX(int bpc_built, int* blocks_per_cu) {                                   \
-    const void* f = bpc_built == BPC_LO ? (const void*)nl_plan_fused_kernel<HT_, 11, G_, BPC_LO>                        \
-                                        : (const void*)nl_plan_fused_kernel<HT_, 11, G_, BPC_HI>;                       \
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 256, 0);                                      \
-  }                                                                                                                     \
-  hipError_t launch_nl_plan_fused_##SUFFIX(const FusedArgs& a, unsigned grid, int bpc_built, hipStream_t s) {          \
-    if (bpc_built != BPC_LO && bpc_built != BPC_HI) return hipErrorInvalidValue;                                        \
-    switch (a.r.net.nt3) {                                                                                              \
-      NLC_FUSED_CASE(7, HT_, G_, BPC_LO, BPC_HI)                                                                        \
-      NLC_FUSED_CASE(9, HT_, G_, BPC_LO, BPC_HI)                                                                        \
-      NLC_FUSED_CASE(11, HT_, G_, BPC_LO, BPC_HI)                                                                       \
-      NLC_FUSED_CASE(13, HT_, G_, BPC_LO, BPC_HI)                                                                       \
-      NLC_FUSED_CASE(17, HT_, G_, BPC_LO, BPC_HI)                                                                       \
-      NLC_FUSED_CASE(21, HT_, G_, BPC_LO, BPC_HI)                                                                       \
-      default:                                                                                                          \
-        return hipErrorInvalidValue;                                                                                    \
-    }                                                                                                                   \
-    return hipGetLastError();                                                                                           \
-  }
-#define NLC_FUSED_CASE(N, HT_, G_, BPC_LO, BPC_HI)                                                                      \
-  case N:                                                                                                               \
-    if (bpc_built == BPC_LO) {                                                                                          \
-      hipLaunchKernelGGL((nl_plan_fused_kernel<HT_, N, G_, BPC_LO>), dim3(grid), dim3(256), 0, s, a);                   \
-    } else {                                                                                                            \
-      hipLaunchKernelGGL((nl_plan_fused_kernel<HT_, N, G_, BPC_HI>), dim3(grid), dim3(256), 0, s, a);                   \
-    }                                                                                                                   \
-    break;
+template <int HT>
+hipError_t fused_max_resident_blocks_ht(int bpc_built, int* blocks_per_cu) {
+  using W = FusedWidth<HT>;
+  const void* f = bpc_built == W::BPC_LO ? (const void*)nl_plan_fused_kernel<HT, 11, W::G, W::BPC_LO>
+                                         : (const void*)nl_plan_fused_kernel<HT, 11, W::G, W::BPC_HI>;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 256, 0);
+}
+
+template <int HT, int BPC>
+hipError_t launch_nl_plan_fused_bpc(const FusedArgs& a, unsigned grid, hipStream_t s) {
+  return launch_nt3<kFusedMaxNt3>(a.r.net.nt3, [&](auto nt3) {
+    hipLaunchKernelGGL((nl_plan_fused_kernel<HT, nt3, FusedWidth<HT>::G, BPC>), dim3(grid), dim3(256), 0, s, a);
+  });
+}
+
+template <int HT>
+hipError_t launch_nl_plan_fused_ht(const FusedArgs& a, unsigned grid, int bpc_built, hipStream_t s) {
+  using W = FusedWidth<HT>;
+  if (bpc_built == W::BPC_LO) return launch_nl_plan_fused_bpc<HT, W::BPC_LO>(a, grid, s);
+  if (bpc_built == W::BPC_HI) return launch_nl_plan_fused_bpc<HT, W::BPC_HI>(a, grid, s);
+  return hipErrorInvalidValue;
+}
+
+}  // namespace nlc

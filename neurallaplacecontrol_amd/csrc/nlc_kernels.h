@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <climits>
+#include <type_traits>
+
 #include "../../include/nlc.h"
 
 namespace nlc {
@@ -553,6 +556,78 @@ struct FusedArgs {   // the kernel's one by-value argument
 // bpc_built: the instance compiled for 3 or 4 workgroups per CU (kernels_fused.hip)
 hipError_t launch_nl_plan_fused(const FusedArgs& a, int g, unsigned grid, int bpc_built, hipStream_t s);
 hipError_t fused_max_resident_blocks(int h, int bpc_built, int* blocks_per_cu);
+
+// ------------------------------------------------------------------ launchers of one hidden width h = 16 HT
+// Defined in nlc_nl_launch.h / nlc_fused_kernel.h and instantiated in the units listed below, one per width and kernel family
+// so the instances compile in parallel; the extern declarations keep every other unit from instantiating them again.
+// launch_nl_rollout / _forward / _repfunc (kernels_nl.hip) and launch_nl_plan_fused (kernels_fused.hip) pick the width.
+template <int HT, bool LIN>
+hipError_t launch_nl_rollout_ht(const RolloutArgs& a, hipStream_t s, bool split);
+template <int HT, bool GENERAL_T>
+hipError_t launch_nl_forward_ht(const ForwardArgs& a, hipStream_t s);
+template <int HT, bool GENERAL_T>
+hipError_t launch_nl_repfunc_ht(const RepFuncArgs& a, hipStream_t s);
+template <int HT>
+hipError_t launch_nl_plan_fused_ht(const FusedArgs& a, unsigned grid, int bpc_built, hipStream_t s);
+template <int HT>
+hipError_t fused_max_resident_blocks_ht(int bpc_built, int* blocks_per_cu);
+
+extern template hipError_t launch_nl_rollout_ht<4, false>(const RolloutArgs&, hipStream_t, bool);   // kernels_nl_h64.hip
+extern template hipError_t launch_nl_rollout_ht<8, false>(const RolloutArgs&, hipStream_t, bool);   // kernels_nl.hip
+extern template hipError_t launch_nl_rollout_ht<16, false>(const RolloutArgs&, hipStream_t, bool);  // kernels_nl_h256.hip
+extern template hipError_t launch_nl_rollout_ht<4, true>(const RolloutArgs&, hipStream_t, bool);    // kernels_nl_lin_h64.hip
+extern template hipError_t launch_nl_rollout_ht<8, true>(const RolloutArgs&, hipStream_t, bool);    // kernels_nl_lin.hip
+extern template hipError_t launch_nl_rollout_ht<16, true>(const RolloutArgs&, hipStream_t, bool);   // kernels_nl_lin_h256.hip
+extern template hipError_t launch_nl_forward_ht<4, false>(const ForwardArgs&, hipStream_t);         // kernels_nl_h64.hip
+extern template hipError_t launch_nl_forward_ht<4, true>(const ForwardArgs&, hipStream_t);          // kernels_nl_h64.hip
+extern template hipError_t launch_nl_forward_ht<8, false>(const ForwardArgs&, hipStream_t);         // kernels_nl_fwd.hip
+extern template hipError_t launch_nl_forward_ht<8, true>(const ForwardArgs&, hipStream_t);          // kernels_nl_fwdt.hip
+extern template hipError_t launch_nl_forward_ht<16, false>(const ForwardArgs&, hipStream_t);        // kernels_nl_h256_fwd.hip
+extern template hipError_t launch_nl_forward_ht<16, true>(const ForwardArgs&, hipStream_t);         // kernels_nl_h256_fwdt.hip
+extern template hipError_t launch_nl_repfunc_ht<4, false>(const RepFuncArgs&, hipStream_t);         // kernels_nl_h64.hip
+extern template hipError_t launch_nl_repfunc_ht<4, true>(const RepFuncArgs&, hipStream_t);          // kernels_nl_h64.hip
+extern template hipError_t launch_nl_repfunc_ht<8, false>(const RepFuncArgs&, hipStream_t);         // kernels_nl_rep.hip
+extern template hipError_t launch_nl_repfunc_ht<8, true>(const RepFuncArgs&, hipStream_t);          // kernels_nl_rep.hip
+extern template hipError_t launch_nl_repfunc_ht<16, false>(const RepFuncArgs&, hipStream_t);        // kernels_nl_h256_rep.hip
+extern template hipError_t launch_nl_repfunc_ht<16, true>(const RepFuncArgs&, hipStream_t);         // kernels_nl_h256_rep.hip
+extern template hipError_t launch_nl_plan_fused_ht<4>(const FusedArgs&, unsigned, int, hipStream_t);  // kernels_fused_h64.hip
+extern template hipError_t launch_nl_plan_fused_ht<8>(const FusedArgs&, unsigned, int, hipStream_t);  // kernels_fused.hip
+extern template hipError_t launch_nl_plan_fused_ht<16>(const FusedArgs&, unsigned, int, hipStream_t);  // kernels_fused_h256.hip
+extern template hipError_t fused_max_resident_blocks_ht<4>(int, int*);                              // kernels_fused_h64.hip
+extern template hipError_t fused_max_resident_blocks_ht<8>(int, int*);                              // kernels_fused.hip
+extern template hipError_t fused_max_resident_blocks_ht<16>(int, int*);                             // kernels_fused_h256.hip
+
+// hidden width h -> f(std::integral_constant<int, HT>) for the widths with instances, h = 16 HT; hipErrorInvalidValue otherwise
+template <class F>
+hipError_t with_width(int h, F&& f) {
+  switch (h) {
+    case 64: return f(std::integral_constant<int, 4>{});
+    case 128: return f(std::integral_constant<int, 8>{});
+    case 256: return f(std::integral_constant<int, 16>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// instantiated layer-3 tile counts; other (d,S) round up to the next one (zero-padded tiles)
+#define NLC_FOR_NT3(X) X(7) X(9) X(11) X(13) X(17) X(21) X(25)
+
+// the nt3 switch of the launchers: f(std::integral_constant<int, N>) launches the instance for nt3 == N, N in NLC_FOR_NT3 up
+// to MAX_NT3; returns the launch's status, or hipErrorInvalidValue for any other nt3
+template <int MAX_NT3 = INT_MAX, class F>
+hipError_t launch_nt3(int nt3, F&& f) {
+  switch (nt3) {
+#define X(N)                               \
+  case N:                                  \
+    if constexpr (N <= MAX_NT3) {          \
+      f(std::integral_constant<int, N>{}); \
+      return hipGetLastError();            \
+    }                                      \
+    break;
+    NLC_FOR_NT3(X)
+#undef X
+  }
+  return hipErrorInvalidValue;
+}
 
 
 }  // namespace nlc

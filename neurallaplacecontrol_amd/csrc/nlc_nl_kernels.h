@@ -1,7 +1,6 @@
-// Kernel templates of the representation MLP + ILT + rollout (dataflow: top of kernels_nl.hip) and the launcher bodies
-// for ONE hidden width h = 16 HT.  Each width is its own translation unit (kernels_nl.hip: h = 128, the harness's
-// hidden_units; kernels_nl_h64.hip: the class default w_nl.py:72; kernels_nl_h256.hip: config.py's alternative) so
-// the three sets of instantiations compile in parallel.
+// Kernel templates of the representation MLP + ILT + rollout (dataflow: top of kernels_nl.hip) for hidden width h = 16 HT:
+// 64 (HT = 4), the class default w_nl.py:72; 128, the harness's hidden_units; 256, config.py's alternative.  Their launchers
+// are in nlc_nl_launch.h; nlc_kernels.h lists the translation unit that holds each width's instances.
 #pragma once
 #include "nlc_device.h"
 #include "nlc_envcost.h"
@@ -264,8 +263,5 @@ __global__ __launch_bounds__(256, 2) void nl_repfunc_split_kernel(const RepFuncA
   __shared__ double H1[KS * 64], H2[KS * 64];
   repfunc_split_tile<HT, NT3>(a, (int64_t)blockIdx.x, H1, H2);
 }
-
-// instantiated layer-3 tile counts; other (d,S) round up to the next one (zero-padded tiles)
-#define NLC_FOR_NT3(X) X(7) X(9) X(11) X(13) X(17) X(21) X(25)
 
 }  // namespace nlc
