@@ -133,45 +133,71 @@ NLC_HD void tanh_pair_d(double xa, double xb, double* ta, double* tb) {
   *tb = copysign((-eb * da) * R, xb);
 }
 
-// ---- hidden-layer activations of the rollout kernels (round 3): instruction count, not ulps.
-// e^{-2|x|}: one-constant reduction (|n| ln2 2^-53 <= 3e-14 where it matters), e^r = (q r + 1) r + 1 with q of degree 7
-// (Chebyshev interpolation of (e^r - 1 - r)/r^2 on |r| <= ln2/2: relative error 7.4e-14), nine FMAs in one Horner chain;
-// the clamp is a bare v_max_f64 on the device (fmax() first canonicalises its operand with a second v_max_f64).
-NLC_HD double exp_m2abs_fast(double x) {
-  double y = -2.0 * fabs(x);
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm("v_max_f64 %0, %1, %2" : "=v"(y) : "v"(y), "s"(-745.0));
-#else
-  y = y < -745.0 ? -745.0 : y;
+// ---- e^y as a ratio, for consumers that divide anyway (sigmoid = 1/(1 + e), tanh = (1 - e)/(1 + e)): the denominator of
+// e^r rides in the consumer's reciprocal.  On the reduced range |r| <= ln2/2, e^r = (E + r O)/(E - r O) with s = r^2,
+// E = 1 + c2 s + c4 s^2, O = c1 + c3 s: the shape of the [4/4] Pade approximant (whose own error is 2.9e-12 at |r| = ln2/2)
+// with minimax coefficients for the relative error of e^r (Remez exchange on |r| <= ln2/2 (1 + 1e-6), tools/exp_ratio_remez.py):
+// 1.11e-14 before rounding.  Six FMA-class instructions, against the nine FMAs of the Horner chain it replaces.
+// T is double or (device, clang) a two-wide ext-vector of doubles; HALF: the argument is r/2 (the coefficients are scaled by
+// powers of two, so num and den are exactly those of r).
+NLC_HD double fma_e(double a, double b, double c) { return fma(a, b, c); }
+#if defined(__clang__)
+typedef double v2d_e __attribute__((ext_vector_type(2)));
+NLC_HD v2d_e fma_e(v2d_e a, v2d_e b, v2d_e c) { return __builtin_elementwise_fma(a, b, c); }
 #endif
+template <bool HALF, class T>
+NLC_HD void exp_ratio_reduced(T r, T* num, T* den) {
+  const double f = HALF ? 2.0 : 1.0;  // r = f * (the argument)
+  const T s = r * r;
+  const T e = fma_e(fma_e(s, (T)(0x1.37bddaaa3389ap-11 * f * f * f * f), (T)(0x1.b6d3630138edep-4 * f * f)), s, (T)1.0);
+  const T o = fma_e(s, (T)(0x1.85f836b858dadp-7 * f * f * f), (T)(0x1.ffffffffff5dep-2 * f));
+  *num = fma_e(r, o, e);
+  *den = fma_e(-r, o, e);
+}
+// y = n ln2 + r by the 1.5 * 2^52 shift with ONE ln2 constant (|n| ln2 2^-53 <= 3e-14 for every argument that matters); the
+// integer is the low word of the shifted sum *sh (exp_shift_int).  e^y = 2^n num / den.  HALF: *num / *den from (y / 2 reduced), for a
+// caller that holds y / 2 (tanh: y = -2|x|, the argument -|x|) -- the same reduction and the same values.
+template <bool HALF, class T>
+NLC_HD void exp_ratio_parts(T y, T* num, T* den, T* sh) {
   const double kShift = 6755399441055744.0;
-  const double sh = fma(y, 1.44269504088896338700e+00, kShift);
-  const double fn = sh - kShift;
-  const double r = fma(-fn, 6.93147180559945286227e-01, y);
+  const double f = HALF ? 2.0 : 1.0;
+  *sh = fma_e(y, (T)(1.44269504088896338700e+00 * f), (T)kShift);
+  const T fn = *sh - kShift;
+  exp_ratio_reduced<HALF>(fma_e(-fn, (T)(6.93147180559945286227e-01 / f), y), num, den);
+}
+NLC_HD int exp_shift_int(double sh) {
   int64_t bits;
   __builtin_memcpy(&bits, &sh, sizeof(bits));
-  const int n = (int)(uint32_t)(bits & 0xffffffffLL);
-  double q = 0x1.72ad458027fbcp-19;
-  q = fma(q, r, 0x1.a136bf03ec612p-16);
-  q = fma(q, r, 0x1.a019c36bc053cp-13);
-  q = fma(q, r, 0x1.6c166bde96885p-10);
-  q = fma(q, r, 0x1.111111170bc08p-7);
-  q = fma(q, r, 0x1.55555565c7e0ep-5);
-  q = fma(q, r, 0x1.5555555554f96p-3);
-  q = fma(q, r, 0x1.fffffffffe062p-2);
-  q = fma(q, r, 1.0);
-  q = fma(q, r, 1.0);
-  return ldexp(q, n);
+  return (int)(uint32_t)(bits & 0xffffffffLL);
 }
-// Two tanh values, t = (1 - e)/(1 + e) with e = e^{-2|x|}, ONE reciprocal for both (denominators in [1, 2]).  Absolute
-// error <= 1.5e-13 (the parity bar is 1e-5, the tests hold 1e-9); a saturated input gives 1 within an ulp.  Hidden
-// layers only: the sphere map keeps tanh_d (exact saturation, few ulp).
+NLC_HD double min_abs(double x, double hi) {  // min(|x|, hi); a bare v_min_f64 on the device (fmin() first
+                                               // canonicalises its operand with a second v_min_f64)
+#if defined(__HIP_DEVICE_COMPILE__)
+  double r;
+  asm("v_min_f64 %0, |%1|, %2" : "=v"(r) : "v"(x), "s"(hi));
+  return r;
+#else
+  const double a = fabs(x);
+  return a < hi ? a : hi;
+#endif
+}
+
+// ---- hidden-layer activations of the rollout kernels: instruction count, not ulps.
+// Two tanh values, t = (D - M)/(D + M) with M / D = e^{-2|x|} (exp_ratio_parts, M = 2^n num), ONE reciprocal for both
+// (D + M in [0.8, 2.4]).  |x| is clamped at 372.5 (e^{-745}: M flushes to 0).  Absolute error <= 1.5e-13 (the parity bar
+// is 1e-5, the tests hold 1e-9); a saturated input gives 1 within an ulp.  Hidden layers only: the sphere map keeps tanh_d
+// (exact saturation, few ulp).
 NLC_HD void tanh_pair_fast(double xa, double xb, double* ta, double* tb) {
-  const double ea = exp_m2abs_fast(xa), eb = exp_m2abs_fast(xb);
-  const double da = 1.0 + ea, db = 1.0 + eb;
-  const double R = rcp_refined(da * db);
-  *ta = copysign(((1.0 - ea) * db) * R, xa);
-  *tb = copysign(((1.0 - eb) * da) * R, xb);
+  const double ma = min_abs(xa, 372.5), mb = min_abs(xb, 372.5);
+  double na, da, sa, nb, db, sb;
+  exp_ratio_parts<true>(-ma, &na, &da, &sa);
+  exp_ratio_parts<true>(-mb, &nb, &db, &sb);
+  na = ldexp(na, exp_shift_int(sa));
+  nb = ldexp(nb, exp_shift_int(sb));
+  const double qa = da + na, qb = db + nb;
+  const double R = rcp_refined(qa * qb);
+  *ta = copysign(((da - na) * qb) * R, xa);
+  *tb = copysign(((db - nb) * qa) * R, xb);
 }
 
 // fdlibm __kernel_sin / __kernel_cos on |y| <= pi/4 (+ a few ulp)
