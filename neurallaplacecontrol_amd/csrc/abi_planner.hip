@@ -243,6 +243,29 @@ int launch_shift_perturb(nlc_ctx* c, RolloutCall& call) {
   NLC_HIP(c, launch_perturb(p, c->stream));
   return NLC_OK;
 }
+
+// the samples and the cost terms of the command's rollout, whichever body runs it; c->U[c->ucur] is the shifted sequence
+SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call) {
+  const nlc_mppi_desc& d = c->pd;
+  SampleCostArgs a{};
+  a.K = call.KE;
+  a.Kep = d.K;
+  a.T = d.T;
+  a.nu = d.nu;
+  a.env = d.cost_external ? -1 : d.env;
+  a.state_per_sample = call.state_per_sample;
+  a.state0 = call.state_dev;
+  a.perturbed = call.buf->perturbed;
+  a.noise = call.buf->noise;
+  a.U = c->U[c->ucur];
+  for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) a.sigma_inv[i] = d.noise_sigma_inv[i];
+  a.lambda_ = d.lambda_;
+  a.u_scale = d.u_scale;
+  a.noise_abs_cost = d.noise_abs_cost;
+  a.states = call.buf->states;
+  a.cost_total = call.buf->cost_total;
+  return a;
+}
 }  // namespace host
 }  // namespace nlc
 
@@ -309,8 +332,6 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
   call.state_per_sample = state_per_sample;
   call.rng = rng;
   call.replay = replay;
-  const WsLayout& w = call.w;
-  double* ws = call.ws;
   double* state_dev = call.state_dev;
   double* abuf_dev = call.abuf_dev;
   const int64_t KE = call.KE;
@@ -410,26 +431,11 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
   }
   if (d.dynamics == NLC_DYN_NL) return rollout_nl(c, call);
   c->last_body = d.dynamics == NLC_DYN_NODE ? 8 : (d.dynamics == NLC_DYN_DTRNN ? 7 : 6);
+  const SampleCostArgs sc = sample_cost_args(c, call);
   if (d.dynamics == NLC_DYN_NODE) {
-    NodeRolloutArgs r{};
+    NodeRolloutArgs r{sc};
     r.net = c->node;
     r.net.nsub = node_substeps(d.ts_pred / c->nd.time_div, c->nd.step_size, r.net.hsub, 8);
-    r.K = KE;
-    r.Kep = d.K;
-    r.T = d.T;
-    r.nu = d.nu;
-    r.env = d.cost_external ? -1 : d.env;
-    r.state_per_sample = state_per_sample;
-    r.state0 = state_dev;
-    r.perturbed = buf->perturbed;
-    r.noise = buf->noise;
-    r.U = c->U[c->ucur];
-    for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) r.sigma_inv[i] = d.noise_sigma_inv[i];
-    r.lambda_ = d.lambda_;
-    r.u_scale = d.u_scale;
-    r.noise_abs_cost = d.noise_abs_cost;
-    r.states = buf->states;
-    r.cost_total = buf->cost_total;
     ProfScope ps(c, "node_rollout_kernel");
     NLC_HIP(c, launch_node_rollout(r, c->node_ht, c->stream));
   } else if (d.dynamics == NLC_DYN_DTRNN) {
@@ -443,58 +449,26 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
     g.Kep = d.K;
     g.K = KE;
     g.N = KE * d.T;
-    g.out = ws + w.rq;
+    g.out = call.ws + call.w.rq;
     {
       ProfScope ps(c, "rnn_encode_kernel");
       NLC_HIP(c, launch_rnn_encode(g, c->rd.hidden, c->stream));
     }
-    RnnRolloutArgs r{};
+    RnnRolloutArgs r{sc};
     r.head = c->rnn_head;
-    r.K = KE;
-    r.Kep = d.K;
-    r.T = d.T;
-    r.nu = d.nu;
-    r.env = d.cost_external ? -1 : d.env;
-    r.state_per_sample = state_per_sample;
-    r.state0 = state_dev;
-    r.q = ws + w.rq;
-    r.perturbed = buf->perturbed;
-    r.noise = buf->noise;
-    r.U = c->U[c->ucur];
-    for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) r.sigma_inv[i] = d.noise_sigma_inv[i];
-    r.lambda_ = d.lambda_;
-    r.u_scale = d.u_scale;
+    r.q = g.out;
     r.ts = d.ts_pred;
-    r.noise_abs_cost = d.noise_abs_cost;
-    r.states = buf->states;
-    r.cost_total = buf->cost_total;
     ProfScope ps(c, "rnn_rollout_kernel");
     NLC_HIP(c, launch_rnn_rollout(r, c->stream));
   } else {
-    OracleRolloutArgs r{};
-    r.K = KE;
-    r.Kep = d.K;
-    r.T = d.T;
-    r.nu = d.nu;
+    OracleRolloutArgs r{sc};
     r.B = d.B;
     r.d = d.d;
-    r.env = d.env;
-    r.cost_env = d.cost_external ? -1 : d.env;
     r.delay = d.delay;
     r.friction = d.friction;
-    r.state_per_sample = state_per_sample;
-    r.state0 = state_dev;
+    r.dyn_env = d.env;
     r.abuf = abuf_dev;
-    r.perturbed = buf->perturbed;
-    r.noise = buf->noise;
-    r.U = c->U[c->ucur];
-    for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) r.sigma_inv[i] = d.noise_sigma_inv[i];
-    r.lambda_ = d.lambda_;
-    r.u_scale = d.u_scale;
     r.ts = d.ts_pred;
-    r.noise_abs_cost = d.noise_abs_cost;
-    r.states = buf->states;
-    r.cost_total = buf->cost_total;
     ProfScope ps(c, "oracle_rollout_kernel");
     NLC_HIP(c, launch_oracle_rollout(r, c->stream));
   }

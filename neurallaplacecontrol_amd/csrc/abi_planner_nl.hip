@@ -40,15 +40,82 @@ inline double now_s() {
   return (double)ts.tv_sec + (double)ts.tv_nsec * 1e-9;
 }
 
+// the context's fork / join events and side streams are created on first use and kept: this one if it is still null ...
+int ensure(nlc_ctx* c, hipEvent_t& e) {
+  if (!e) NLC_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return NLC_OK;
+}
+int ensure(nlc_ctx* c, hipStream_t& s) {
+  if (!s) NLC_HIP(c, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  return NLC_OK;
+}
+// ... or a vector of them grown to n
+template <class H>
+int grow(nlc_ctx* c, std::vector<H>& v, int n) {
+  while ((int)v.size() < n) {
+    H h = nullptr;
+    if (int rc = ensure(c, h)) return rc;
+    v.push_back(h);
+  }
+  return NLC_OK;
+}
+
+// the block's fields into an argument block that spells them out itself (RolloutArgs, DehoogChainArgs: nlc_kernels.h); Kep,
+// which the latter has not, is the caller's
+template <class A>
+void put_sample_cost(A& a, const SampleCostArgs& s) {
+  a.K = s.K;
+  a.T = s.T;
+  a.nu = s.nu;
+  a.env = s.env;
+  a.state_per_sample = s.state_per_sample;
+  a.state0 = s.state0;
+  a.perturbed = s.perturbed;
+  a.noise = s.noise;
+  a.U = s.U;
+  std::memcpy(a.sigma_inv, s.sigma_inv, sizeof(a.sigma_inv));
+  a.lambda_ = s.lambda_;
+  a.u_scale = s.u_scale;
+  a.noise_abs_cost = s.noise_abs_cost;
+  a.states = s.states;
+  a.cost_total = s.cost_total;
+}
+
+// GRU encode in C horizon chunks of Tc steps on a low-priority stream of its own, forked behind what c->stream holds (the
+// perturb kernel, the staged inputs); ev_gru[ch] tells the consumer that the latents of chunk ch are there
+int gru_encode_chunks(nlc_ctx* c, GruArgs& g, int64_t KE, int C, int Tc, bool coop, unsigned lds_pad) {
+  const int T = c->pd.T;
+  if (!c->gru_stream) {
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = lowest priority: the consumer's workgroups go first
+    NLC_HIP(c, hipStreamCreateWithPriority(&c->gru_stream, hipStreamNonBlocking, lo));
+  }
+  if (int rc = ensure(c, c->ev_fork)) return rc;
+  if (int rc = grow(c, c->ev_gru, C)) return rc;
+  NLC_HIP(c, hipEventRecord(c->ev_fork, c->stream));
+  NLC_HIP(c, hipStreamWaitEvent(c->gru_stream, c->ev_fork, 0));
+  for (int ch = 0; ch < C; ++ch) {
+    g.t0 = ch * Tc;
+    g.Tc = (g.t0 + Tc <= T) ? Tc : T - g.t0;
+    if (g.Tc <= 0) break;
+    g.N = KE * g.Tc;
+    {
+      ProfScope ps(c, "gru_encode_kernel", c->gru_stream, true);
+      NLC_HIP(c, launch_gru_encode(g, c->g, c->gru_stream, coop, lds_pad));
+    }
+    NLC_HIP(c, hipEventRecord(c->ev_gru[ch], c->gru_stream));
+  }
+  return NLC_OK;
+}
+
 // staged planner path (BASELINE configs[4]): hoisted GRU, then per horizon step two launches -- [tail of the previous step +]
 // representation function -> F_k, then de Hoog ILT -> dx; fixed_tablot / stehfest models (option linear_fused = 0) take the
 // same path with the slot-major linear ILT in de Hoog's place.  Everything stays on the device.
-int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r, double* pa) {
+int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc, GruArgs& g, RolloutArgs& r, double* pa) {
   const nlc_mppi_desc& d = c->pd;
   const nlc_mppi_buffers* buf = call.buf;
   const WsLayout& w = call.w;
   double* ws = call.ws;
-  double* state_dev = call.state_dev;
   const int64_t KE = call.KE;
   const int state_per_sample = call.state_per_sample;
   // staged de Hoog planner path (BASELINE configs[4]): hoisted GRU, then per horizon step three launches --
@@ -127,28 +194,14 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r,
   c->last_body = chain ? 5 : 4;
   if (chain) {
     DehoogChainArgs ca{};
+    put_sample_cost(ca, sc);
     ca.net = r.net;
-    ca.K = KE;
-    ca.T = d.T;
-    ca.nu = d.nu;
-    ca.env = d.cost_external ? -1 : d.env;
-    ca.state_per_sample = state_per_sample;
-    ca.state0 = state_dev;
     ca.pa = pa;
-    ca.perturbed = buf->perturbed;
-    ca.noise = buf->noise;
-    ca.U = r.U;
-    for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) ca.sigma_inv[i] = d.noise_sigma_inv[i];
-    ca.lambda_ = d.lambda_;
-    ca.u_scale = d.u_scale;
-    ca.noise_abs_cost = d.noise_abs_cost;
     ca.tn = c->tn;
     ca.slot = c->slot_dev;
     ca.eidx = c->eidx_dev;
     ca.fre = ws + w.fre;  // one private (8 nt3) x 64 block per 64 samples
     ca.fim = ws + w.fim;
-    ca.states = buf->states;
-    ca.cost_total = buf->cost_total;
     ca.phases = c->opt_dehoog_chain_phases;
     {
       ProfScope ps(c, "nl_dehoog_chain_kernel");
@@ -160,32 +213,9 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r,
   double* tconst = ws + w.tconst;
   NLC_HIP(c, hipMemcpyAsync(tconst, &c->tn, sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (C > 1) {
-    if (!c->gru_stream) {
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = lowest priority: the step chain's workgroups go first
-      NLC_HIP(c, hipStreamCreateWithPriority(&c->gru_stream, hipStreamNonBlocking, lo));
-    }
-    if (!c->ev_fork) NLC_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    while ((int)c->ev_gru.size() < C) {
-      hipEvent_t e2 = nullptr;
-      NLC_HIP(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-      c->ev_gru.push_back(e2);
-    }
-    NLC_HIP(c, hipEventRecord(c->ev_fork, c->stream));  // behind the perturb kernel and the staged inputs
-    NLC_HIP(c, hipStreamWaitEvent(c->gru_stream, c->ev_fork, 0));
-    for (int ch = 0; ch < C; ++ch) {
-      g.t0 = ch * Tc;
-      g.Tc = (g.t0 + Tc <= d.T) ? Tc : d.T - g.t0;
-      if (g.Tc <= 0) break;
-      g.N = KE * g.Tc;
-      {
-        ProfScope ps(c, "gru_encode_kernel", c->gru_stream, true);
-        // (cooperative kernel at reduced occupancy unless "gru_coop" = 0 asks for the wave-per-tile one)
-        const bool coop = c->opt_gru_coop != 0;
-        NLC_HIP(c, launch_gru_encode(g, c->g, c->gru_stream, coop, coop ? (unsigned)c->opt_dehoog_gru_lds_pad : 0u));
-      }
-      NLC_HIP(c, hipEventRecord(c->ev_gru[ch], c->gru_stream));
-    }
+    // (cooperative kernel at reduced occupancy unless "gru_coop" = 0 asks for the wave-per-tile one)
+    const bool coop = c->opt_gru_coop != 0;
+    if (int rc = gru_encode_chunks(c, g, KE, C, Tc, coop, coop ? (unsigned)c->opt_dehoog_gru_lds_pad : 0u)) return rc;
   }
   RepFuncArgs rf{};
   rf.net = r.net;
@@ -204,27 +234,11 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r,
   rf.split = c->md.h == 128 && c->opt_repfunc_split != 0;
   IltArgs ia{nullptr, nullptr, tconst, ws + w.dx, KE, d.d, c->S, c->md.ilt.alpha, std::log(c->md.ilt.tol),
              c->md.ilt.scale, rf.fre, rf.fim, 1.0, 0, 0, 0, 0, c->eidx_dev};
-  StepTailArgs st{};
-  st.K = KE;
-  st.Kep = d.K;
-  st.T = d.T;
-  st.nu = d.nu;
+  StepTailArgs st{sc};
   st.d = d.d;
-  st.env = d.cost_external ? -1 : d.env;
-  st.state_per_sample = state_per_sample;
-  st.state0 = state_dev;
   st.x = r.xcarry;
   st.dx = ws + w.dx;
   st.ccarry = r.ccarry;
-  st.perturbed = buf->perturbed;
-  st.noise = buf->noise;
-  st.U = r.U;
-  for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) st.sigma_inv[i] = d.noise_sigma_inv[i];
-  st.lambda_ = d.lambda_;
-  st.u_scale = d.u_scale;
-  st.noise_abs_cost = d.noise_abs_cost;
-  st.states = buf->states;
-  st.cost_total = buf->cost_total;
   // two launches per horizon step: [tail of step t-1 +] representation function -> F, then de Hoog -> dx; the tail
   // of the LAST step is a launch of its own.
   // Round 3: the population is cut into P contiguous parts (multiples of 64 samples) whose 2 T + 1 launches run on P
@@ -239,17 +253,9 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r,
   if (P > 4) P = 4;
   while (P > 1 && KE / P < 1024) --P;
   if (P > 1) {
-    while ((int)c->aux_streams.size() < P - 1) {
-      hipStream_t s2 = nullptr;
-      NLC_HIP(c, hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-      c->aux_streams.push_back(s2);
-    }
-    if (!c->ev_fork) NLC_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    while ((int)c->ev_join.size() < P - 1) {
-      hipEvent_t e2 = nullptr;
-      NLC_HIP(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-      c->ev_join.push_back(e2);
-    }
+    if (int rc = grow(c, c->aux_streams, P - 1)) return rc;
+    if (int rc = ensure(c, c->ev_fork)) return rc;
+    if (int rc = grow(c, c->ev_join, P - 1)) return rc;
     NLC_HIP(c, hipEventRecord(c->ev_fork, c->stream));  // behind the GRU encode and the staged inputs
     for (int h = 1; h < P; ++h) NLC_HIP(c, hipStreamWaitEvent(c->aux_streams[h - 1], c->ev_fork, 0));
   }
@@ -266,16 +272,10 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r,
   auto part = [&](int h, RepFuncArgs& rfp, IltArgs& iap, StepTailArgs& stp) {
     const int64_t o = off_h[h], n = n_h[h];
     stp = st;
-    stp.K = n;
-    stp.Kep = P > 1 ? n : d.K;
-    stp.state0 = state_dev + (state_per_sample ? o * d.d : 0);
+    static_cast<SampleCostArgs&>(stp) = st.part(o, n, d.d);
     stp.x = st.x + o * d.d;
     stp.dx = st.dx + o * d.d;
     stp.ccarry = st.ccarry + o * 2;
-    stp.perturbed = st.perturbed + o * d.T * d.nu;
-    stp.noise = st.noise + o * d.T * d.nu;
-    stp.states = st.states ? st.states + o * d.T * d.d : nullptr;
-    stp.cost_total = st.cost_total + o;
     rfp = rf;
     rfp.N = n;
     rfp.Kep = stp.Kep;
@@ -472,30 +472,7 @@ int rollout_nl_two_launch(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs
     NLC_HIP(c, launch_nl_rollout(r, c->stream, variant));
   } else {
     const int Tc = (d.T + C - 1) / C;
-    if (!c->gru_stream) {
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // lo = lowest priority: the rollout's workgroups go first
-      NLC_HIP(c, hipStreamCreateWithPriority(&c->gru_stream, hipStreamNonBlocking, lo));
-    }
-    if (!c->ev_fork) NLC_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    while ((int)c->ev_gru.size() < C) {
-      hipEvent_t e2 = nullptr;
-      NLC_HIP(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-      c->ev_gru.push_back(e2);
-    }
-    NLC_HIP(c, hipEventRecord(c->ev_fork, c->stream));  // behind the perturb kernel and the staged inputs
-    NLC_HIP(c, hipStreamWaitEvent(c->gru_stream, c->ev_fork, 0));
-    for (int ch = 0; ch < C; ++ch) {
-      g.t0 = ch * Tc;
-      g.Tc = (g.t0 + Tc <= d.T) ? Tc : d.T - g.t0;
-      if (g.Tc <= 0) break;
-      g.N = KE * g.Tc;
-      {
-        ProfScope ps(c, "gru_encode_kernel", c->gru_stream, true);
-        NLC_HIP(c, launch_gru_encode(g, c->g, c->gru_stream, false));
-      }
-      NLC_HIP(c, hipEventRecord(c->ev_gru[ch], c->gru_stream));
-    }
+    if (int rc = gru_encode_chunks(c, g, KE, C, Tc, false, 0u)) return rc;
     for (int ch = 0; ch < C; ++ch) {
       r.t_begin = ch * Tc;
       r.t_end = (r.t_begin + Tc <= d.T) ? r.t_begin + Tc : d.T;
@@ -515,45 +492,29 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
   const nlc_mppi_buffers* buf = call.buf;
   const WsLayout& w = call.w;
   double* ws = call.ws;
-  double* state_dev = call.state_dev;
-  double* abuf_dev = call.abuf_dev;
   const int64_t KE = call.KE;
-  const int state_per_sample = call.state_per_sample;
   const bool replay = call.replay;
   const bool lin_direct = linear_on_rollout_kernels(c);
   double* pa = ws + w.pa;
   GruArgs g = c->gru;
   g.mode = 1;
   g.perturbed = buf->perturbed;
-  g.abuf = abuf_dev;
+  g.abuf = call.abuf_dev;
   g.u_scale = d.u_scale;
   g.T = d.T;
   g.B = d.B;
   g.Kep = d.K;
   g.nact = d.nu;
   g.out = pa;
+  const SampleCostArgs sc = sample_cost_args(c, call);
   RolloutArgs r{};
+  put_sample_cost(r, sc);
+  r.Kep = sc.Kep;
   r.net = c->net;
   r.net.b1 = c->b1fold;
-  r.K = KE;
-  r.Kep = d.K;
-  r.T = d.T;
-  r.nu = d.nu;
   r.B = d.B;
-  r.env = d.cost_external ? -1 : d.env;  // only the running cost reads it in the NL rollout
-  r.state_per_sample = state_per_sample;
-  r.state0 = state_dev;
   r.pa = pa;
-  r.perturbed = buf->perturbed;
-  r.noise = buf->noise;
-  r.U = c->U[c->ucur];
-  for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) r.sigma_inv[i] = d.noise_sigma_inv[i];
-  r.lambda_ = d.lambda_;
-  r.u_scale = d.u_scale;
-  r.noise_abs_cost = d.noise_abs_cost;
   r.tn = c->tn;
-  r.states = buf->states;
-  r.cost_total = buf->cost_total;
   r.xcarry = ws + w.xcarry;
   r.ccarry = ws + w.ccarry;
   if (lin_direct) {
@@ -563,7 +524,7 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
     r.net.Cp2 = c->cp_lin + ng;
     r.net.lin = 1;
   }
-  if (c->md.ilt.algo != NLC_ILT_FOURIER && !lin_direct) return rollout_nl_staged(c, call, g, r, pa);
+  if (c->md.ilt.algo != NLC_ILT_FOURIER && !lin_direct) return rollout_nl_staged(c, call, sc, g, r, pa);
   // rollout_variant (nlc_set_option): 0 auto, 1 wave-per-tile, 2 latency-split, 3 fused one-launch body
   int variant = c->opt_rollout_variant;
   const int h_ = c->md.h;

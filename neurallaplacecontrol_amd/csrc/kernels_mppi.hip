@@ -4,6 +4,7 @@
 //   oracle.*_dynamics_dt_delay        oracle.py:11-224        (rollout with model_name == "oracle")
 // All of these are HBM-light streaming / reduction kernels over the (K, T, nu) noise tensor.
 #include "nlc_device.h"
+#include "nlc_envcost.h"
 #include "nlc_kernels.h"
 #include "nlc_mppi_dev.h"
 
@@ -240,45 +241,6 @@ hipError_t launch_merge(const MergeArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------ oracle-dynamics rollout
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
-__device__ __forceinline__ double trig2angle_o(double c, double s) {
-  const double C = c * c + s * s;
-  c = c / C;
-  s = s / C;
-  return atan2(s / C, c / C);
-}
-
-// running costs: same formulas as kernels_nl.hip (kept local: this TU has no MFMA code)
-__device__ __forceinline__ double running_cost_o(int env, const double* x, const double* u, int nu) {
-  if (env < 0) return 0.0;  // cost_external: the caller evaluates its own running cost on the stored states
-  double uu = 0.0;
-  for (int j = 0; j < nu; ++j) uu += u[j] * u[j];
-  if (env == NLC_ENV_CARTPOLE) {
-    const double e0 = x[0] + x[3] - 0.0, e1 = x[2] - 1.0;
-    const double sr = -(e0 * e0 + e1 * e1);
-    const double vr = -(x[1] * x[1]) - x[4] * x[4];
-    return -((sr + 0.01 * vr) + (-0.01 * uu));
-  } else if (env == NLC_ENV_CARTPOLE_NOTRIG) {  // ctcartpole.py:297-300: explicit angle
-    const double cl = 1.0 * cos(x[2]), sl = 1.0 * sin(x[2]);
-    const double e0 = x[0] + sl - 0.0, e1 = cl - 1.0;
-    const double sr = -(e0 * e0 + e1 * e1);
-    const double vr = -(x[1] * x[1]) - x[3] * x[3];
-    return -((sr + 0.01 * vr) + (-0.01 * uu));
-  } else if (env == NLC_ENV_PENDULUM) {
-    const double om = 1.0 - x[0];
-    const double sr = -(om * om + x[1] * x[1]);
-    const double vr = -(x[2] * x[2]);
-    return -((sr + 0.01 * vr) + (-0.01 * uu));
-  } else {
-    const double th1 = trig2angle_o(x[0], x[1]), th2 = trig2angle_o(x[2], x[3]);
-    const double vr = -(x[4] * x[4]) - x[5] * x[5];
-    const double p1x = -cos(th1), p1y = sin(th1);
-    const double p2x = p1x - cos(th1 + th2), p2y = p1y + sin(th1 + th2);
-    const double ex = p2x - 1.0 - 1.0;
-    const double sr = -(ex * ex) - p2y * p2y;
-    return -((sr + 1e-1 * vr) + (-1e-4 * uu));
-  }
-}
-
 // One Euler step of the closed-form dynamics on the trig observation (oracle.py:11-86, 89-174, 177-224)
 __device__ __forceinline__ void oracle_step(int env, double* x, const double* uraw, double ts, int friction) {
   if (env == NLC_ENV_CARTPOLE || env == NLC_ENV_CARTPOLE_NOTRIG) {
@@ -336,7 +298,7 @@ __device__ __forceinline__ void oracle_step(int env, double* x, const double* ur
     x[2] = nthd;
   } else {
     const double u0 = clampd(uraw[0], -5.0, 5.0), u1 = clampd(uraw[1], -5.0, 5.0);
-    const double th1 = trig2angle_o(x[0], x[1]), th2 = trig2angle_o(x[2], x[3]);
+    const double th1 = trig2angle(x[0], x[1]), th2 = trig2angle(x[2], x[3]);
     const double d1v = x[4], d2v = x[5];
     const double m1 = 1.0, m2 = 1.0, l1 = 1.0, lc1 = 0.5, lc2 = 0.5, I1 = 1.0, I2 = 1.0, g = 9.8;
     const double c2 = cos(th2), s2 = sin(th2);
@@ -378,21 +340,12 @@ __global__ __launch_bounds__(256) void oracle_rollout_kernel(const OracleRollout
                             : a.u_scale * a.perturbed[(k * a.T + (i - (a.B - 1))) * a.nu + j];
       u[j] = a.u_scale * a.perturbed[(k * a.T + t) * a.nu + j];
     }
-    oracle_step(a.env, x, ud, a.ts, a.friction);
+    oracle_step(a.dyn_env, x, ud, a.ts, a.friction);
     if (a.states != nullptr)
       for (int ii = 0; ii < a.d; ++ii) a.states[(k * a.T + t) * a.d + ii] = x[ii];
-    double pc = 0.0;
-    for (int j = 0; j < a.nu; ++j) {
-      double acj = 0.0;
-      for (int ii = 0; ii < a.nu; ++ii) {
-        double e = a.noise[(k * a.T + t) * a.nu + ii];
-        if (a.noise_abs_cost) e = fabs(e);
-        acj += (a.lambda_ * e) * a.sigma_inv[ii * a.nu + j];
-      }
-      pc += U[t * a.nu + j] * acj;
-    }
-    cost += running_cost_o(a.cost_env, x, u, a.nu);
-    pcost += pc;
+    cost += running_cost(a.env, x, u, a.nu);
+    pcost += perturbation_cost_step(a.noise + (k * a.T + t) * a.nu, U + t * a.nu, a.sigma_inv, a.lambda_, a.nu,
+                                    a.noise_abs_cost);
   }
   a.cost_total[k] = cost + pcost;
 }
@@ -561,18 +514,9 @@ __global__ __launch_bounds__(256) void rnn_rollout_kernel(const RnnRolloutArgs a
     for (int j = 0; j < a.nu; ++j) u[j] = a.u_scale * a.perturbed[(k * a.T + t) * a.nu + j];
     if (a.states != nullptr)
       for (int i = 0; i < d; ++i) a.states[(k * a.T + t) * d + i] = x[i];
-    double pc = 0.0;
-    for (int j = 0; j < a.nu; ++j) {
-      double acj = 0.0;
-      for (int ii = 0; ii < a.nu; ++ii) {
-        double e2 = a.noise[(k * a.T + t) * a.nu + ii];
-        if (a.noise_abs_cost) e2 = fabs(e2);
-        acj += (a.lambda_ * e2) * a.sigma_inv[ii * a.nu + j];
-      }
-      pc += U[t * a.nu + j] * acj;
-    }
-    cost += running_cost_o(a.env, x, u, a.nu);
-    pcost += pc;
+    cost += running_cost(a.env, x, u, a.nu);
+    pcost += perturbation_cost_step(a.noise + (k * a.T + t) * a.nu, U + t * a.nu, a.sigma_inv, a.lambda_, a.nu,
+                                    a.noise_abs_cost);
   }
   a.cost_total[k] = cost + pcost;
 }

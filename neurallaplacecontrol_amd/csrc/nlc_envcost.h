@@ -1,5 +1,7 @@
-// Env running costs on the trig observation, shared by the MFMA rollout kernels (kernels_nl.hip, kernels_node.hip).
-// (kernels_mppi.hip keeps its own copy: that file is built with -ffp-contract=off to follow the torch-CPU op order.)
+// Env running costs on the trig observation and the perturbation cost of a horizon step, shared by every rollout body: the
+// Neural-Laplace rollouts and the de Hoog step tails (nlc_nl_kernels.h, nlc_rollout.h, kernels_nl.hip,
+// kernels_dehoog_chain.hip), the NODE rollout (kernels_node.hip) and the oracle / Delta-t RNN rollouts (kernels_mppi.hip).
+// The functions pin fp contract(off) themselves: the same bits whatever contraction their unit is built with.
 #pragma once
 #include "nlc_device.h"
 #include "../../include/nlc.h"
@@ -55,7 +57,9 @@ __device__ __forceinline__ double running_cost(int env, const double (&x)[NLC_MA
 }
 
 // perturbation cost of one horizon step: sum_j U[t,j] (lambda eps Sigma^-1)[j]   (planners/mppi_delay.py:335, 343).
-// eps / U: the step's nu entries.  Used by every tail of the de Hoog planner path (staged launches and the persistent chain).
+// eps / U: the step's nu entries.  Used by every tail of the de Hoog planner path (staged launches and the persistent chain)
+// and by the oracle and Delta-t RNN rollouts.  The MFMA rollout bodies (nl_rollout_kernel, rollout_split_tile,
+// node_rollout_kernel) keep their own loops: contraction is on there and the loops are scheduled by hand.
 __device__ __forceinline__ double perturbation_cost_step(const double* eps, const double* U, const double* sigma_inv,
                                                          double lambda_, int nu, int noise_abs_cost) {
 #pragma clang fp contract(off)

@@ -314,6 +314,7 @@ struct RolloutCall {
   bool replay;           // re-run of the last command on the two-launch body
 };
 int launch_shift_perturb(nlc_ctx* c, RolloutCall& call);
+SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call);  // once the shifted U is current
 // ---- abi_planner_nl.hip
 int rollout_nl(nlc_ctx* c, RolloutCall& call);
 

@@ -163,6 +163,45 @@ hipError_t launch_gru_encode(const GruArgs& a, int g, hipStream_t s, bool coop =
 hipError_t launch_gru_encode_i8(const GruArgs& a, hipStream_t s);
 unsigned long long gru_i8_launch_count();  // process-wide
 
+// ------------------------------------------------------------------ samples and cost of one planner rollout
+// What every rollout body of phase 1 reads and writes besides its dynamics.  The argument blocks of the step tail and of the
+// oracle, Delta-t RNN and NODE rollouts derive from it.  RolloutArgs and DehoogChainArgs spell the same fields out under the same
+// names, at the offsets their kernels were built and measured with: those kernels keep hundreds of scalars in spilled registers,
+// and moving a kernel argument reshuffles that allocation (their vector instruction counts moved by up to 350 when tried).
+// Episodes (nlc_mppi_desc.E): K counts ALL local samples (E * Kep); sample k belongs to episode e = k / Kep and
+// reads that episode's state0 row, action_buffer block and U block.  E == 1 <=> Kep == K.
+struct SampleCostArgs {
+  int64_t K;                // all local samples
+  int64_t Kep;              // samples per episode
+  int T;                    // horizon steps
+  int nu;                   // action dims
+  int env;                  // env of the running cost, -1 = none (cost_external: the caller adds its own)
+  int state_per_sample;     // state0 holds one row per sample instead of one per episode
+  const double* state0;     // (E, d) or (K, d)
+  const double* perturbed;  // (K, T, nu) bounded actions
+  const double* noise;      // (K, T, nu) bounded noise
+  const double* U;          // (E, T, nu) nominal sequence, already shifted
+  double sigma_inv[NLC_MAX_NU * NLC_MAX_NU];  // inverse noise covariance, row-major nu x nu
+  double lambda_;           // temperature
+  double u_scale;           // perturbed * u_scale = the action the dynamics and the running cost see
+  int noise_abs_cost;       // perturbation cost on |noise|
+  double* states;           // (K, T, d) or NULL
+  double* cost_total;       // (K) running + perturbation cost
+  // the same block for samples [o, o + n) of a state dimension d; a proper part lies inside a single planner's population
+  // (Kep == K) and counts as a population of its own
+  SampleCostArgs part(int64_t o, int64_t n, int d) const {
+    SampleCostArgs v = *this;
+    v.K = n;
+    if (n < K) v.Kep = n;
+    v.state0 = state0 + (state_per_sample ? o * d : 0);
+    v.perturbed = perturbed + o * T * nu;
+    v.noise = noise + o * T * nu;
+    v.states = states ? states + o * T * d : nullptr;
+    v.cost_total = cost_total + o;
+    return v;
+  }
+};
+
 // ------------------------------------------------------------------ Delta-t RNN baseline (train_utils.py:589-631)
 // One-layer forward GRU over the action window (hidden H) + the hidden part of linear_out: q = W_out[:, :H] h_last.
 struct RnnArgs {
@@ -202,22 +241,12 @@ struct RnnForwardArgs {  // DeltaTRNN.forward: out = q + Wx obs_n + wt ts_n + b
   double* out;        // (N, d)
 };
 hipError_t launch_rnn_forward_tail(const RnnForwardArgs& a, hipStream_t s);
-struct RnnRolloutArgs {  // x <- x + DeltaTRNN(x, window_t, ts_pred), running cost, perturbation cost
+struct RnnRolloutArgs : SampleCostArgs {  // x <- x + DeltaTRNN(x, window_t, ts_pred), running cost, perturbation cost
   RnnHead head;
-  int64_t K, Kep;
-  int T, nu, env;  // env: running cost, -1 = none (cost_external)
-  int state_per_sample;
-  const double* state0;
   const double* q;  // (T, K, d)
-  const double* perturbed;
-  const double* noise;
-  const double* U;
-  double sigma_inv[NLC_MAX_NU * NLC_MAX_NU];
-  double lambda_, u_scale, ts;
-  int noise_abs_cost;
-  double* states;
-  double* cost_total;
+  double ts;
 };
+static_assert(std::is_trivially_copyable<RnnRolloutArgs>::value, "passed to its kernel by value");
 hipError_t launch_rnn_rollout(const RnnRolloutArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ representation MLP + ILT + rollout
@@ -241,9 +270,7 @@ struct NlNetArgs {
   double alpha, log_tol, scale, time_div;
 };
 
-// Episodes (nlc_mppi_desc.E): K counts ALL local samples (E * Kep); sample k belongs to episode e = k / Kep and
-// reads that episode's state0 row, action_buffer block and U block.  E == 1 <=> Kep == K.
-struct RolloutArgs {
+struct RolloutArgs {  // (spells the fields of SampleCostArgs out: see there)
   NlNetArgs net;
   int64_t K, Kep;
   int T, nu, B, env;
@@ -280,23 +307,13 @@ struct ForwardArgs {
 hipError_t launch_nl_forward(const ForwardArgs& a, hipStream_t s);
 
 // x <- x + dx, running cost, state store: the per-step tail of the staged (de Hoog) planner path
-struct StepTailArgs {
-  int64_t K, Kep;
-  int T, t, nu, d, env, first, last;
-  int state_per_sample;
-  const double* state0;  // read when first
+struct StepTailArgs : SampleCostArgs {  // state0 is read when first, cost_total written when last
+  int t, d, first, last;
   double* x;             // (K, d) carried state
   const double* dx;      // (K, d)
   double* ccarry;        // (K, 2) running cost / perturbation cost
-  const double* perturbed;
-  const double* noise;
-  const double* U;
-  double sigma_inv[NLC_MAX_NU * NLC_MAX_NU];
-  double lambda_, u_scale;
-  int noise_abs_cost;
-  double* states;      // (K, T, d) or NULL
-  double* cost_total;  // (K), written when last
 };
+static_assert(std::is_trivially_copyable<StepTailArgs>::value, "passed to its kernel by value");
 hipError_t launch_step_tail(const StepTailArgs& a, hipStream_t s);
 
 // representation function only: F_k (re, im) of every Laplace term -> (N, d, S) arrays (de Hoog path)
@@ -332,7 +349,7 @@ hipError_t launch_nl_repfunc(const RepFuncArgs& a, hipStream_t s);
 
 // the whole step chain of the de Hoog planner as one persistent launch (kernels_dehoog_chain.hip): a workgroup owns 64
 // consecutive samples for all T horizon steps.  Single planner (E == 1), hidden_units 128, 17 or 33 terms.
-struct DehoogChainArgs {
+struct DehoogChainArgs {  // (spells the fields of SampleCostArgs out, Kep == K left away: see there)
   NlNetArgs net;            // net.b1: the bias with the constant sphere inputs folded in
   int64_t K;
   int T, nu, env;
@@ -358,22 +375,13 @@ hipError_t launch_nl_dehoog_chain(const DehoogChainArgs& a, int block_tiles, hip
 bool nl_dehoog_chain_available(int h, int nt3, int S);
 
 // ------------------------------------------------------------------ oracle-dynamics rollout (§8f-1)
-struct OracleRolloutArgs {
-  int64_t K, Kep;
-  int T, nu, B, d, env, delay, friction;
-  int cost_env;  // env of the running cost, -1 = none (the caller adds its own cost)
-  int state_per_sample;
-  const double* state0;
+struct OracleRolloutArgs : SampleCostArgs {
   const double* abuf;  // (E, B, nu)
-  const double* perturbed;
-  const double* noise;
-  const double* U;
-  double sigma_inv[NLC_MAX_NU * NLC_MAX_NU];
-  double lambda_, u_scale, ts;
-  int noise_abs_cost;
-  double* states;
-  double* cost_total;
+  double ts;
+  int B, d, delay, friction;
+  int dyn_env;         // env of the dynamics (the base's env selects the running cost)
 };
+static_assert(std::is_trivially_copyable<OracleRolloutArgs>::value, "passed to its kernel by value");
 hipError_t launch_oracle_rollout(const OracleRolloutArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ NODE baseline (train_utils.py:637-738)
@@ -389,21 +397,10 @@ struct NodeNetArgs {
   int nsub;            // Euler sub-steps of the fixed grid over [0, ts_pred / time_div] (step_size 0.05)
   double hsub[8];
 };
-struct NodeRolloutArgs {
+struct NodeRolloutArgs : SampleCostArgs {
   NodeNetArgs net;
-  int64_t K, Kep;
-  int T, nu, env;
-  int state_per_sample;
-  const double* state0;
-  const double* perturbed;
-  const double* noise;
-  const double* U;
-  double sigma_inv[NLC_MAX_NU * NLC_MAX_NU];
-  double lambda_, u_scale;
-  int noise_abs_cost;
-  double* states;
-  double* cost_total;
 };
+static_assert(std::is_trivially_copyable<NodeRolloutArgs>::value, "passed to its kernel by value");
 struct NodeForwardArgs {
   NodeNetArgs net;
   int64_t N;
