@@ -7,6 +7,7 @@ safe to import in ``multiprocessing`` *spawn* workers before they pick a device
 (cf. reference ``run_exp_multi.py:145,207``).
 """
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -307,6 +308,21 @@ class Ctx:
 
         s = torch.cuda.current_stream(self.device_index).cuda_stream
         self.check(self.lib.nlc_set_stream(self.h, C.c_void_p(s)))
+
+    @contextlib.contextmanager
+    def stream(self):
+        """Guard of every library call that launches: this ctx's device is torch's current one and the ctx enqueues on torch's
+        current stream there.  A block of several calls (or of calls and torch ops) takes it once and keeps its ``check`` lines."""
+        import torch
+
+        with torch.cuda.device(self.device_index):
+            self.use_torch_stream()
+            yield
+
+    def launch(self, fn, *args):
+        """One library call ``fn(self.h, *args)`` under ``stream()``, checked."""
+        with self.stream():
+            self.check(fn(self.h, *args))
 
     def set_option(self, name, value):
         """Planner tuning knob of ``include/nlc.h`` (``nlc_set_option``)."""

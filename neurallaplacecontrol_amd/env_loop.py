@@ -92,23 +92,16 @@ class BatchedEnv:
         return self.get_obs()
 
     def get_obs(self):
-        with torch.cuda.device(self.device):
-            self.ctx.use_torch_stream()
-            self.ctx.check(self.ctx.lib.nlc_env_obs(self.ctx.h, _lib.ENV_IDS[self.env_name], self.E,
-                                                    _lib.ptr(self.state), _lib.ptr(self._obs)))
+        self.ctx.launch(self.ctx.lib.nlc_env_obs, _lib.ENV_IDS[self.env_name], self.E, _lib.ptr(self.state), _lib.ptr(self._obs))
         return self._obs
 
     def step(self, actions):
         """One control step of every env: returns (obs (E, nx), reward (E)) device tensors (re-used buffers)."""
         act = torch.as_tensor(actions).detach().to(self.device, torch.float64).reshape(self.E, self.nu).contiguous()
-        with torch.cuda.device(self.device):
-            self.ctx.use_torch_stream()
-            self.ctx.check(
-                self.ctx.lib.nlc_env_step(
-                    self.ctx.h, _lib.ENV_IDS[self.env_name], int(self.friction), self.dt, self.delay, self.E, self.B,
-                    self.nu, _lib.ptr(self.state), _lib.ptr(self.action_buffer), _lib.ptr(act), _lib.ptr(self._obs),
-                    _lib.ptr(self._reward),
-                )
-            )
+        self.ctx.launch(
+            self.ctx.lib.nlc_env_step, _lib.ENV_IDS[self.env_name], int(self.friction), self.dt, self.delay, self.E, self.B,
+            self.nu, _lib.ptr(self.state), _lib.ptr(self.action_buffer), _lib.ptr(act), _lib.ptr(self._obs),
+            _lib.ptr(self._reward),
+        )
         self.time_step += 1
         return self._obs, self._reward

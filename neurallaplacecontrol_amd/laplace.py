@@ -43,6 +43,14 @@ def _prep(t, dev):
     return t.detach().to(device=dev, dtype=torch.float64).contiguous()
 
 
+def _ctx_on(dev, ctx=None):
+    """The ctx a stateless ILT call on ``dev`` launches through: the shared one, or the caller's -- which must be a ctx of
+    that device, since a ctx launches on its own device (``Ctx.launch``) and the tensors live on ``dev``."""
+    ctx = ctx or default_ctx(dev.index)
+    assert ctx.device_index == dev.index, f"ctx of cuda:{ctx.device_index} given for tensors on {dev}"
+    return ctx
+
+
 def rep_func_inputs(p, t, ilt_reconstruction_terms, ilt_algorithm="fourier", options=None, ctx=None):
     """(B, Tt, 2S+P) rows ``[theta_s | phi_s | p]`` and the (B, Tt) time grid, on the device."""
     dev = compute_device(p, t)
@@ -62,14 +70,8 @@ def rep_func_inputs(p, t, ilt_reconstruction_terms, ilt_algorithm="fourier", opt
         raise ValueError("t must be (time,) or (batch, time)")
     S = desc.terms
     out = torch.empty((B, Tt, 2 * S + P), dtype=torch.float64, device=dev)
-    ctx = ctx or default_ctx(dev.index)
-    with torch.cuda.device(dev):
-        ctx.use_torch_stream()
-        ctx.check(
-            ctx.lib.nlc_ilt_rep_inputs(
-                ctx.h, C.byref(desc), _lib.ptr(p_d), _lib.ptr(t_d), batched, B, Tt, P, _lib.ptr(out)
-            )
-        )
+    ctx = _ctx_on(dev, ctx)
+    ctx.launch(ctx.lib.nlc_ilt_rep_inputs, C.byref(desc), _lib.ptr(p_d), _lib.ptr(t_d), batched, B, Tt, P, _lib.ptr(out))
     t2 = t_d if batched else t_d.view(1, -1).expand(B, -1)
     return out, t2
 
@@ -77,13 +79,7 @@ def rep_func_inputs(p, t, ilt_reconstruction_terms, ilt_algorithm="fourier", opt
 def _ilt_forward(theta_d, phi_d, t_d, desc, ctx):
     N, d, _ = theta_d.shape
     x = torch.empty((N, d), dtype=torch.float64, device=theta_d.device)
-    with torch.cuda.device(theta_d.device):
-        ctx.use_torch_stream()
-        ctx.check(
-            ctx.lib.nlc_ilt_reconstruct(
-                ctx.h, C.byref(desc), _lib.ptr(theta_d), _lib.ptr(phi_d), _lib.ptr(t_d), N, d, _lib.ptr(x)
-            )
-        )
+    ctx.launch(ctx.lib.nlc_ilt_reconstruct, C.byref(desc), _lib.ptr(theta_d), _lib.ptr(phi_d), _lib.ptr(t_d), N, d, _lib.ptr(x))
     return x
 
 
@@ -106,14 +102,8 @@ class _IltFn(torch.autograd.Function):
         N, d, _ = theta_d.shape
         g = grad_x.detach().to(dtype=torch.float64).contiguous()
         g_theta, g_phi = torch.empty_like(theta_d), torch.empty_like(phi_d)
-        with torch.cuda.device(theta_d.device):
-            ctx.use_torch_stream()
-            ctx.check(
-                ctx.lib.nlc_ilt_reconstruct_backward(
-                    ctx.h, C.byref(desc), _lib.ptr(theta_d), _lib.ptr(phi_d), _lib.ptr(t_d), _lib.ptr(g), N, d,
-                    _lib.ptr(g_theta), _lib.ptr(g_phi),
-                )
-            )
+        ctx.launch(ctx.lib.nlc_ilt_reconstruct_backward, C.byref(desc), _lib.ptr(theta_d), _lib.ptr(phi_d), _lib.ptr(t_d),
+                   _lib.ptr(g), N, d, _lib.ptr(g_theta), _lib.ptr(g_phi))
         return g_theta, g_phi, None, None, None
 
 
@@ -133,7 +123,7 @@ def ilt_reconstruct(theta, phi, t, ilt_algorithm="fourier", options=None, ctx=No
     if t_d.numel() != N:
         raise ValueError("t must have one entry per row of theta/phi")
     desc = _lib.ilt_desc(ilt_algorithm, S, options)
-    ctx = ctx or default_ctx(dev.index)
+    ctx = _ctx_on(dev, ctx)  # (theta / phi are moved to `dev` below: _ilt_forward and the backward launch on it)
     if needs_grad:
         # HIP forward + HIP backward kernels behind one autograd Function
         return _IltFn.apply(

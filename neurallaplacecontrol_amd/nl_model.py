@@ -17,10 +17,12 @@ for hidden_units 64 / 128 / 256, state_dim <= 6 and GRU input dim <= 3.  Any oth
 8b "falls back to the torch path on UNSUPPORTED"): when ``nlc_set_model`` answers ``NLC_ERR_UNSUPPORTED`` the no-grad forward
 runs the same op sequence as the grad-mode one -- GRU and MLP as PyTorch-ROCm ops on the GPU, contour / sphere map / line
 integral in the HIP ILT kernels -- with a one-time warning, and a planner over such a model takes its callables path.
+
+The plumbing every mirror shares (normalisation buffers and constants, ``upload`` / ``hip_ctx``, the guards) is
+``_weights.HipModelMirror``; this file keeps the model's own decisions (``model_desc``) and its forwards.
 """
 
 import copy
-import ctypes as C
 import warnings
 
 import numpy as np
@@ -28,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._weights import WeightsKeyMixin
+from ._weights import HipModelMirror
 from .laplace import compute_device, laplace_reconstruct
 
 
@@ -80,27 +82,6 @@ class LaplaceRepresentationFunc(nn.Module):
         return theta, phi
 
 
-# state_dict order of the weight blob nlc_set_model expects (include/nlc.h)
-_BLOB_KEYS = [
-    "action_encoder.gru.weight_ih_l0",
-    "action_encoder.gru.weight_hh_l0",
-    "action_encoder.gru.bias_ih_l0",
-    "action_encoder.gru.bias_hh_l0",
-    "action_encoder.gru.weight_ih_l1",
-    "action_encoder.gru.weight_hh_l1",
-    "action_encoder.gru.bias_ih_l1",
-    "action_encoder.gru.bias_hh_l1",
-    "action_encoder.linear_out.weight",
-    "action_encoder.linear_out.bias",
-    "laplace_rep_func.linear_tanh_stack.0.weight",
-    "laplace_rep_func.linear_tanh_stack.0.bias",
-    "laplace_rep_func.linear_tanh_stack.2.weight",
-    "laplace_rep_func.linear_tanh_stack.2.bias",
-    "laplace_rep_func.linear_tanh_stack.4.weight",
-    "laplace_rep_func.linear_tanh_stack.4.bias",
-]
-
-
 def cme_reconstruction_terms():
     """Orders for which the CME (concentrated matrix-exponential) inversion method has published parameter sets -- the
     values of the reference's ``config.CME_reconstruction_terms()`` (config.py:278-418), generated from their run
@@ -128,12 +109,32 @@ class _DeviceCopy(nn.Module):
         super().__init__()
         self.action_encoder = copy.deepcopy(src.action_encoder).to(dev)
         self.laplace_rep_func = copy.deepcopy(src.laplace_rep_func).to(dev)
-        for name in ("state_mean", "state_std", "action_mean", "action_std", "dt"):
+        for name in src._NORM_BUFFERS:
             self.register_buffer(name, getattr(src, name).detach().to(dev))
 
 
-class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
-    _dyn_id = _lib.DYN_NL  # rollout the fused planner selects for NLDynamics(model, dt)
+class NeuralLaplaceModel(HipModelMirror, nn.Module):
+    _dyn_id = _lib.DYN_NL
+    # state_dict order of the weight blob nlc_set_model expects (include/nlc.h); also the order of model.parameters()
+    _BLOB_KEYS = [
+        "action_encoder.gru.weight_ih_l0",
+        "action_encoder.gru.weight_hh_l0",
+        "action_encoder.gru.bias_ih_l0",
+        "action_encoder.gru.bias_hh_l0",
+        "action_encoder.gru.weight_ih_l1",
+        "action_encoder.gru.weight_hh_l1",
+        "action_encoder.gru.bias_ih_l1",
+        "action_encoder.gru.bias_hh_l1",
+        "action_encoder.linear_out.weight",
+        "action_encoder.linear_out.bias",
+        "laplace_rep_func.linear_tanh_stack.0.weight",
+        "laplace_rep_func.linear_tanh_stack.0.bias",
+        "laplace_rep_func.linear_tanh_stack.2.weight",
+        "laplace_rep_func.linear_tanh_stack.2.bias",
+        "laplace_rep_func.linear_tanh_stack.4.weight",
+        "laplace_rep_func.linear_tanh_stack.4.bias",
+    ]
+    _blob_size_symbol, _set_model_symbol = "nlc_model_blob_size", "nlc_set_model"
 
     def __init__(
         self,
@@ -173,15 +174,7 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
         self.normalize_time = normalize_time
         self.s_recon_terms = s_recon_terms
         self.ilt_options = None  # optional dict(alpha=, tol=, scale=) override of the torchlaplace defaults
-        # same dtypes as the reference (w_nl.py:111-115): torch.tensor(dt) is FLOAT32, so after .double()
-        # the time normaliser is float32(0.05) widened; action_mean built from np.array([0]*nu) is int64
-        self.register_buffer("state_mean", torch.tensor(state_mean))
-        self.register_buffer("state_std", torch.tensor(state_std))
-        self.register_buffer("action_mean", torch.tensor(action_mean))
-        self.register_buffer("action_std", torch.tensor(action_std))
-        self.register_buffer("dt", torch.tensor(dt))
-        self._ctx = None
-        self._uploaded_key = None
+        self._register_norm_buffers(state_mean, state_std, action_mean, action_std, dt)
         self._rep_dev = None  # (key, device copy of laplace_rep_func) for the staged path
 
     @classmethod
@@ -196,18 +189,12 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
         """
         gru = ref.action_encoder.gru
         enc = bool(ref.encode_obs_time)
-        first = next(ref.parameters())
-        m = cls(
+        return cls(
             ref.output_dim, gru.input_size - int(enc), ref.latent_dim, hidden_units=2 * gru.hidden_size,
             s_recon_terms=ref.s_recon_terms, ilt_algorithm=ref.ilt_algorithm, encode_obs_time=enc,
             state_mean=[0.0] * ref.output_dim, state_std=[1.0] * ref.output_dim, action_mean=[0], action_std=[1.0],
             normalize=ref.normalize, normalize_time=ref.normalize_time,
-        ).to(device=first.device, dtype=first.dtype)
-        for name in ("state_mean", "state_std", "action_mean", "action_std", "dt"):
-            m.register_buffer(name, getattr(ref, name).detach().clone())
-        m.load_state_dict(ref.state_dict())
-        m.train(ref.training)
-        return m
+        )._take_over(ref)
 
     # ------------------------------------------------------------------ HIP plumbing
     def _weights_key_extra(self):
@@ -223,58 +210,9 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
         # fourier: fused forward and planner kernels; dehoog / fixed_tablot / stehfest: staged all-HIP forward (representation
         # kernel -> ILT kernel) and staged planner path
         desc.ilt = _lib.ilt_desc(self.ilt_algorithm, self.s_recon_terms, self.ilt_options)
-        f64 = lambda t: t.detach().to("cpu", torch.float64).reshape(-1)  # noqa: E731
-        if self.normalize:
-            sm, ss = f64(self.state_mean), f64(self.state_std)
-            am = f64(self.action_mean).expand(nin) if self.action_mean.numel() == 1 else f64(self.action_mean)
-            a_s = f64(self.action_std).expand(nin) if self.action_std.numel() == 1 else f64(self.action_std)
-            if am.numel() != nin or a_s.numel() != nin or sm.numel() != d or ss.numel() != d:
-                raise ValueError("normalisation buffers do not broadcast against the model's input dims")
-            desc.time_div = float(f64(self.dt)[0] * 8.0) if self.normalize_time else 1.0
-        else:
-            sm, ss = torch.zeros(d, dtype=torch.float64), torch.ones(d, dtype=torch.float64)
-            am, a_s = torch.zeros(nin, dtype=torch.float64), torch.full((nin,), 3.0, dtype=torch.float64)
-            desc.time_div = 1.0
-        for i in range(d):
-            desc.state_mean[i], desc.state_std[i] = float(sm[i]), float(ss[i])
-        for i in range(nin):
-            desc.action_mean[i], desc.action_std[i] = float(am[i]), float(a_s[i])
+        self._fill_norm_constants(desc, d, nin, self.normalize)
+        desc.time_div = self._time_div() if self.normalize else 1.0  # normalize_time counts inside the normalised branch only
         return desc
-
-    def upload(self, ctx):
-        """Pack the current weights into ``ctx`` (``nlc_set_model``); returns the key they were taken at.  Planners
-        keep their own ctx (planner state lives there) and call this when the key changes."""
-        if any(p.dtype != torch.float64 for p in self.parameters()):
-            raise NotImplementedError(
-                "the HIP path computes in float64 only: call model.double() first (reference: mppi_with_model.py:101)"
-            )
-        key = self._weights_key()
-        sd = self.state_dict()
-        blob = torch.cat([sd[k].detach().to("cpu", torch.float64).reshape(-1) for k in _BLOB_KEYS]).contiguous()
-        desc = self.model_desc()
-        n = ctx.lib.nlc_model_blob_size(C.byref(desc))
-        if n != blob.numel():
-            raise ValueError(f"weight blob has {blob.numel()} doubles, library expects {n}")
-        ctx.check(ctx.lib.nlc_set_model(ctx.h, C.byref(desc), _lib.ptr(blob), blob.numel()))
-        return key
-
-    def hip_ctx(self, device=None):
-        """The model's own ``nlc_ctx`` (forward / encode_actions) with its current weights uploaded."""
-        dev = compute_device(next(self.parameters())) if device is None else torch.device(device)
-        if self._ctx is None or self._ctx.device_index != dev.index:
-            self._ctx = _lib.Ctx(dev.index)
-            self._uploaded_key = None
-        if self._weights_key() != self._uploaded_key:
-            self._uploaded_key = self.upload(self._ctx)
-        return self._ctx
-
-    @staticmethod
-    def _no_grad_only():
-        if torch.is_grad_enabled():
-            raise NotImplementedError(
-                "neurallaplacecontrol_amd.NeuralLaplaceModel is inference-only on the HIP path: "
-                "wrap the call in torch.no_grad() (as the reference harness does, mppi_with_model.py:319)"
-            )
 
     def encode_actions(self, in_batch_action):
         """HIP GRU encoder on raw (un-normalised) action windows (N, B, nin) -> (N, 2)  [stage a7]."""
@@ -286,9 +224,7 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
             win = win.unsqueeze(1)
         N, B, nin = win.shape
         out = torch.empty((N, 2), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            ctx.use_torch_stream()
-            ctx.check(ctx.lib.nlc_gru_encode(ctx.h, _lib.ptr(win), N, B, _lib.ptr(out)))
+        ctx.launch(ctx.lib.nlc_gru_encode, _lib.ptr(win), N, B, _lib.ptr(out))
         return out
 
     def rep_func_hip(self, i):
@@ -302,9 +238,7 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
         N = rows.shape[0]
         theta = torch.empty((N, d, S), dtype=torch.float64, device=dev)
         phi = torch.empty((N, d, S), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            ctx.use_torch_stream()
-            ctx.check(ctx.lib.nlc_rep_func(ctx.h, _lib.ptr(rows), N, _lib.ptr(theta), _lib.ptr(phi)))
+        ctx.launch(ctx.lib.nlc_rep_func, _lib.ptr(rows), N, _lib.ptr(theta), _lib.ptr(phi))
         return theta, phi
 
     def _forward_train(self, in_batch_obs, in_batch_action, ts_pred, mod=None):
@@ -314,8 +248,7 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
         ``mod``: the module whose sub-modules / buffers to use (``_forward_generic``'s device copy); default ``self``."""
         mod = self if mod is None else mod
         dev = compute_device(in_batch_obs, in_batch_action, next(mod.parameters()))
-        if next(mod.parameters()).device != dev:
-            raise RuntimeError("training forward: move the model to the GPU first (model.to('cuda'))")
+        self._train_device(dev, mod)
         obs = in_batch_obs.to(dev, torch.float64)
         act = in_batch_action.to(dev, torch.float64)
         ts = torch.as_tensor(ts_pred).to(dev, torch.float64)
@@ -415,35 +348,20 @@ class NeuralLaplaceModel(WeightsKeyMixin, nn.Module):
             # one query time for every row (the harness closure's ts_pred = dt): constant sphere inputs, folded bias
             out = torch.empty((N, d), dtype=torch.float64, device=dev)
             ws = torch.empty(ctx.lib.nlc_model_workspace_bytes(ctx.h, N) // 8, dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                ctx.use_torch_stream()
-                ctx.check(ctx.lib.nlc_model_forward_const_t(ctx.h, _lib.ptr(obs), _lib.ptr(win), t_const, N, win.shape[1],
-                                                            _lib.ptr(out), _lib.ptr(ws)))
+            ctx.launch(ctx.lib.nlc_model_forward_const_t, _lib.ptr(obs), _lib.ptr(win), t_const, N, win.shape[1], _lib.ptr(out),
+                       _lib.ptr(ws))
             return torch.squeeze(out.view(N, 1, d)).to(out_device)
         ts = torch.as_tensor(ts_pred).detach().to(dev, torch.float64)
         fused = ts.numel() == N  # one query time per row: all-HIP forward for every implemented algorithm
         if fused:
             out = torch.empty((N, d), dtype=torch.float64, device=dev)
             ws = torch.empty(ctx.lib.nlc_model_workspace_bytes(ctx.h, N) // 8, dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                ctx.use_torch_stream()
-                ctx.check(
-                    ctx.lib.nlc_model_forward(
-                        ctx.h,
-                        _lib.ptr(obs),
-                        _lib.ptr(win),
-                        _lib.ptr(ts.reshape(-1).contiguous()),
-                        N,
-                        win.shape[1],
-                        _lib.ptr(out),
-                        _lib.ptr(ws),
-                    )
-                )
+            ctx.launch(ctx.lib.nlc_model_forward, _lib.ptr(obs), _lib.ptr(win), _lib.ptr(ts.reshape(-1).contiguous()), N,
+                       win.shape[1], _lib.ptr(out), _lib.ptr(ws))
             return torch.squeeze(out.view(N, 1, d)).to(out_device)
         # several time points per row: HIP GRU -> PyTorch-ROCm MLP (laplace_rep_func) -> HIP ILT
         desc = self.model_desc()
-        sm = torch.tensor(list(desc.state_mean)[:d], dtype=torch.float64, device=dev)
-        ss = torch.tensor(list(desc.state_std)[:d], dtype=torch.float64, device=dev)
+        sm, ss = self._norm_tensors(desc, torch.float64, dev)[:2]
         p = torch.cat(((obs - sm) / ss, self.encode_actions(win)), dim=1)
         rep = self.laplace_rep_func
         if next(rep.parameters()).device != dev:

@@ -63,8 +63,7 @@ class BatchedMPPIDelay(MPPIDelay):
                 t = t.to(self.cd)
             return t.contiguous()
 
-        with torch.cuda.device(self.cd):
-            self.ctx.use_torch_stream()  # (re)configuration uploads are ordered on the command's stream
+        with self.ctx.stream():  # (re)configuration uploads are ordered on the command's stream
             self._ensure_configured(ab.shape[1])
         if self.encode_obs_time and ab.shape[2] == nu + 1:
             ab = ab[:, :, :nu]  # drop the time-stamp column (mppi_delay.py:262-264)
@@ -73,8 +72,7 @@ class BatchedMPPIDelay(MPPIDelay):
         st, ab = stage(st), stage(ab)
         lib, ctx = self.ctx.lib, self.ctx
         rng = 1 if self.noise_rng == "philox" else 0
-        with torch.cuda.device(self.cd):
-            ctx.use_torch_stream()
+        with ctx.stream():
             if not rng:
                 self._noise.copy_(self.noise_dist.sample((E, K, T)).reshape(E, K, T, nu))
             ctx.check(

@@ -181,8 +181,7 @@ class MPPIDelay:
         planner_options = opts_in
 
         if compute_device is None:
-            model_holder = dynamics if isinstance(dynamics, NLDynamics) else (
-                self._candidate[0] if self._candidate is not None and isinstance(self._candidate[0], NLDynamics) else None)
+            model_holder = self._model_holder()
             if self.d.type == "cuda":
                 compute_device = self.d
             elif model_holder is not None and next(model_holder.model.parameters()).is_cuda:
@@ -233,8 +232,7 @@ class MPPIDelay:
                                          self.cd)
             ok = 1
             try:
-                with torch.cuda.device(self.cd):
-                    self.ctx.use_torch_stream()
+                with self.ctx.stream():
                     self.ctx.comm_init(self.rank, self.G, uid)
                     self.ctx.comm_self_test()  # one all-gather of the rank numbers, checked on the host
             except _lib.NlcError as err:
@@ -304,6 +302,14 @@ class MPPIDelay:
             self.store_rollouts = True
         if isinstance(dynamics, OracleDynamics) and not self.fused_dynamics:
             raise NotImplementedError("OracleDynamics needs the default rollout options (no step-dependent dynamics)")
+
+    def _model_holder(self):
+        """The ``NLDynamics`` whose model this planner follows -- its dynamics, or the recognised candidate behind literal
+        closures -- else None."""
+        for dyn in (self.F, self._candidate[0] if self._candidate is not None else None):
+            if isinstance(dyn, NLDynamics):
+                return dyn
+        return None
 
     def _verify_candidate(self, state, action_buffer):
         """First command(): run the literal closures and the recognised fused objects on one short probe command (this
@@ -531,8 +537,7 @@ class MPPIDelay:
         rng = 1 if self.noise_rng == "philox" else 0
         if self._candidate is not None:
             self._verify_candidate(state, action_buffer)
-        with torch.cuda.device(self.cd):
-            ctx.use_torch_stream()  # before any (re)configuration: its uploads are ordered on this stream too
+        with ctx.stream():  # bound before any (re)configuration: its uploads are ordered on this stream too
             self._ensure_configured(ab.shape[0])
             if not rng:
                 # K x T x nu draw on `device`, same generator consumption as the reference (:319)
@@ -728,8 +733,7 @@ class MPPIDelay:
         once -- ``p.data.copy_()`` / ``p.data.mul_()`` on the model a recognised harness closure closes over (its
         ``(data_ptr, _version)`` key does not move; the content check runs every ``_recognise.TWIN_CONTENT_CHECK_EVERY``
         commands), or on one of this package's own models (``mark_weights_dirty``).  The next command() uploads them."""
-        holder = self.F if isinstance(self.F, NLDynamics) else (
-            self._candidate[0] if self._candidate is not None and isinstance(self._candidate[0], NLDynamics) else None)
+        holder = self._model_holder()
         if holder is None:
             return
         _recognise.refresh_twin(holder.model, force=True)

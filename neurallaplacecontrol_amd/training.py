@@ -21,7 +21,6 @@ import torch
 
 from . import _lib
 from .laplace import compute_device
-from .nl_model import _BLOB_KEYS
 
 
 def _i64_ptr(t, offset=0):
@@ -50,10 +49,7 @@ class NLTrainer:
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
         params = list(model.parameters())
-        if any(p.dtype != torch.float64 for p in params):
-            raise NotImplementedError(
-                "the HIP path computes in float64 only: call model.double() first (reference: mppi_with_model.py:101)"
-            )
+        model._require_float64()
         if not params[0].is_cuda:
             raise RuntimeError("training: move the model to the GPU first (model.to('cuda'))")
         self.model = model
@@ -61,7 +57,7 @@ class NLTrainer:
         self.weight_decay, self.clip_grad_norm = float(weight_decay), float(clip_grad_norm)
         self._dev = compute_device(params[0])
         named = dict(model.named_parameters())
-        self._params = [named[k] for k in _BLOB_KEYS]  # blob order (= model.parameters() order)
+        self._params = [named[k] for k in model._BLOB_KEYS]  # blob order (= model.parameters() order)
         self._sizes = [p.numel() for p in self._params]
         self._fallback = None
         why = None
@@ -183,8 +179,7 @@ class NLTrainer:
         grad = torch.empty_like(self._flat)
         loss = torch.empty((), dtype=torch.float64, device=self._dev)
         ctx = self._ctx
-        with torch.cuda.device(self._dev):
-            ctx.use_torch_stream()
+        with ctx.stream():
             rc = ctx.lib.nlc_train_loss_grad(
                 ctx.h, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), _i64_ptr(self._idx(N)),
                 N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)))
@@ -208,8 +203,7 @@ class NLTrainer:
         self._gather()
         loss = torch.empty((), dtype=torch.float64, device=self._dev)
         ctx = self._ctx
-        with torch.cuda.device(self._dev):
-            ctx.use_torch_stream()
+        with ctx.stream():
             try:
                 self._launch_step(_i64_ptr(self._idx(N)), obs, win, ts, tgt, N, _f64_ptr(loss), self._workspace(N))
             except _lib.NlcError as err:
@@ -302,8 +296,7 @@ class NLTrainer:
         self._gather()
         desc = self._desc()
         ctx = self._ctx
-        with torch.cuda.device(self._dev):
-            ctx.use_torch_stream()
+        with ctx.stream():
             for i in range(iters):
                 try:
                     self._launch_step(_i64_ptr(perm, i * bs), obs, win, tsd, tgt, bs, _f64_ptr(losses, i), ws, desc)
