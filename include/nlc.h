@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 10
+#define NLC_ABI_VERSION 11
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -324,6 +324,22 @@ int nlc_set_rnn_model(nlc_ctx* ctx, const nlc_rnn_desc* desc, const double* weig
  * predicted state difference.  ws_dev: N*d doubles of scratch. */
 int nlc_rnn_forward(nlc_ctx* ctx, const double* obs_dev, const double* window_dev, const double* ts_dev, int64_t N,
                     int B, double* out_dev, void* ws_dev);
+/* ---- training of these two models: the same iteration (train_utils.py:388-408 over DeltaTRNN.forward :618-631 /
+ *      RNN.forward :577-586), signatures and contract as nlc_train_workspace_bytes / nlc_train_loss_grad / nlc_train_step
+ *      above (nlc_train_desc is reused).  The shape comes from nlc_set_rnn_model on the same ctx (without it: NLC_ERR_STATE);
+ *      B outside 1..16: NLC_ERR_UNSUPPORTED; N < 1: NLC_ERR_BAD_SHAPE; all checked on the host before any launch.
+ *   params_dev, grad_dev, m_dev, v_dev: nlc_rnn_blob_size doubles in nlc_set_rnn_model's blob order.
+ *   ts_dev is read only by a time_input model (may be NULL otherwise). */
+int64_t nlc_rnn_train_workspace_bytes(nlc_ctx* ctx, int64_t N);
+/* train_utils.py:391-402 */
+int nlc_rnn_train_loss_grad(nlc_ctx* ctx, const double* params_dev, const double* obs_dev, const double* window_dev,
+                            const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
+                            double* grad_dev, double* loss_dev, void* ws_dev);
+/* train_utils.py:391-404 */
+int nlc_rnn_train_step(nlc_ctx* ctx, const nlc_train_desc* desc, double* params_dev, double* m_dev, double* v_dev,
+                       int64_t step, const double* obs_dev, const double* window_dev, const double* ts_dev,
+                       const double* target_dev, const int64_t* idx_dev, int64_t N, int B, double* loss_dev,
+                       double* gradnorm_dev, void* ws_dev);
 
 /* ---- baseline model: NODE (train_utils.py:664-724; ODE function xOdeFuncInXAndU :637-661; factory :101-125;
  * node_hidden_units 270, node_augment_dim 1, node_method "euler": config.py:40-42).

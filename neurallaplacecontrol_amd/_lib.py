@@ -64,6 +64,9 @@ SYMBOLS = [
     "nlc_rnn_blob_size",
     "nlc_set_rnn_model",
     "nlc_rnn_forward",
+    "nlc_rnn_train_workspace_bytes",
+    "nlc_rnn_train_loss_grad",
+    "nlc_rnn_train_step",
     "nlc_node_blob_size",
     "nlc_set_node_model",
     "nlc_node_forward",
@@ -227,6 +230,10 @@ def load_library():
         lib.nlc_train_workspace_bytes.restype = i64
         lib.nlc_train_loss_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
         lib.nlc_train_step.argtypes = [vp, P(TrainDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]
+        lib.nlc_rnn_train_workspace_bytes.argtypes = lib.nlc_train_workspace_bytes.argtypes
+        lib.nlc_rnn_train_workspace_bytes.restype = i64
+        lib.nlc_rnn_train_loss_grad.argtypes = lib.nlc_train_loss_grad.argtypes
+        lib.nlc_rnn_train_step.argtypes = lib.nlc_train_step.argtypes
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]
         lib.nlc_rnn_blob_size.restype = i64
         lib.nlc_set_rnn_model.argtypes = [vp, P(RnnDesc), vp, i64]

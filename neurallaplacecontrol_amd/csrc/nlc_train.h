@@ -138,6 +138,60 @@ inline void blob_offsets(int d, int nin, int g, int h, int S, int64_t off[kTenso
   for (int i = 0; i < kTensors; ++i) off[i + 1] = off[i] + n[i];
 }
 
+// first reduce / Adam chunk of each tensor (cstart[kTensors] = number of chunks): chunks are cut per tensor, so none straddles
+// two, and an empty tensor owns none
+inline int chunk_starts(const int64_t off[kTensors + 1], int cstart[kTensors + 1]) {
+  cstart[0] = 0;
+  for (int t = 0; t < kTensors; ++t) cstart[t + 1] = cstart[t] + (int)((off[t + 1] - off[t] + kChunk - 1) / kChunk);
+  return cstart[kTensors];
+}
+
+// ---- DeltaTRNN / RNN (kernels_train_rnn.hip): one GRU layer of width H and linear_out over [h_B | obs_n | ts_n]
+constexpr int kRnnTensors = 6;  // W_ih, W_hh, b_ih, b_hh, linear_out.weight, linear_out.bias (nlc_set_rnn_model's order)
+
+// blob offsets of the six tensors; the table is padded to kTensors with empty tensors (off[6..] = P), which own no reduce /
+// Adam chunk and add 0 to the gradient norm, so train_reduce_kernel / train_adam_kernel serve both models unchanged
+inline void rnn_blob_offsets(int d, int nin, int H, int time_input, int64_t off[kTensors + 1]) {
+  const int64_t H3 = 3 * (int64_t)H, F = H + d + (time_input ? 1 : 0);
+  const int64_t n[kRnnTensors] = {H3 * nin, H3 * H, H3, H3, d * F, d};
+  off[0] = 0;
+  for (int i = 0; i < kTensors; ++i) off[i + 1] = off[i] + (i < kRnnTensors ? n[i] : 0);
+}
+
+// one workgroup's slab: the tapes and gate gradients of a tile, [s][r][...] (the current step's state lives in LDS)
+struct RnnActLayout {
+  int64_t X, Hs, G, DI, DH, total;
+};
+NLC_HD RnnActLayout rnn_act_layout(int nin, int H, int B) {
+  const int64_t R = kRows;
+  RnnActLayout L;
+  int64_t o = 0;
+  L.X = act_take(&o, B * R * nin);       // normalised window, forward order: [s][r][nin]
+  L.Hs = act_take(&o, (B + 1) * R * H);  // hidden states h_0 = 0 .. h_B: [s][r][H]
+  L.G = act_take(&o, B * R * 4 * H);     // tape [r | z | n | W_hn h + b_hn]: [s][r][4H]
+  L.DI = act_take(&o, B * R * 3 * H);    // input-side gate gradients [s][r][3H]
+  L.DH = act_take(&o, B * R * 3 * H);    // hidden-side gate gradients [s][r][3H]
+  L.total = o;
+  return L;
+}
+
+struct RnnTrainArgs {
+  int d, nin, B, time_input;
+  double time_div;
+  double sm[8], ss[8], am[3], as[3];
+  const double* params;
+  const double *obs, *window, *ts, *target;  // ts is not read unless time_input
+  const int64_t* idx;
+  int64_t N;
+  int ntiles;
+  int64_t P, A;
+  RnnActLayout L;
+  double* partial;
+  double* tile_loss;
+  double* act;
+  int64_t off[kRnnTensors + 1];
+};
+
 struct TrainArgs {
   int d, nin, g, h, S, B;
   double time_div, alpha, log_tol;
@@ -188,6 +242,7 @@ namespace train {
 hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, hipStream_t s);
 hipError_t launch_train_reduce(const ReduceArgs& a, hipStream_t s);
 hipError_t launch_train_adam(const AdamArgs& a, hipStream_t s);
+hipError_t launch_rnn_train_fwd_bwd(const RnnTrainArgs& a, int H, int nblk, hipStream_t s);  // H: 64, 128 or 160
 }  // namespace train
 }  // namespace nlc
 #endif

@@ -1,9 +1,10 @@
-"""Fused training step of ``NeuralLaplaceModel``: the reference's training iteration (``train_utils.py:388-408``) --
+"""Fused training step of ``NeuralLaplaceModel`` (``NLTrainer``) and of the ``DeltaTRNN`` / ``RNN`` baselines
+(``RNNTrainer``): the reference's training iteration (``train_utils.py:388-408``) --
 
     pred_sd = model(bs0, ba0, bts); loss = nn.MSELoss()(pred_sd.squeeze(), bsd.squeeze())
     loss.backward(); torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()   # Adam
 
--- as three HIP launches (``nlc_train_step``, ``include/nlc.h``): forward + backward of a 16-row tile per workgroup,
+-- as three HIP launches (``nlc_train_step`` / ``nlc_rnn_train_step``, ``include/nlc.h``): forward + backward of a 16-row tile per workgroup,
 a fixed-order reduction of the tile gradients, clip + Adam.  No host synchronisation inside, so ``run()`` walks a whole
 permutation with the weights, Adam moments and per-iteration losses on the device.
 
@@ -12,6 +13,10 @@ the reference's op sequence -- the model's grad-mode forward + ``clip_grad_norm_
 construction on, with one warning.  A fused trainer sends a single call the library refuses (a window longer than 16, a
 model setting changed to one the kernels do not take) through the same op sequence, on the trainer's own Adam state, also
 with one warning.
+
+What does not depend on the model -- the flat parameter buffer and its views, the workspace cache, the re-upload of a changed
+model descriptor, the grad-mode fallbacks on the shared Adam state, ``run()`` and the optimiser state -- is ``_FusedTrainer``;
+a trainer class names its three library entries and says which models it takes.
 """
 
 import ctypes as C
@@ -29,12 +34,14 @@ def _i64_ptr(t, offset=0):
 
 
 def _f64_ptr(t, offset=0):
+    if t is None:
+        return C.c_void_p(0)
     assert t.dtype == torch.float64 and t.is_contiguous()
     return C.c_void_p(t.data_ptr() + 8 * offset)
 
 
-class NLTrainer:
-    """``tr = NLTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)``
+class _FusedTrainer:
+    """``tr = Trainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)``
 
     * ``tr.loss_and_grad(bs0, ba0, bts, bsd)`` -- loss (0-dim device tensor) and ``p.grad`` of every parameter;
     * ``tr.step(bs0, ba0, bts, bsd)`` -- one reference iteration (loss, backward, clip, Adam); the loss BEFORE the update;
@@ -46,6 +53,13 @@ class NLTrainer:
     hold the new weights, written in place (their ``_version`` moves, so ``model.forward`` and planners re-upload).  The
     model's buffers and settings (normalisation constants, ``normalize`` / ``normalize_time``, ``ilt_options``) are
     re-read before every call: a change after construction (``model.load_state_dict(checkpoint)``, say) takes effect."""
+
+    _entries = None  # the library's (workspace_bytes, loss_grad, step) of the model family
+    _reads_ts = True  # False: the model ignores ts_pred, and the kernels get no ts pointer (a property where it varies)
+
+    def _unsupported(self, model):
+        """Why no fused kernels exist for ``model`` whatever its shape (None: ask the library)."""
+        return None
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
         params = list(model.parameters())
@@ -60,15 +74,14 @@ class NLTrainer:
         self._params = [named[k] for k in model._BLOB_KEYS]  # blob order (= model.parameters() order)
         self._sizes = [p.numel() for p in self._params]
         self._fallback = None
-        why = None
-        if model.ilt_algorithm != "fourier":
-            why = f"ilt_algorithm {model.ilt_algorithm!r} has no fused training kernels (fourier only)"
-        else:
+        self._name = type(self).__name__
+        why = self._unsupported(model)
+        if why is None:
             self._ctx = _lib.Ctx(self._dev.index)
             self._model_key = None
             why = self._sync_model()
         if why is not None:
-            warnings.warn(f"NLTrainer: {why} -- this model trains through its grad-mode forward + clip_grad_norm_ + "
+            warnings.warn(f"{self._name}: {why} -- this model trains through its grad-mode forward + clip_grad_norm_ + "
                           "torch.optim.Adam instead of the fused HIP step", stacklevel=2)
             self._fallback = torch.optim.Adam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
             return
@@ -115,7 +128,7 @@ class NLTrainer:
         """A call the fused kernels do not take: warn once per trainer."""
         if not self._warned:
             self._warned = True
-            warnings.warn(f"NLTrainer: {why} -- calls the library refuses run the grad-mode forward + clip_grad_norm_ + "
+            warnings.warn(f"{self._name}: {why} -- calls the library refuses run the grad-mode forward + clip_grad_norm_ + "
                           "torch.optim.Adam on the trainer's optimiser state instead of the fused HIP step", stacklevel=3)
 
     def _views(self, flat):
@@ -136,9 +149,9 @@ class NLTrainer:
     def _workspace(self, N):
         ws = self._ws.get(N)
         if ws is None:
-            n = self._ctx.lib.nlc_train_workspace_bytes(self._ctx.h, N)
+            n = getattr(self._ctx.lib, self._entries[0])(self._ctx.h, N)
             if n < 0:
-                raise _lib.NlcError(n, "nlc_train_workspace_bytes")
+                raise _lib.NlcError(n, self._entries[0])
             ws = self._ws[N] = torch.empty((n + 7) // 8, dtype=torch.float64, device=self._dev)
         return ws
 
@@ -147,11 +160,12 @@ class NLTrainer:
 
     def _data(self, s0, a0, ts, target):
         f64 = lambda t: torch.as_tensor(t).detach().to(self._dev, torch.float64).contiguous()  # noqa: E731
-        obs, win, ts, tgt = f64(s0), f64(a0), f64(ts).reshape(-1), f64(target)
+        obs, win, tgt = f64(s0), f64(a0), f64(target)
+        ts = f64(ts).reshape(-1) if self._reads_ts else None
         if win.dim() == 2:
             win = win.unsqueeze(1)
         N = obs.shape[0]
-        if ts.numel() != N or tgt.numel() != obs.numel() or win.shape[0] != N:
+        if (ts is not None and ts.numel() != N) or tgt.numel() != obs.numel() or win.shape[0] != N:
             raise ValueError("training batch: s0 (N, d), a0 (N, B, nin), ts (N,) or (N, 1), target (N, d)")
         return obs, win, ts, tgt.reshape(obs.shape)
 
@@ -180,7 +194,7 @@ class NLTrainer:
         loss = torch.empty((), dtype=torch.float64, device=self._dev)
         ctx = self._ctx
         with ctx.stream():
-            rc = ctx.lib.nlc_train_loss_grad(
+            rc = getattr(ctx.lib, self._entries[1])(
                 ctx.h, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), _i64_ptr(self._idx(N)),
                 N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)))
         why = self._refused(rc)
@@ -214,10 +228,10 @@ class NLTrainer:
         return loss
 
     def _launch_step(self, idx_ptr, obs, win, ts, tgt, N, loss_ptr, ws, desc=None):
-        """One ``nlc_train_step``; the Adam step count moves only once the library has accepted the call (it checks
+        """One ``nlc_train_step`` / ``nlc_rnn_train_step``; the Adam step count moves only once the library has accepted the call (it checks
         everything on the host before the first launch)."""
         ctx = self._ctx
-        ctx.check(ctx.lib.nlc_train_step(
+        ctx.check(getattr(ctx.lib, self._entries[2])(
             ctx.h, C.byref(desc if desc is not None else self._desc()), _f64_ptr(self._flat), _f64_ptr(self._m),
             _f64_ptr(self._v), self._step + 1, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), idx_ptr, N,
             win.shape[1], loss_ptr, None, _f64_ptr(ws)))
@@ -336,7 +350,7 @@ class NLTrainer:
         for grp in sd.get("param_groups", []):
             for flag in ("amsgrad", "maximize"):
                 if grp.get(flag):
-                    raise ValueError(f"NLTrainer.load_state_dict: an Adam state with {flag}=True is not supported "
+                    raise ValueError(f"{self._name}.load_state_dict: an Adam state with {flag}=True is not supported "
                                      "(the trainer runs plain Adam)")
         if not self.fused:
             self._fallback.load_state_dict(sd)
@@ -350,10 +364,34 @@ class NLTrainer:
         self.weight_decay = float(grp["weight_decay"])
         steps = {int(opt.state[p]["step"]) for p in self._params if p in opt.state}
         if len(steps) > 1:
-            raise ValueError("NLTrainer keeps one Adam step count for all parameters")
+            raise ValueError(f"{self._name} keeps one Adam step count for all parameters")
         self._step = steps.pop() if steps else 0
         with torch.no_grad():
             for p, m, v in zip(self._params, self._views(self._m), self._views(self._v)):
                 st = opt.state.get(p)
                 m.copy_(st["exp_avg"] if st else torch.zeros_like(m))
                 v.copy_(st["exp_avg_sq"] if st else torch.zeros_like(v))
+
+
+class NLTrainer(_FusedTrainer):
+    """``tr = NLTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)`` for a
+    ``NeuralLaplaceModel``; the fused step takes Fourier models (``nlc_train_step``)."""
+
+    _entries = ("nlc_train_workspace_bytes", "nlc_train_loss_grad", "nlc_train_step")
+
+    def _unsupported(self, model):
+        if model.ilt_algorithm != "fourier":
+            return f"ilt_algorithm {model.ilt_algorithm!r} has no fused training kernels (fourier only)"
+        return None
+
+
+class RNNTrainer(_FusedTrainer):
+    """``tr = RNNTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)`` for a
+    ``DeltaTRNN`` or an ``RNN`` (``nlc_rnn_train_step``): the methods and semantics of ``NLTrainer``.  An ``RNN`` ignores
+    ``ts`` as its forward does; the reference's loop still passes it, so every method accepts it."""
+
+    _entries = ("nlc_rnn_train_workspace_bytes", "nlc_rnn_train_loss_grad", "nlc_rnn_train_step")
+
+    @property
+    def _reads_ts(self):
+        return bool(self.model._time_input)

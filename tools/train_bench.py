@@ -1,4 +1,5 @@
-"""Training-step throughput of NeuralLaplaceModel on cartpole (d = 5, h = 128, S = 17, B = 4), one JSON line:
+"""Training-step throughput on cartpole of NeuralLaplaceModel (d = 5, h = 128, S = 17, B = 4; --model nl, the default) or of
+the DeltaTRNN baseline (d = 5, H = 160, B = 4; --model delta_t_rnn, RNNTrainer), one JSON line:
 
   (a) the reference's iteration (train_utils.py:391-408) through the existing grad-mode model(...): forward, MSELoss,
       backward, clip_grad_norm_(0.1), torch.optim.Adam.step(), loss.item() every iteration;
@@ -7,13 +8,17 @@
 
 Every variant runs a warm-up first and every timing ends with torch.cuda.synchronize().  Iterations / s per variant and the
 ratios (b) / (a), (c) / (a) at each batch size.  `--only run --run-iters 200` is the shape for a rocprofv3 kernel trace.
+Each (batch size, variant) measurement is a child process of its own under --step-timeout seconds; the first one that fails or
+runs out of time ends the tool (nothing more is started on the GPU).  `--kernel-ms` adds the mean time of each kernel of the
+fused step from the library's event profiling (200 step()s).
 
-    python tools/train_bench.py [--batches 16 256] [--ref-iters 200] [--step-iters 1000] [--run-iters 10000] [--out FILE]
+    python tools/train_bench.py [--model nl|delta_t_rnn] [--batches 16 256] [--ref-iters 200] [--step-iters 1000] [--run-iters 10000] [--out FILE]
 """
 
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -27,10 +32,26 @@ import neurallaplacecontrol_amd as nlc  # noqa: E402
 from oracle import nl_model as onl  # noqa: E402
 
 ENV, D, NU, H, S, B = "oderl-cartpole", 5, 1, 128, 17, 4
+RNN_H = 160  # rnn_hidden_units, config.py:43
+MODEL = "nl"
+WORKLOADS = {"nl": "NeuralLaplaceModel training step, cartpole d=5 h=128 S=17 B=4, float64",
+             "delta_t_rnn": "DeltaTRNN training step, cartpole d=5 H=160 B=4, float64"}
+
+
+def make_trainer(model):
+    return nlc.RNNTrainer(model) if MODEL == "delta_t_rnn" else nlc.NLTrainer(model)
 
 
 def make_model():
     st = onl.ENV_STATS[ENV]
+    if MODEL == "delta_t_rnn":
+        from oracle import rnn_model as orn
+
+        sd = orn.make_synthetic_state_dict(0, D, NU, RNN_H, st["state_std"], [st["act_high"] / 2])
+        m = nlc.DeltaTRNN(D, NU, hidden_units=RNN_H, state_mean=np.zeros(D), state_std=np.ones(D), action_mean=np.array([0]),
+                          action_std=np.array([1.0]), normalize=True, normalize_time=True).double()
+        m.load_state_dict(sd)
+        return m.to("cuda")
     sd = onl.make_synthetic_state_dict(0, D, NU, H, S, st["state_std"], [st["act_high"] / 2], tame=True)
     m = nlc.NeuralLaplaceModel(D, NU, D, hidden_units=H, s_recon_terms=S, ilt_algorithm="fourier", state_mean=np.zeros(D),
                                state_std=np.ones(D), action_mean=np.array([0]), action_std=np.array([1.0]), normalize=True,
@@ -79,7 +100,7 @@ def time_ref(bs, iters, warm):
 
 
 def time_step(bs, iters, warm):
-    tr = nlc.NLTrainer(make_model())
+    tr = make_trainer(make_model())
     s0, a0, sn, ts = dataset(bs * (iters + warm))
     perm = torch.randperm(s0.shape[0]).cuda()
 
@@ -99,7 +120,7 @@ def time_step(bs, iters, warm):
 
 
 def time_run(bs, iters, warm):
-    tr = nlc.NLTrainer(make_model())
+    tr = make_trainer(make_model())
     s0, a0, sn, ts = dataset(bs * iters)
     perm = torch.randperm(s0.shape[0]).cuda()
     tr.run(s0, a0, sn, ts, perm[: bs * warm], batch_size=bs)
@@ -112,9 +133,28 @@ def time_run(bs, iters, warm):
     return iters / dt
 
 
+def kernel_ms(bs, iters=200, warm=20):
+    """Mean milliseconds per launch of each kernel of step() (the library's event pairs around every launch)."""
+    tr = make_trainer(make_model())
+    s0, a0, sn, ts = dataset(bs)
+    for _ in range(warm):
+        tr.step(s0, a0, ts, sn - s0)
+    torch.cuda.synchronize()
+    tr._ctx.profile(True)
+    tr._ctx.profile_reset()
+    for _ in range(iters):
+        tr.step(s0, a0, ts, sn - s0)
+    torch.cuda.synchronize()
+    out = {k: v["total_ms"] / max(v["launches"], 1) for k, v in tr._ctx.profile_read().items()}
+    tr._ctx.profile(False)
+    return out
+
+
 def flops_per_iter(bs):
     """Multiply-adds x 2 of the dense products (forward + the two backward products per weight matrix); transcendentals
     and element-wise work not counted."""
+    if MODEL == "delta_t_rnn":
+        return int(2 * bs * 3 * (B * 3 * RNN_H * (NU + RNN_H) + D * (RNN_H + D + 1)))
     g, K0, O = H // 2, 2 * S + D + 2, 2 * D * S
     gru = B * (3 * g * (NU + g) + 3 * g * (g + g))  # both layers, per row per window
     mlp = K0 * H + H * H + H * O
@@ -132,19 +172,39 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--only", choices=["ref", "step", "run"], default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--model", choices=sorted(WORKLOADS), default="nl")
+    ap.add_argument("--kernel-ms", action="store_true")
+    ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds each child measurement may take")
+    ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    global MODEL
+    MODEL = args.model
     torch.manual_seed(0)
-    res = {"workload": "NeuralLaplaceModel training step, cartpole d=5 h=128 S=17 B=4, float64", "device": torch.cuda.get_device_name(0),
-           "batches": {}}
+    if args.child:
+        bs, variant = int(args.child[0]), args.child[1]
+        fn = {"ref": lambda: time_ref(bs, args.ref_iters, args.warmup), "step": lambda: time_step(bs, args.step_iters, args.warmup),
+              "run": lambda: time_run(bs, args.run_iters, args.warmup), "kernel_ms": lambda: kernel_ms(bs)}[variant]
+        print("RESULT " + json.dumps(fn()))
+        return
+
+    def measure(bs, variant):
+        cmd = [sys.executable, os.path.abspath(__file__), "--model", MODEL, "--ref-iters", str(args.ref_iters), "--step-iters",
+               str(args.step_iters), "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--child", str(bs), variant]
+        out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
+        return json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+    res = {"workload": WORKLOADS[MODEL], "device": torch.cuda.get_device_name(0), "batches": {}}
     for bs in args.batches:
         r = {"flops_per_iter": flops_per_iter(bs)}
         if args.only in (None, "ref"):
-            r["ref_it_s"] = time_ref(bs, args.ref_iters, args.warmup)
+            r["ref_it_s"] = measure(bs, "ref")
         if args.only in (None, "step"):
-            r["step_it_s"] = time_step(bs, args.step_iters, args.warmup)
+            r["step_it_s"] = measure(bs, "step")
         if args.only in (None, "run"):
-            r["run_it_s"] = time_run(bs, args.run_iters, args.warmup)
+            r["run_it_s"] = measure(bs, "run")
             r["run_iters"] = args.run_iters
+        if args.kernel_ms:
+            r["kernel_ms"] = measure(bs, "kernel_ms")
         if "ref_it_s" in r:
             for k in ("step", "run"):
                 if f"{k}_it_s" in r:
