@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 11
+#define NLC_ABI_VERSION 12
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -298,6 +298,29 @@ int nlc_train_loss_grad(nlc_ctx* ctx, const double* params_dev, const double* ob
 int nlc_train_step(nlc_ctx* ctx, const nlc_train_desc* desc, double* params_dev, double* m_dev, double* v_dev, int64_t step,
                    const double* obs_dev, const double* window_dev, const double* ts_dev, const double* target_dev,
                    const int64_t* idx_dev, int64_t N, int B, double* loss_dev, double* gradnorm_dev, void* ws_dev);
+/* ---- grouped training: M models of one descriptor in the same three launches, the member on the grid's y axis.  The
+ *      reference trains one model per (env, delay, model_name) (run_exp_multi.py:105-110), times seeds; for a fixed env and
+ *      family these share the architecture and the normalisation constants and differ in weights and data, and one model's
+ *      iteration (train_utils.py:388-408) occupies one compute unit.  Contract of the three entries above, plus:
+ *   params_dev, m_dev, v_dev, grad_dev: [M][P] (P = nlc_model_blob_size); idx_dev: [M][N]; loss_dev, gradnorm_dev: [M]
+ *   (gradnorm_dev may be NULL); one nlc_train_desc and one Adam step count for the whole group.
+ *   data_row_stride: 0 = every member reads the same obs / window / ts / target; R > 0 = they are stacked, member m reads
+ *   rows [m R, (m + 1) R) (its idx entries index within them).
+ *   ws_dev: nlc_train_group_workspace_bytes(ctx, M, N) = M x the single-model layout, each region 256-byte aligned.
+ *   The refusals of the single entries apply; M < 1 or data_row_stride < 0: NLC_ERR_BAD_SHAPE; M > 65535 (the grid's y
+ *   limit): NLC_ERR_UNSUPPORTED; all on the host before any launch.  No atomics and no cross-member reads: a member's
+ *   results are bit-identical whatever M and its neighbours are, and the single entries are the M = 1, stride 0 case. */
+/* train_utils.py:388-408, run_exp_multi.py:105-110 */
+int64_t nlc_train_group_workspace_bytes(nlc_ctx* ctx, int M, int64_t N);
+/* train_utils.py:391-402 per member, run_exp_multi.py:105-110 */
+int nlc_train_group_loss_grad(nlc_ctx* ctx, int M, int64_t data_row_stride, const double* params_dev, const double* obs_dev,
+                              const double* window_dev, const double* ts_dev, const double* target_dev,
+                              const int64_t* idx_dev, int64_t N, int B, double* grad_dev, double* loss_dev, void* ws_dev);
+/* train_utils.py:391-404 per member, run_exp_multi.py:105-110 */
+int nlc_train_group_step(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_t data_row_stride, double* params_dev,
+                         double* m_dev, double* v_dev, int64_t step, const double* obs_dev, const double* window_dev,
+                         const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
+                         double* loss_dev, double* gradnorm_dev, void* ws_dev);
 
 /* ---- baseline models: DeltaTRNN (train_utils.py:589-631; factory :56-74) and RNN (:550-586; factory :77-98);
  *      rnn_hidden_units config.py:43 ------
@@ -340,6 +363,19 @@ int nlc_rnn_train_step(nlc_ctx* ctx, const nlc_train_desc* desc, double* params_
                        int64_t step, const double* obs_dev, const double* window_dev, const double* ts_dev,
                        const double* target_dev, const int64_t* idx_dev, int64_t N, int B, double* loss_dev,
                        double* gradnorm_dev, void* ws_dev);
+/* grouped training of these two models: layout and contract of nlc_train_group_* above (P = nlc_rnn_blob_size) */
+/* train_utils.py:388-408, run_exp_multi.py:105-110 */
+int64_t nlc_rnn_train_group_workspace_bytes(nlc_ctx* ctx, int M, int64_t N);
+/* train_utils.py:391-402 per member, run_exp_multi.py:105-110 */
+int nlc_rnn_train_group_loss_grad(nlc_ctx* ctx, int M, int64_t data_row_stride, const double* params_dev,
+                                  const double* obs_dev, const double* window_dev, const double* ts_dev,
+                                  const double* target_dev, const int64_t* idx_dev, int64_t N, int B, double* grad_dev,
+                                  double* loss_dev, void* ws_dev);
+/* train_utils.py:391-404 per member, run_exp_multi.py:105-110 */
+int nlc_rnn_train_group_step(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_t data_row_stride, double* params_dev,
+                             double* m_dev, double* v_dev, int64_t step, const double* obs_dev, const double* window_dev,
+                             const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
+                             double* loss_dev, double* gradnorm_dev, void* ws_dev);
 
 /* ---- baseline model: NODE (train_utils.py:664-724; ODE function xOdeFuncInXAndU :637-661; factory :101-125;
  * node_hidden_units 270, node_augment_dim 1, node_method "euler": config.py:40-42).

@@ -19,7 +19,7 @@ from .laplace import ilt_reconstruct, laplace_reconstruct, rep_func_inputs  # no
 from .nl_model import LaplaceRepresentationFunc, NeuralLaplaceModel, ReverseGRUEncoder  # noqa: F401
 from .node_model import NODE, xOdeFuncInXAndU  # noqa: F401
 from .rnn_model import RNN, DeltaTRNN  # noqa: F401
-from .training import NLTrainer, RNNTrainer  # noqa: F401
+from .training import NLTrainer, NLTrainerGroup, RNNTrainer, RNNTrainerGroup  # noqa: F401
 from .planners.mppi_batch import BatchedMPPIDelay  # noqa: F401
 from .planners.mppi_delay import MPPIDelay  # noqa: F401
 
@@ -29,7 +29,9 @@ __all__ = [
     "BatchedEnv",
     "NeuralLaplaceModel",
     "NLTrainer",
+    "NLTrainerGroup",
     "RNNTrainer",
+    "RNNTrainerGroup",
     "DeltaTRNN",
     "RNN",
     "NODE",

@@ -61,12 +61,18 @@ SYMBOLS = [
     "nlc_train_workspace_bytes",
     "nlc_train_loss_grad",
     "nlc_train_step",
+    "nlc_train_group_workspace_bytes",
+    "nlc_train_group_loss_grad",
+    "nlc_train_group_step",
     "nlc_rnn_blob_size",
     "nlc_set_rnn_model",
     "nlc_rnn_forward",
     "nlc_rnn_train_workspace_bytes",
     "nlc_rnn_train_loss_grad",
     "nlc_rnn_train_step",
+    "nlc_rnn_train_group_workspace_bytes",
+    "nlc_rnn_train_group_loss_grad",
+    "nlc_rnn_train_group_step",
     "nlc_node_blob_size",
     "nlc_set_node_model",
     "nlc_node_forward",
@@ -234,6 +240,15 @@ def load_library():
         lib.nlc_rnn_train_workspace_bytes.restype = i64
         lib.nlc_rnn_train_loss_grad.argtypes = lib.nlc_train_loss_grad.argtypes
         lib.nlc_rnn_train_step.argtypes = lib.nlc_train_step.argtypes
+        # grouped: M and data_row_stride after the ctx (after the desc for a step)
+        lib.nlc_train_group_workspace_bytes.argtypes = [vp, i32, i64]
+        lib.nlc_train_group_workspace_bytes.restype = i64
+        lib.nlc_train_group_loss_grad.argtypes = [vp, i32, i64] + lib.nlc_train_loss_grad.argtypes[1:]
+        lib.nlc_train_group_step.argtypes = [vp, P(TrainDesc), i32, i64] + lib.nlc_train_step.argtypes[2:]
+        lib.nlc_rnn_train_group_workspace_bytes.argtypes = lib.nlc_train_group_workspace_bytes.argtypes
+        lib.nlc_rnn_train_group_workspace_bytes.restype = i64
+        lib.nlc_rnn_train_group_loss_grad.argtypes = lib.nlc_train_group_loss_grad.argtypes
+        lib.nlc_rnn_train_group_step.argtypes = lib.nlc_train_group_step.argtypes
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]
         lib.nlc_rnn_blob_size.restype = i64
         lib.nlc_set_rnn_model.argtypes = [vp, P(RnnDesc), vp, i64]

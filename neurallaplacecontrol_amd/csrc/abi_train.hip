@@ -1,7 +1,8 @@
 // Host side of libnlc_hip.so, training unit: the fused training step of a NeuralLaplaceModel (kernels_train.hip) and of the
 // DeltaTRNN / RNN baselines (kernels_train_rnn.hip), one iteration of the reference's loop, train_utils.py:388-408 (forward,
 // MSELoss, backward, clip_grad_norm_, Adam.step).  The two models differ in the forward + backward launch and the blob's
-// tensors; the workspace, the reduction and the Adam launch are written once.
+// tensors; the workspace, the reduction and the Adam launch are written once.  Every entry is the group path: M same-shaped
+// models (run_exp_multi.py:105-110) in the same three launches, the member on the grid's y axis; a single model is M = 1.
 #include <cmath>
 
 #include "nlc_host.h"
@@ -18,6 +19,9 @@ struct Plan {
   int64_t P, A, ntiles;
   int64_t off[kTensors + 1];
   int cstart[kTensors + 1];
+  TrainWsLayout ws;      // one member's workspace region
+  GroupStrides gs;  // for a group whose gradient lives in the workspace (a step); loss_grad overrides gs.grad
+  int M;
 };
 
 // workgroups, partial size and the reduce / Adam chunking of a call with N rows, once p.off, p.A and p.d are set
@@ -26,6 +30,13 @@ void plan_rows(Plan& p, int64_t N) {
   p.ntiles = (N + kRows - 1) / kRows;
   p.nblk = (int)(p.ntiles < kMaxBlocks ? p.ntiles : kMaxBlocks);
   p.chunks = chunk_starts(p.off, p.cstart);
+  p.ws = train_ws_layout(p.nblk, p.P, p.A, p.chunks);
+}
+
+// the members' strides of a call: M members, N index entries each, data_rows dataset rows apart (0: one shared dataset)
+void plan_group(Plan& p, int M, int64_t N, int64_t data_rows) {
+  p.M = M;
+  p.gs = GroupStrides{p.P, p.ws.total, p.ws.total, N, data_rows};
 }
 
 // (slabs sized for the longest window)
@@ -51,26 +62,20 @@ Plan rnn_plan_of(const nlc_ctx* c, int64_t N) {
   return p;
 }
 
-// scratch: [partials nblk * P | tile losses | slabs nblk * A | summed gradient P | chunk sums of squares]
+// member 0's arrays in the workspace (nlc_train.h TrainWsLayout; member m's are gs.ws doubles further on)
 struct WsPtrs {
   double *partial, *tile_loss, *act, *grad, *sq;
 };
-int64_t ws_doubles(const Plan& p, WsPtrs* w, void* base) {
-  auto al = [](int64_t n) { return (n + 31) / 32 * 32; };
-  int64_t o = 0;
+WsPtrs ws_ptrs(const Plan& p, void* base) {
   double* b = (double*)base;
-  const int64_t o_part = o;
-  o += al((int64_t)p.nblk * p.P);
-  const int64_t o_loss = o;
-  o += al(p.nblk);
-  const int64_t o_act = o;
-  o += al((int64_t)p.nblk * p.A);
-  const int64_t o_grad = o;
-  o += al(p.P);
-  const int64_t o_sq = o;
-  o += al(p.chunks);
-  if (w && b) *w = WsPtrs{b + o_part, b + o_loss, b + o_act, b + o_grad, b + o_sq};
-  return o;
+  return WsPtrs{b + p.ws.partial, b + p.ws.tile_loss, b + p.ws.act, b + p.ws.grad, b + p.ws.sq};
+}
+
+int check_group(nlc_ctx* c, int M, int64_t data_rows) {
+  if (M < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: a group needs M >= 1 members");
+  if (M > kMaxGroup) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: at most 65535 members in a group");
+  if (data_rows < 0) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: data_row_stride must be >= 0");
+  return NLC_OK;
 }
 
 int check_train(nlc_ctx* c, int64_t N, int B) {
@@ -82,8 +87,15 @@ int check_train(nlc_ctx* c, int64_t N, int B) {
   return NLC_OK;
 }
 
-// partials -> grad (blob order) and loss; sq gets the chunk sums of squares
-int reduce(nlc_ctx* c, int64_t N, double* grad, double* loss, const Plan& p, const WsPtrs& w) {
+int check_rnn_train(nlc_ctx* c, int64_t N, int B) {
+  if (!c->has_rnn) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
+  if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
+  if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
+  return NLC_OK;
+}
+
+// partials -> grad (blob order, members grad_stride apart) and loss [M]; sq gets the chunk sums of squares
+int reduce(nlc_ctx* c, int64_t N, double* grad, int64_t grad_stride, double* loss, const Plan& p, const WsPtrs& w) {
   ReduceArgs r{};
   r.partial = w.partial;
   r.tile_loss = w.tile_loss;
@@ -98,12 +110,14 @@ int reduce(nlc_ctx* c, int64_t N, double* grad, double* loss, const Plan& p, con
     r.off[i] = p.off[i];
     r.cstart[i] = p.cstart[i];
   }
+  r.gs = p.gs;
+  r.gs.grad = grad_stride;
   ProfScope ps(c, "train_reduce_kernel");
-  NLC_HIP(c, launch_train_reduce(r, c->stream));
+  NLC_HIP(c, launch_train_reduce(r, p.M, c->stream));
   return NLC_OK;
 }
 
-// clip_grad_norm_ + Adam.step() on the summed gradient in the workspace
+// clip_grad_norm_ + Adam.step() on the summed gradients in the workspace, per member
 int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, double* v, int64_t step, double* gradnorm,
          const Plan& p, const WsPtrs& w) {
   // the host-side scalars of torch.optim.Adam's foreach step (python floats there: beta ** step, (lr / bc1) * -1, bc2 ** 0.5)
@@ -128,23 +142,43 @@ int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, doub
     a.off[i] = p.off[i];
     a.cstart[i] = p.cstart[i];
   }
+  a.gs = p.gs;
   ProfScope ps(c, "train_adam_kernel");
-  NLC_HIP(c, launch_train_adam(a, c->stream));
+  NLC_HIP(c, launch_train_adam(a, p.M, c->stream));
   return NLC_OK;
 }
 
-// forward + backward + reduce: grad (blob order) and loss; sq gets the chunk sums of squares
-int loss_grad(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
-              const double* target, const int64_t* idx, int64_t N, int B, double* grad, double* loss, const Plan& p,
-              const WsPtrs& w) {
+// what the two families' forward + backward launches share: the batch, the plan's sizes and the workspace
+template <class Args>
+void fill_common(Args& a, int B, const double* params, const double* obs, const double* window, const double* ts,
+                 const double* target, const int64_t* idx, int64_t N, const Plan& p, const WsPtrs& w) {
+  a.B = B;
+  a.params = params;
+  a.obs = obs;
+  a.window = window;
+  a.ts = ts;
+  a.target = target;
+  a.idx = idx;
+  a.N = N;
+  a.ntiles = (int)p.ntiles;
+  a.P = p.P;
+  a.A = p.A;
+  a.partial = w.partial;
+  a.tile_loss = w.tile_loss;
+  a.act = w.act;
+  a.gs = p.gs;
+}
+
+int nl_fwd_bwd(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
+               const double* target, const int64_t* idx, int64_t N, int B, const Plan& p, const WsPtrs& w) {
   const nlc_model_desc& md = c->md;
   TrainArgs a{};
+  fill_common(a, B, params, obs, window, ts, target, idx, N, p, w);
   a.d = md.d;
   a.nin = md.nin;
   a.g = p.g;
   a.h = md.h;
   a.S = p.S;
-  a.B = B;
   a.time_div = md.time_div;
   a.alpha = md.ilt.alpha;
   a.log_tol = std::log(md.ilt.tol);
@@ -156,43 +190,20 @@ int loss_grad(nlc_ctx* c, const double* params, const double* obs, const double*
     a.am[i] = md.action_mean[i];
     a.as[i] = md.action_std[i];
   }
-  a.params = params;
-  a.obs = obs;
-  a.window = window;
-  a.ts = ts;
-  a.target = target;
-  a.idx = idx;
-  a.N = N;
-  a.ntiles = (int)p.ntiles;
-  a.P = p.P;
-  a.A = p.A;
   a.L = act_layout(md.d, md.nin, p.g, md.h, p.S, B);
-  a.partial = w.partial;
-  a.tile_loss = w.tile_loss;
-  a.act = w.act;
   for (int i = 0; i <= kTensors; ++i) a.off[i] = p.off[i];
-  {
-    ProfScope ps(c, "train_fwd_bwd_kernel");
-    NLC_HIP(c, launch_train_fwd_bwd(a, p.nblk, c->stream));
-  }
-  return reduce(c, N, grad, loss, p, w);
-}
-
-int check_rnn_train(nlc_ctx* c, int64_t N, int B) {
-  if (!c->has_rnn) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
-  if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
-  if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
+  ProfScope ps(c, "train_fwd_bwd_kernel");
+  NLC_HIP(c, launch_train_fwd_bwd(a, p.nblk, p.M, c->stream));
   return NLC_OK;
 }
 
-int rnn_loss_grad(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
-                  const double* target, const int64_t* idx, int64_t N, int B, double* grad, double* loss, const Plan& p,
-                  const WsPtrs& w) {
+int rnn_fwd_bwd(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
+                const double* target, const int64_t* idx, int64_t N, int B, const Plan& p, const WsPtrs& w) {
   const nlc_rnn_desc& rd = c->rd;
   RnnTrainArgs a{};
+  fill_common(a, B, params, obs, window, ts, target, idx, N, p, w);
   a.d = rd.d;
   a.nin = rd.nin;
-  a.B = B;
   a.time_input = rd.time_input;
   a.time_div = rd.time_div;
   for (int i = 0; i < rd.d; ++i) {
@@ -203,117 +214,136 @@ int rnn_loss_grad(nlc_ctx* c, const double* params, const double* obs, const dou
     a.am[i] = rd.action_mean[i];
     a.as[i] = rd.action_std[i];
   }
-  a.params = params;
-  a.obs = obs;
-  a.window = window;
-  a.ts = ts;
-  a.target = target;
-  a.idx = idx;
-  a.N = N;
-  a.ntiles = (int)p.ntiles;
-  a.P = p.P;
-  a.A = p.A;
   a.L = rnn_act_layout(rd.nin, rd.hidden, B);
-  a.partial = w.partial;
-  a.tile_loss = w.tile_loss;
-  a.act = w.act;
   for (int i = 0; i <= kRnnTensors; ++i) a.off[i] = p.off[i];
-  {
-    ProfScope ps(c, "rnn_train_fwd_bwd_kernel");
-    NLC_HIP(c, launch_rnn_train_fwd_bwd(a, rd.hidden, p.nblk, c->stream));
-  }
-  return reduce(c, N, grad, loss, p, w);
+  ProfScope ps(c, "rnn_train_fwd_bwd_kernel");
+  NLC_HIP(c, launch_rnn_train_fwd_bwd(a, rd.hidden, p.nblk, p.M, c->stream));
+  return NLC_OK;
+}
+
+// ---- the three entries of a family (rnn: DeltaTRNN / RNN, else NeuralLaplaceModel), written once for both and for any M
+int64_t group_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
+  if (!c || !(rnn ? c->has_rnn : c->has_model) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+  const Plan p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
+  return (int64_t)M * p.ws.total * (int64_t)sizeof(double);
+}
+
+// checks (all on the host, before any launch, in the single entries' order: model state and shape, the group, the step count,
+// NULL pointers), then forward + backward + reduce of every member.  A step (step != NULL: its Adam step count; more_null: one
+// of its own pointers is NULL) keeps the summed gradients in the workspace; else they go to the caller's grad [M][P]
+int group_loss_grad(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
+                    const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
+                    double* grad, double* loss, void* ws, Plan* plan, const int64_t* step = nullptr, bool more_null = false) {
+  if (int rc = rnn ? check_rnn_train(c, N, B) : check_train(c, N, B)) return rc;
+  if (int rc = check_group(c, M, data_rows)) return rc;
+  if (step && *step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
+  const bool need_ts = rnn ? c->rd.time_input != 0 : true;
+  if (!params || !obs || !window || (!ts && need_ts) || !target || !idx || (!step && !grad) || !loss || !ws || more_null)
+    return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
+  NLC_HIP(c, hipSetDevice(c->device));
+  Plan& p = *plan;
+  p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
+  plan_group(p, M, N, data_rows);
+  const WsPtrs w = ws_ptrs(p, ws);
+  if (int rc = (rnn ? rnn_fwd_bwd : nl_fwd_bwd)(c, params, obs, window, ts, target, idx, N, B, p, w)) return rc;
+  return reduce(c, N, step ? w.grad : grad, step ? p.gs.ws : p.P, loss, p, w);
+}
+
+int group_loss_grad_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
+                          const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N,
+                          int B, double* grad, double* loss, void* ws) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  NLC_GUARD_BEGIN
+  Plan p;
+  return group_loss_grad(c, rnn, M, data_rows, params, obs, window, ts, target, idx, N, B, grad, loss, ws, &p);
+  NLC_GUARD_END(c)
+}
+
+int group_step_entry(nlc_ctx* c, bool rnn, const nlc_train_desc* desc, int M, int64_t data_rows, double* params, double* m,
+                     double* v, int64_t step, const double* obs, const double* window, const double* ts,
+                     const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  NLC_GUARD_BEGIN
+  if (!desc) return fail(c, NLC_ERR_BAD_ARG, "NULL train desc");
+  Plan p;
+  if (int rc = group_loss_grad(c, rnn, M, data_rows, params, obs, window, ts, target, idx, N, B, nullptr, loss, ws, &p, &step,
+                               !m || !v))
+    return rc;
+  return adam(c, desc, params, m, v, step, gradnorm, p, ws_ptrs(p, ws));
+  NLC_GUARD_END(c)
 }
 
 }  // namespace
 
-// train_utils.py:388-408
-extern "C" int64_t nlc_train_workspace_bytes(nlc_ctx* c, int64_t N) {
-  if (!c || !c->has_model || N < 1) return -1;
-  const Plan p = plan_of(c, N);
-  return ws_doubles(p, nullptr, nullptr) * (int64_t)sizeof(double);
+// ---- NeuralLaplaceModel.  A group (run_exp_multi.py:105-110: one model per (env, delay, model_name), times seeds) is M
+// models of one descriptor: params / m / v / grad [M][P], idx [M][N], loss / gradnorm [M], data_row_stride 0 (one dataset)
+// or the rows per member of a stacked one; the single entries are its M = 1 case
+// train_utils.py:388-408, run_exp_multi.py:105-110
+extern "C" int64_t nlc_train_group_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
+  return group_workspace_bytes(c, false, M, N);
 }
-
+// train_utils.py:391-402 per member, run_exp_multi.py:105-110
+extern "C" int nlc_train_group_loss_grad(nlc_ctx* c, int M, int64_t data_row_stride, const double* params,
+                                         const double* obs, const double* window, const double* ts, const double* target,
+                                         const int64_t* idx, int64_t N, int B, double* grad, double* loss, void* ws) {
+  return group_loss_grad_entry(c, false, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
+}
+// train_utils.py:391-404 per member, run_exp_multi.py:105-110
+extern "C" int nlc_train_group_step(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride, double* params,
+                                    double* m, double* v, int64_t step, const double* obs, const double* window,
+                                    const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
+                                    double* loss, double* gradnorm, void* ws) {
+  return group_step_entry(c, false, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+                          gradnorm, ws);
+}
+// train_utils.py:388-408
+extern "C" int64_t nlc_train_workspace_bytes(nlc_ctx* c, int64_t N) { return group_workspace_bytes(c, false, 1, N); }
 // train_utils.py:391-402 (zero_grad, forward, MSELoss, backward)
 extern "C" int nlc_train_loss_grad(nlc_ctx* c, const double* params, const double* obs, const double* window,
                                    const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                                    double* grad, double* loss, void* ws) {
-  if (!c) return NLC_ERR_BAD_ARG;
-  NLC_GUARD_BEGIN
-  if (int rc = check_train(c, N, B)) return rc;
-  if (!params || !obs || !window || !ts || !target || !idx || !grad || !loss || !ws)
-    return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
-  NLC_HIP(c, hipSetDevice(c->device));
-  const Plan p = plan_of(c, N);
-  WsPtrs w;
-  ws_doubles(p, &w, ws);
-  return loss_grad(c, params, obs, window, ts, target, idx, N, B, grad, loss, p, w);
-  NLC_GUARD_END(c)
+  return group_loss_grad_entry(c, false, 1, 0, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
 }
-
 // train_utils.py:391-404 (one whole iteration: + clip_grad_norm_ + optimizer.step())
 extern "C" int nlc_train_step(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, double* v, int64_t step,
                               const double* obs, const double* window, const double* ts, const double* target,
                               const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws) {
-  if (!c) return NLC_ERR_BAD_ARG;
-  NLC_GUARD_BEGIN
-  if (!desc) return fail(c, NLC_ERR_BAD_ARG, "NULL train desc");
-  if (int rc = check_train(c, N, B)) return rc;
-  if (step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
-  if (!params || !m || !v || !obs || !window || !ts || !target || !idx || !loss || !ws)
-    return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
-  NLC_HIP(c, hipSetDevice(c->device));
-  const Plan p = plan_of(c, N);
-  WsPtrs w;
-  ws_doubles(p, &w, ws);
-  if (int rc = loss_grad(c, params, obs, window, ts, target, idx, N, B, w.grad, loss, p, w)) return rc;
-  return adam(c, desc, params, m, v, step, gradnorm, p, w);
-  NLC_GUARD_END(c)
+  return group_step_entry(c, false, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
 }
 
-// ---- DeltaTRNN / RNN (train_utils.py:550-631): the same three entries and contract; params, m, v flat in
-// nlc_set_rnn_model's blob order; ts may be NULL for a model without time input
+// ---- DeltaTRNN / RNN (train_utils.py:550-631): the same entries and contract; params, m, v flat in nlc_set_rnn_model's blob
+// order; ts may be NULL for a model without time input
+// train_utils.py:388-408, run_exp_multi.py:105-110
+extern "C" int64_t nlc_rnn_train_group_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
+  return group_workspace_bytes(c, true, M, N);
+}
+// train_utils.py:391-402 per member, run_exp_multi.py:105-110
+extern "C" int nlc_rnn_train_group_loss_grad(nlc_ctx* c, int M, int64_t data_row_stride, const double* params,
+                                             const double* obs, const double* window, const double* ts,
+                                             const double* target, const int64_t* idx, int64_t N, int B, double* grad,
+                                             double* loss, void* ws) {
+  return group_loss_grad_entry(c, true, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
+}
+// train_utils.py:391-404 per member, run_exp_multi.py:105-110
+extern "C" int nlc_rnn_train_group_step(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                        double* params, double* m, double* v, int64_t step, const double* obs,
+                                        const double* window, const double* ts, const double* target, const int64_t* idx,
+                                        int64_t N, int B, double* loss, double* gradnorm, void* ws) {
+  return group_step_entry(c, true, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+                          gradnorm, ws);
+}
 // train_utils.py:388-408
-extern "C" int64_t nlc_rnn_train_workspace_bytes(nlc_ctx* c, int64_t N) {
-  if (!c || !c->has_rnn || N < 1) return -1;
-  const Plan p = rnn_plan_of(c, N);
-  return ws_doubles(p, nullptr, nullptr) * (int64_t)sizeof(double);
-}
-
+extern "C" int64_t nlc_rnn_train_workspace_bytes(nlc_ctx* c, int64_t N) { return group_workspace_bytes(c, true, 1, N); }
 // train_utils.py:391-402 (zero_grad, forward, MSELoss, backward)
 extern "C" int nlc_rnn_train_loss_grad(nlc_ctx* c, const double* params, const double* obs, const double* window,
                                        const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                                        double* grad, double* loss, void* ws) {
-  if (!c) return NLC_ERR_BAD_ARG;
-  NLC_GUARD_BEGIN
-  if (int rc = check_rnn_train(c, N, B)) return rc;
-  if (!params || !obs || !window || (!ts && c->rd.time_input) || !target || !idx || !grad || !loss || !ws)
-    return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
-  NLC_HIP(c, hipSetDevice(c->device));
-  const Plan p = rnn_plan_of(c, N);
-  WsPtrs w;
-  ws_doubles(p, &w, ws);
-  return rnn_loss_grad(c, params, obs, window, ts, target, idx, N, B, grad, loss, p, w);
-  NLC_GUARD_END(c)
+  return group_loss_grad_entry(c, true, 1, 0, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
 }
-
 // train_utils.py:391-404 (one whole iteration: + clip_grad_norm_ + optimizer.step())
 extern "C" int nlc_rnn_train_step(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, double* v,
                                   int64_t step, const double* obs, const double* window, const double* ts,
                                   const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm,
                                   void* ws) {
-  if (!c) return NLC_ERR_BAD_ARG;
-  NLC_GUARD_BEGIN
-  if (!desc) return fail(c, NLC_ERR_BAD_ARG, "NULL train desc");
-  if (int rc = check_rnn_train(c, N, B)) return rc;
-  if (step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
-  if (!params || !m || !v || !obs || !window || (!ts && c->rd.time_input) || !target || !idx || !loss || !ws)
-    return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
-  NLC_HIP(c, hipSetDevice(c->device));
-  const Plan p = rnn_plan_of(c, N);
-  WsPtrs w;
-  ws_doubles(p, &w, ws);
-  if (int rc = rnn_loss_grad(c, params, obs, window, ts, target, idx, N, B, w.grad, loss, p, w)) return rc;
-  return adam(c, desc, params, m, v, step, gradnorm, p, w);
-  NLC_GUARD_END(c)
+  return group_step_entry(c, true, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
 }

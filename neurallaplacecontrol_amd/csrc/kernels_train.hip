@@ -2,6 +2,10 @@
 // (train_utils.py:388-408: model(bs0, ba0, bts), MSELoss, backward, clip_grad_norm_, Adam.step), float64 throughout
 // (model.double(), train_utils.py:267).  Three launches, no host synchronisation:
 //
+// blockIdx.y is the member of a group of same-shaped models (nlc_train.h GroupStrides; a single model is M = 1): every kernel
+// moves its base pointers by the member's strides and then does what it does for one model, with no atomics and no read of
+// another member's memory, so a member's bits do not depend on M or on its neighbours.
+//
 //   train_fwd_bwd_kernel  one workgroup per 16-row tile (a workgroup walks tiles b, b + G, ... when N needs more than
 //                         kMaxBlocks tiles): rows gathered through the int64 index array, normalisation as
 //                         nlc_model_forward, 2-layer reverse GRU with its gates taped, linear_out, per-row query points,
@@ -19,9 +23,10 @@
 // points and the line integral are the device library's.  tests/test_gpu_train.py holds the loss to 1e-12 relative and every
 // gradient to 1e-9 of its tensor's max |grad| against float64 autograd on the CPU.
 //
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage): train_fwd_bwd_kernel 256 VGPRs + AGPRs and 68 B/lane of scratch,
-// not yet traced to its source; one wave per SIMD.  The kernel is latency-bound at 2.3 ms per batch-16 iteration
-// (docs/training.md): the next step is LDS-resident activations and MFMA forward products, not this scratch.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage; table in docs/training.md): train_fwd_bwd_kernel 256 VGPRs + 250
+// AGPRs and 68 B/lane of scratch, not yet traced to its source; one wave per SIMD.  The kernel is latency-bound at 2.3 ms
+// per batch-16 iteration (docs/training.md): the next step is LDS-resident activations and MFMA forward products, not this
+// scratch.
 #include "nlc_train_dev.h"
 
 namespace nlc {
@@ -171,7 +176,8 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
   const int d = a.d, nin = a.nin, g = a.g, h = a.h, S = a.S, B = a.B;
   const int K0 = 2 * S + d + 2, O = 2 * d * S;
   const ActLayout& L = a.L;
-  double* ws = a.act + (int64_t)blockIdx.x * a.A;
+  const int64_t mi = blockIdx.y;  // member of the group: its own blob, workspace region, index array and dataset rows
+  double* ws = a.act + mi * a.gs.ws + (int64_t)blockIdx.x * a.A;
   double* X0 = ws + L.X0;
   double* H0 = ws + L.H0;
   double* G0 = ws + L.G0;
@@ -195,9 +201,10 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
   double* DX1 = ws + L.DX1;
   double* dhA = ws + L.dhA;
   double* dD = ws + L.dD;
-  const double* prm = a.params;
+  const double* prm = a.params + mi * a.gs.params;
   const int64_t* off = a.off;
-  double* part = a.partial + (int64_t)blockIdx.x * a.P;
+  double* part = a.partial + mi * a.gs.ws + (int64_t)blockIdx.x * a.P;
+  double* tile_loss = a.tile_loss + mi * a.gs.ws;
   const double loss_norm = 2.0 / ((double)a.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
   const double scale = 2.0;
 
@@ -209,7 +216,10 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
     for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
       const int r = p & (kRows - 1), e = p >> 4;
       const bool valid = row0 + r < a.N;
-      const int64_t src = valid ? a.idx[row0 + r] : 0;
+      // the member's rows: its slice of the index array, and of a stacked dataset (gs.rows = 0: the shared one).  The offset
+      // goes onto the row index here, not onto four base pointers before the loop: those stayed live across the whole
+      // kernel and took its scratch from 68 to 132 B/lane
+      const int64_t src = (valid ? a.idx[mi * a.gs.idx + row0 + r] : 0) + mi * a.gs.rows;
       if (e < B * nin) {
         const int s = e / nin, c = e - s * nin;  // step s of the reversed window = window row B - 1 - s
         X0[((int64_t)s * kRows + r) * nin + c] =
@@ -295,9 +305,9 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      double s = first ? 0.0 : a.tile_loss[blockIdx.x];
+      double s = first ? 0.0 : tile_loss[blockIdx.x];
       for (int i = 0; i < kRows * d; ++i) s += sq[i];
-      a.tile_loss[blockIdx.x] = s;
+      tile_loss[blockIdx.x] = s;
     }
     // ---- MLP backward
     dense_tanh_bwd(prm + off[14], d3, h, O, a2, d2);
@@ -364,6 +374,9 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
 __global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs a) {
   __shared__ double red[kThreads];
   const int b = blockIdx.x;
+  const int64_t mi = blockIdx.y;  // member of the group: its own partials, tile losses, gradient, chunk sums and loss
+  const double* partial = a.partial + mi * a.gs.ws;
+  double* grad = a.grad + mi * a.gs.grad;
   int t = 0;
   while (t + 1 < kTensors && a.cstart[t + 1] <= b) ++t;
   const int64_t e0 = a.off[t] + (int64_t)(b - a.cstart[t]) * kChunk;
@@ -371,8 +384,8 @@ __global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs
   double s = 0.0;
   for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
     double gsum = 0.0;
-    for (int k = 0; k < a.nblk; ++k) gsum += a.partial[(int64_t)k * a.P + e];
-    a.grad[e] = gsum;
+    for (int k = 0; k < a.nblk; ++k) gsum += partial[(int64_t)k * a.P + e];
+    grad[e] = gsum;
     s += gsum * gsum;
   }
   red[threadIdx.x] = s;
@@ -382,11 +395,12 @@ __global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    a.sq[b] = red[0];
+    a.sq[mi * a.gs.ws + b] = red[0];
     if (b == 0) {
+      const double* tile_loss = a.tile_loss + mi * a.gs.ws;
       double l = 0.0;
-      for (int k = 0; k < a.nblk; ++k) l += a.tile_loss[k];
-      *a.loss = l / ((double)a.N * (double)a.d);
+      for (int k = 0; k < a.nblk; ++k) l += tile_loss[k];
+      a.loss[mi] = l / ((double)a.N * (double)a.d);
     }
   }
 }
@@ -394,6 +408,12 @@ __global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs
 __global__ __launch_bounds__(kThreads) void train_adam_kernel(const AdamArgs a) {
   __shared__ double coef_s;
   const int b = blockIdx.x;
+  const int64_t mi = blockIdx.y;  // member of the group: its own chunk sums, clip coefficient and slices of params / m / v
+  const double* sq = a.sq + mi * a.gs.ws;
+  const double* grad = a.grad + mi * a.gs.grad;
+  double* params = a.params + mi * a.gs.params;
+  double* mom = a.m + mi * a.gs.params;
+  double* var = a.v + mi * a.gs.params;
   int t = 0;
   while (t + 1 < kTensors && a.cstart[t + 1] <= b) ++t;
   if (threadIdx.x == 0) {
@@ -401,39 +421,39 @@ __global__ __launch_bounds__(kThreads) void train_adam_kernel(const AdamArgs a) 
     double tot2 = 0.0;
     for (int i = 0; i < kTensors; ++i) {
       double s = 0.0;
-      for (int c = a.cstart[i]; c < a.cstart[i + 1]; ++c) s += a.sq[c];
+      for (int c = a.cstart[i]; c < a.cstart[i + 1]; ++c) s += sq[c];
       const double n = sqrt(s);
       tot2 += n * n;
     }
     const double total = sqrt(tot2);
     coef_s = a.max_norm > 0.0 ? clip_coef(a.max_norm, total) : 1.0;
-    if (b == 0 && a.gradnorm) *a.gradnorm = total;
+    if (b == 0 && a.gradnorm) a.gradnorm[mi] = total;
   }
   __syncthreads();
   const double coef = coef_s;
   const int64_t e0 = a.off[t] + (int64_t)(b - a.cstart[t]) * kChunk;
   const int64_t e1 = e0 + kChunk < a.off[t + 1] ? e0 + kChunk : a.off[t + 1];
   for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
-    double gv = a.grad[e];
+    double gv = grad[e];
     if (a.max_norm > 0.0) gv = gv * coef;
-    double p = a.params[e], mm = a.m[e], vv = a.v[e];
+    double p = params[e], mm = mom[e], vv = var[e];
     adam_element(&p, &mm, &vv, gv, a.k);
-    a.params[e] = p;
-    a.m[e] = mm;
-    a.v[e] = vv;
+    params[e] = p;
+    mom[e] = mm;
+    var[e] = vv;
   }
 }
 
-hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, hipStream_t s) {
-  hipLaunchKernelGGL(train_fwd_bwd_kernel, dim3(nblk), dim3(kThreads), 0, s, a);
+hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, int M, hipStream_t s) {
+  hipLaunchKernelGGL(train_fwd_bwd_kernel, dim3(nblk, M), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
-hipError_t launch_train_reduce(const ReduceArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(train_reduce_kernel, dim3(a.cstart[kTensors]), dim3(kThreads), 0, s, a);
+hipError_t launch_train_reduce(const ReduceArgs& a, int M, hipStream_t s) {
+  hipLaunchKernelGGL(train_reduce_kernel, dim3(a.cstart[kTensors], M), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
-hipError_t launch_train_adam(const AdamArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(train_adam_kernel, dim3(a.cstart[kTensors]), dim3(kThreads), 0, s, a);
+hipError_t launch_train_adam(const AdamArgs& a, int M, hipStream_t s) {
+  hipLaunchKernelGGL(train_adam_kernel, dim3(a.cstart[kTensors], M), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
 

@@ -86,19 +86,29 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
   const int d = a.d, nin = a.nin, B = a.B, ti = a.time_input ? 1 : 0;
   const int F = H + d + ti;
   const RnnActLayout& L = a.L;
-  double* ws = a.act + (int64_t)blockIdx.x * a.A;
+  const int64_t mi = blockIdx.y;  // member of the group (nlc_train.h GroupStrides; a single model is M = 1)
+  double* ws = a.act + mi * a.gs.ws + (int64_t)blockIdx.x * a.A;
   double* X = ws + L.X;
   double* Hs = ws + L.Hs;
   double* G = ws + L.G;
   double* DI = ws + L.DI;
   double* DH = ws + L.DH;
-  const double* Wih = a.params + a.off[0];
-  const double* Whh = a.params + a.off[1];
-  const double* bih = a.params + a.off[2];
-  const double* bhh = a.params + a.off[3];
-  const double* Wo = a.params + a.off[4];
-  const double* bo = a.params + a.off[5];
-  double* part = a.partial + (int64_t)blockIdx.x * a.P;
+  const double* prm = a.params + mi * a.gs.params;
+  const double* Wih = prm + a.off[0];
+  const double* Whh = prm + a.off[1];
+  const double* bih = prm + a.off[2];
+  const double* bhh = prm + a.off[3];
+  const double* Wo = prm + a.off[4];
+  const double* bo = prm + a.off[5];
+  double* part = a.partial + mi * a.gs.ws + (int64_t)blockIdx.x * a.P;
+  double* tile_loss = a.tile_loss + mi * a.gs.ws;
+  // the member's slice of the index array and its rows of a stacked dataset (gs.rows = 0: the shared one)
+  const int64_t* idx = a.idx + mi * a.gs.idx;
+  const int64_t drow = mi * a.gs.rows;
+  const double* obs = a.obs + drow * d;
+  const double* window = a.window + drow * B * nin;
+  const double* tsp = ti ? a.ts + drow : nullptr;  // a model without time input has no ts (a.ts may be NULL)
+  const double* target = a.target + drow * d;
   const double loss_norm = 2.0 / ((double)a.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
 
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
@@ -109,16 +119,16 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
     for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
       const int r = p & (kRows - 1), e = p >> 4;
       const bool valid = row0 + r < a.N;
-      const int64_t src = valid ? a.idx[row0 + r] : 0;
+      const int64_t src = valid ? idx[row0 + r] : 0;
       if (e < B * nin) {
         const int s = e / nin, c = e - s * nin;
-        X[((int64_t)s * kRows + r) * nin + c] = valid ? (a.window[(src * B + s) * nin + c] - a.am[c]) / a.as[c] : 0.0;
+        X[((int64_t)s * kRows + r) * nin + c] = valid ? (window[(src * B + s) * nin + c] - a.am[c]) / a.as[c] : 0.0;
       } else if (e < B * nin + d) {
         const int c = e - B * nin;
-        fS[r * LF + c] = valid ? (a.obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
-        tS[r * kMaxDim + c] = valid ? a.target[src * d + c] : 0.0;
+        fS[r * LF + c] = valid ? (obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
+        tS[r * kMaxDim + c] = valid ? target[src * d + c] : 0.0;
       } else {
-        fS[r * LF + d] = (valid && ti) ? a.ts[src] / a.time_div : 0.0;
+        fS[r * LF + d] = (valid && ti) ? tsp[src] / a.time_div : 0.0;
       }
     }
     for (int p = threadIdx.x; p < kRows * H; p += kThreads) {
@@ -181,9 +191,9 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      double s = first ? 0.0 : a.tile_loss[blockIdx.x];
+      double s = first ? 0.0 : tile_loss[blockIdx.x];
       for (int i = 0; i < kRows * d; ++i) s += sqS[i];
-      a.tile_loss[blockIdx.x] = s;
+      tile_loss[blockIdx.x] = s;
     }
     // ---- linear_out backward: its weight / bias gradients and dL/dh_B
     for (int p = threadIdx.x; p < d * F; p += kThreads) {
@@ -243,16 +253,17 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
 
 // one launcher over the widths nlc_set_rnn_model takes
 template <int... Ws>
-static hipError_t launch_widths(const RnnTrainArgs& a, int H, int nblk, hipStream_t s, std::integer_sequence<int, Ws...>) {
+static hipError_t launch_widths(const RnnTrainArgs& a, int H, int nblk, int M, hipStream_t s,
+                                std::integer_sequence<int, Ws...>) {
   auto launch = [&](auto w) {
-    hipLaunchKernelGGL((rnn_train_fwd_bwd_kernel<decltype(w)::value>), dim3(nblk), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL((rnn_train_fwd_bwd_kernel<decltype(w)::value>), dim3(nblk, M), dim3(kThreads), 0, s, a);
     return true;
   };
   const bool found = ((H == Ws && launch(std::integral_constant<int, Ws>{})) || ...);
   return found ? hipGetLastError() : hipErrorInvalidValue;
 }
-hipError_t launch_rnn_train_fwd_bwd(const RnnTrainArgs& a, int H, int nblk, hipStream_t s) {
-  return launch_widths(a, H, nblk, s, std::integer_sequence<int, 64, 128, 160>{});
+hipError_t launch_rnn_train_fwd_bwd(const RnnTrainArgs& a, int H, int nblk, int M, hipStream_t s) {
+  return launch_widths(a, H, nblk, M, s, std::integer_sequence<int, 64, 128, 160>{});
 }
 
 }  // namespace train

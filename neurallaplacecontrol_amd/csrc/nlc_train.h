@@ -175,6 +175,42 @@ NLC_HD RnnActLayout rnn_act_layout(int nin, int H, int B) {
   return L;
 }
 
+// ---- a group of M same-shaped models trained by the same launches (run_exp_multi.py:105-110 fans (env, delay, model_name)
+// out; the members of a group share the descriptor and differ in weights and data): blockIdx.y is the member, and a kernel
+// moves its base pointers by these strides, in doubles / int64 / rows from member m to member m + 1.  A single model is the
+// M = 1 case (blockIdx.y = 0: every stride multiplies 0).
+struct GroupStrides {
+  int64_t params;  // parameter blob (and Adam moments): P
+  int64_t ws;      // the member's workspace region (partials, tile losses, slabs, summed gradient, chunk sums): TrainWsLayout::total
+  int64_t grad;    // summed gradient: ws when it lives in the workspace (a step), P when the caller supplies [M][P]
+  int64_t idx;     // index array: N
+  int64_t rows;    // dataset rows (obs, window, ts, target): 0 = every member reads the same dataset
+};
+
+// one member's workspace, in doubles: [partials nblk * P | tile losses | slabs nblk * A | summed gradient P | chunk sums of
+// squares], every array and the total a multiple of 32 doubles, so M regions back to back stay 256-byte aligned
+struct TrainWsLayout {
+  int64_t partial, tile_loss, act, grad, sq, total;
+};
+inline TrainWsLayout train_ws_layout(int nblk, int64_t P, int64_t A, int chunks) {
+  auto al = [](int64_t n) { return (n + 31) / 32 * 32; };
+  TrainWsLayout w;
+  int64_t o = 0;
+  w.partial = o;
+  o += al((int64_t)nblk * P);
+  w.tile_loss = o;
+  o += al(nblk);
+  w.act = o;
+  o += al((int64_t)nblk * A);
+  w.grad = o;
+  o += al(P);
+  w.sq = o;
+  o += al(chunks);
+  w.total = o;
+  return w;
+}
+constexpr int kMaxGroup = 65535;  // members of a group: the grid's y limit
+
 struct RnnTrainArgs {
   int d, nin, B, time_input;
   double time_div;
@@ -190,6 +226,7 @@ struct RnnTrainArgs {
   double* tile_loss;
   double* act;
   int64_t off[kRnnTensors + 1];
+  GroupStrides gs;
 };
 
 struct TrainArgs {
@@ -207,6 +244,7 @@ struct TrainArgs {
   double* tile_loss;  // [gridDim.x] per-workgroup sums of squared errors
   double* act;        // [gridDim.x][A]
   int64_t off[kTensors + 1];
+  GroupStrides gs;    // params, partial / tile_loss / act, idx and the dataset pointers above are member 0's
 };
 
 struct ReduceArgs {
@@ -219,6 +257,7 @@ struct ReduceArgs {
   double* loss;  // 0-dim
   int64_t off[kTensors + 1];
   int cstart[kTensors + 1];  // first chunk of each tensor
+  GroupStrides gs;           // partial / tile_loss / sq by ws, grad by grad; loss is [gridDim.y]
 };
 
 struct AdamArgs {
@@ -227,9 +266,10 @@ struct AdamArgs {
   const double* sq;
   double max_norm;  // <= 0: no clipping
   AdamScalars k;
-  double* gradnorm;  // may be NULL
+  double* gradnorm;  // [gridDim.y]; may be NULL
   int64_t off[kTensors + 1];
   int cstart[kTensors + 1];
+  GroupStrides gs;  // params / m / v by params, grad by grad, sq by ws
 };
 
 }  // namespace train
@@ -239,10 +279,11 @@ struct AdamArgs {
 #include <hip/hip_runtime.h>
 namespace nlc {
 namespace train {
-hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, hipStream_t s);
-hipError_t launch_train_reduce(const ReduceArgs& a, hipStream_t s);
-hipError_t launch_train_adam(const AdamArgs& a, hipStream_t s);
-hipError_t launch_rnn_train_fwd_bwd(const RnnTrainArgs& a, int H, int nblk, hipStream_t s);  // H: 64, 128 or 160
+// M: members of the group = the grid's y dimension (1: a single model)
+hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, int M, hipStream_t s);
+hipError_t launch_train_reduce(const ReduceArgs& a, int M, hipStream_t s);
+hipError_t launch_train_adam(const AdamArgs& a, int M, hipStream_t s);
+hipError_t launch_rnn_train_fwd_bwd(const RnnTrainArgs& a, int H, int nblk, int M, hipStream_t s);  // H: 64, 128 or 160
 }  // namespace train
 }  // namespace nlc
 #endif

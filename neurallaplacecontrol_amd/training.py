@@ -17,6 +17,13 @@ with one warning.
 What does not depend on the model -- the flat parameter buffer and its views, the workspace cache, the re-upload of a changed
 model descriptor, the grad-mode fallbacks on the shared Adam state, ``run()`` and the optimiser state -- is ``_FusedTrainer``;
 a trainer class names its three library entries and says which models it takes.
+
+``NLTrainerGroup`` / ``RNNTrainerGroup`` train M models of one descriptor -- the reference's ``run_exp_multi.py:105-110``
+trains one model per (env, delay, model_name), times seeds, and for a fixed env and family those share the architecture and
+the normalisation constants -- in the same three launches, the member on the grid's second axis
+(``nlc_train_group_step`` / ``nlc_rnn_train_group_step``).  ``_FusedTrainer`` is written over a list of members: a single
+trainer is the group of one, and the group classes only change what a call takes (stacked data, ``(M, L)`` permutations) and
+returns (``(M,)`` losses, a list of optimiser states).  A member's results are bit-identical to its single trainer's.
 """
 
 import ctypes as C
@@ -52,29 +59,43 @@ class _FusedTrainer:
     ``tr.lr`` may change between calls (what a ``StepLR`` would do).  After ``step()`` / ``run()`` the model's parameters
     hold the new weights, written in place (their ``_version`` moves, so ``model.forward`` and planners re-upload).  The
     model's buffers and settings (normalisation constants, ``normalize`` / ``normalize_time``, ``ilt_options``) are
-    re-read before every call: a change after construction (``model.load_state_dict(checkpoint)``, say) takes effect."""
+    re-read before every call: a change after construction (``model.load_state_dict(checkpoint)``, say) takes effect.
 
-    _entries = None  # the library's (workspace_bytes, loss_grad, step) of the model family
+    Internally a trainer holds ``self.models`` (one member here, M in a group class): parameters, moments and gradients are
+    ``(M, P)`` buffers, losses ``(M,)``, and every library call is the group entry with its M."""
+
+    _entries = None  # the library's group (workspace_bytes, loss_grad, step) of the model family
     _reads_ts = True  # False: the model ignores ts_pred, and the kernels get no ts pointer (a property where it varies)
+    _grouped = False  # True: calls take / return the leading M (the group classes)
 
     def _unsupported(self, model):
         """Why no fused kernels exist for ``model`` whatever its shape (None: ask the library)."""
         return None
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
-        params = list(model.parameters())
-        model._require_float64()
-        if not params[0].is_cuda:
-            raise RuntimeError("training: move the model to the GPU first (model.to('cuda'))")
-        self.model = model
+        self._init([model], lr, betas, eps, weight_decay, clip_grad_norm)
+
+    def _init(self, models, lr, betas, eps, weight_decay, clip_grad_norm):
+        self._name = type(self).__name__
+        self.models = list(models)
+        if not self.models:
+            raise ValueError(f"{self._name}: needs at least one model")
+        self.model = model = self.models[0]  # the member whose descriptor the ctx holds
+        self._M = len(self.models)
+        self._members_key = None
+        self._check_members()
+        for mdl in self.models:
+            mdl._require_float64()
+            if not next(mdl.parameters()).is_cuda:
+                raise RuntimeError("training: move the model to the GPU first (model.to('cuda'))")
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.weight_decay, self.clip_grad_norm = float(weight_decay), float(clip_grad_norm)
-        self._dev = compute_device(params[0])
-        named = dict(model.named_parameters())
-        self._params = [named[k] for k in model._BLOB_KEYS]  # blob order (= model.parameters() order)
+        self._dev = compute_device(next(model.parameters()))
+        # blob order (= model.parameters() order), per member
+        self._mparams = [[dict(mdl.named_parameters())[k] for k in mdl._BLOB_KEYS] for mdl in self.models]
+        self._params = self._mparams[0]
         self._sizes = [p.numel() for p in self._params]
         self._fallback = None
-        self._name = type(self).__name__
         why = self._unsupported(model)
         if why is None:
             self._ctx = _lib.Ctx(self._dev.index)
@@ -82,13 +103,13 @@ class _FusedTrainer:
             why = self._sync_model()
         if why is not None:
             warnings.warn(f"{self._name}: {why} -- this model trains through its grad-mode forward + clip_grad_norm_ + "
-                          "torch.optim.Adam instead of the fused HIP step", stacklevel=2)
-            self._fallback = torch.optim.Adam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+                          "torch.optim.Adam instead of the fused HIP step", stacklevel=3)
+            self._fallback = [self._adam(i) for i in range(self._M)]
             return
-        P = sum(self._sizes)
-        self._flat = torch.empty(P, dtype=torch.float64, device=self._dev)
-        self._m = torch.zeros(P, dtype=torch.float64, device=self._dev)
-        self._v = torch.zeros(P, dtype=torch.float64, device=self._dev)
+        M, P = self._M, sum(self._sizes)
+        self._flat = torch.empty(M, P, dtype=torch.float64, device=self._dev)
+        self._m = torch.zeros(M, P, dtype=torch.float64, device=self._dev)
+        self._v = torch.zeros(M, P, dtype=torch.float64, device=self._dev)
         self._step = 0
         self._ws = {}
         self._arange = {}
@@ -100,17 +121,57 @@ class _FusedTrainer:
         return self._fallback is None
 
     # ------------------------------------------------------------------ plumbing
-    def _model_state_key(self):
+    def _model_state_key(self, model=None):
         """What the kernels read from the model descriptor besides the weights: the buffers (normalisation, dt) and the
         settings of ``_weights_key_extra()``.  Not the parameters: the trainer's own write-back moves their versions, and
         the kernels read the weights from ``_flat`` on every call."""
-        m = self.model
+        m = self.model if model is None else model
         return (tuple((id(b), b.data_ptr(), b._version) for b in m.buffers()), m._wk_dirty, tuple(m._weights_key_extra()))
+
+    @staticmethod
+    def _first_difference(a, b):
+        """The first thing the descriptor holds in which model ``b`` differs from ``a`` (None: they agree)."""
+        if type(a) is not type(b):
+            return f"class ({type(b).__name__} against {type(a).__name__})"
+        pa = {k: tuple(p.shape) for k, p in a.named_parameters()}
+        pb = {k: tuple(p.shape) for k, p in b.named_parameters()}
+        for k in pa:
+            if pa[k] != pb.get(k):
+                return f"the shape of {k} ({pb.get(k)} against {pa[k]})"
+        if len(pb) != len(pa):
+            return "its set of parameters"
+        ba, bb = dict(a.named_buffers()), dict(b.named_buffers())
+        for k in ba:
+            if k not in bb or ba[k].shape != bb[k].shape or not torch.equal(ba[k].detach().cpu(), bb[k].detach().cpu()):
+                return f"buffer {k}"
+        if len(bb) != len(ba):
+            return "its set of buffers"
+        if tuple(a._weights_key_extra()) != tuple(b._weights_key_extra()):
+            return "its settings (_weights_key_extra())"
+        return None
+
+    def _check_members(self):
+        """The equality rule of a group: every member agrees with member 0 on all the descriptor holds (class, shapes,
+        buffers by value, ``_weights_key_extra()``), else ValueError naming the first member and field that differ.  Run at
+        construction and before every call; the by-value comparison is redone only when some member's buffers or settings
+        have moved since the last one."""
+        if self._M == 1:
+            return
+        key = tuple(self._model_state_key(m) for m in self.models)
+        if key == self._members_key:
+            return
+        for i, mdl in enumerate(self.models[1:], 1):
+            field = self._first_difference(self.models[0], mdl)
+            if field is not None:
+                raise ValueError(f"{self._name}: member {i} differs from member 0 in {field}; a group trains models of one "
+                                 "descriptor (class, shapes, buffers, settings)")
+        self._members_key = key
 
     def _sync_model(self):
         """Re-upload the model descriptor if the buffers or settings changed since the last upload.  Returns None when the
         descriptor in the ctx is current, else the library's reason for refusing the new one (the fused kernels must not
         run then: the ctx still holds the old constants)."""
+        self._check_members()
         key = self._model_state_key()
         if self._model_key is not None and self._model_key[0] == key:
             return self._model_key[1]
@@ -131,25 +192,27 @@ class _FusedTrainer:
             warnings.warn(f"{self._name}: {why} -- calls the library refuses run the grad-mode forward + clip_grad_norm_ + "
                           "torch.optim.Adam on the trainer's optimiser state instead of the fused HIP step", stacklevel=3)
 
-    def _views(self, flat):
+    def _views(self, flat, i=0):
+        """Member ``i``'s row of an ``(M, P)`` buffer as views shaped like its parameters."""
         out, o = [], 0
-        for p, n in zip(self._params, self._sizes):
-            out.append(flat[o : o + n].view_as(p))
+        for p, n in zip(self._mparams[i], self._sizes):
+            out.append(flat[i, o : o + n].view_as(p))
             o += n
         return out
 
     def _gather(self):
-        torch.cat([p.detach().reshape(-1) for p in self._params], out=self._flat)
+        torch.cat([p.detach().reshape(-1) for ps in self._mparams for p in ps], out=self._flat.view(-1))
 
     def _scatter(self):
         with torch.no_grad():
-            for p, v in zip(self._params, self._views(self._flat)):
-                p.copy_(v)
+            for i, ps in enumerate(self._mparams):
+                for p, v in zip(ps, self._views(self._flat, i)):
+                    p.copy_(v)
 
     def _workspace(self, N):
         ws = self._ws.get(N)
         if ws is None:
-            n = getattr(self._ctx.lib, self._entries[0])(self._ctx.h, N)
+            n = getattr(self._ctx.lib, self._entries[0])(self._ctx.h, self._M, N)
             if n < 0:
                 raise _lib.NlcError(n, self._entries[0])
             ws = self._ws[N] = torch.empty((n + 7) // 8, dtype=torch.float64, device=self._dev)
@@ -169,14 +232,49 @@ class _FusedTrainer:
             raise ValueError("training batch: s0 (N, d), a0 (N, B, nin), ts (N,) or (N, 1), target (N, d)")
         return obs, win, ts, tgt.reshape(obs.shape)
 
+    def _stacked(self, s0):
+        """True when the data carry a leading M (``s0`` is (M, N, d)): member m reads its own rows."""
+        stacked = torch.as_tensor(s0).dim() == 3
+        if stacked and not self._grouped:
+            raise ValueError(f"{self._name}: s0 must be (N, d)")
+        if stacked and torch.as_tensor(s0).shape[0] != self._M:
+            raise ValueError(f"{self._name}: stacked data must lead with the group's {self._M} members")
+        return stacked
+
+    def _group_data(self, s0, a0, ts, target):
+        """``_data`` of a shared (2-D ``s0``) or stacked (3-D: the members' rows back to back) batch or dataset; also the
+        rows per member and the library's data_row_stride (0: shared)."""
+        if not self._stacked(s0):
+            obs, win, tsd, tgt = self._data(s0, a0, ts, target)
+            return obs, win, tsd, tgt, obs.shape[0], 0
+        rows = torch.as_tensor(s0).shape[1]
+
+        def flat(t):  # (M, rows, ...) -> (M rows, ...); a model that ignores ts may get none
+            if t is None:
+                return None
+            t = torch.as_tensor(t)
+            return t.reshape((self._M * rows,) + tuple(t.shape[2:]))
+
+        obs, win, tsd, tgt = self._data(flat(s0), flat(a0), flat(ts) if self._reads_ts else None, flat(target))
+        return obs, win, tsd, tgt, rows, rows
+
+    def _member_data(self, i, stacked, *tensors):
+        return tuple(torch.as_tensor(t)[i] if stacked and t is not None else t for t in tensors)
+
     def _idx(self, N):
+        """``(M, N)``: every member takes rows 0 .. N - 1 (of the shared batch, or of its own rows of a stacked one)."""
         idx = self._arange.get(N)
         if idx is None:
-            idx = self._arange[N] = torch.arange(N, dtype=torch.int64, device=self._dev)
+            idx = torch.arange(N, dtype=torch.int64, device=self._dev).repeat(self._M, 1).contiguous()
+            self._arange[N] = idx
         return idx
 
-    def _ref_loss(self, bs0, ba0, bts, bsd):
-        pred = self.model(bs0, ba0, bts)
+    def _out(self, t):
+        """An ``(M, ...)`` result as the class returns it: a single trainer drops the member axis."""
+        return t if self._grouped else t[0]
+
+    def _ref_loss(self, bs0, ba0, bts, bsd, i=0):
+        pred = self.models[i](bs0, ba0, bts)
         return torch.nn.functional.mse_loss(pred.squeeze(), bsd.squeeze())
 
     # ------------------------------------------------------------------ API
@@ -187,54 +285,57 @@ class _FusedTrainer:
             if why is not None:
                 self._host_path(why)
             return self._host_loss_and_grad(bs0, ba0, bts, bsd)
-        obs, win, ts, tgt = self._data(bs0, ba0, bts, bsd)
-        N = obs.shape[0]
+        obs, win, ts, tgt, N, rows = self._group_data(bs0, ba0, bts, bsd)
         self._gather()
         grad = torch.empty_like(self._flat)
-        loss = torch.empty((), dtype=torch.float64, device=self._dev)
+        loss = torch.empty(self._M, dtype=torch.float64, device=self._dev)
         ctx = self._ctx
         with ctx.stream():
             rc = getattr(ctx.lib, self._entries[1])(
-                ctx.h, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), _i64_ptr(self._idx(N)),
-                N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)))
+                ctx.h, self._M, rows, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt),
+                _i64_ptr(self._idx(N)), N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)))
         why = self._refused(rc)
         if why is not None:
             self._host_path(why)
             return self._host_loss_and_grad(bs0, ba0, bts, bsd)
-        for p, g in zip(self._params, self._views(grad)):
-            p.grad = g
-        return loss
+        for i, ps in enumerate(self._mparams):
+            for p, g in zip(ps, self._views(grad, i)):
+                p.grad = g
+        return self._out(loss)
 
     def step(self, bs0, ba0, bts, bsd):
         """One iteration of the reference's loop (train_utils.py:391-404); returns the loss before the update."""
+        stacked = self._stacked(bs0)
+        batches = lambda: [[self._member_data(i, stacked, bs0, ba0, bts, bsd)] for i in range(self._M)]  # noqa: E731
         if not self.fused:
-            return self._fallback_step(bs0, ba0, bts, bsd)
+            self._check_members()
+            return self._out(torch.stack([self._fallback_step(*b[0], i=i) for i, b in enumerate(batches())]))
         why = self._sync_model()
         if why is not None:
-            return self._host_steps(why, [(bs0, ba0, bts, bsd)])[0]
-        obs, win, ts, tgt = self._data(bs0, ba0, bts, bsd)
-        N = obs.shape[0]
+            return self._out(self._host_steps(why, batches())[:, 0])
+        obs, win, ts, tgt, N, rows = self._group_data(bs0, ba0, bts, bsd)
         self._gather()
-        loss = torch.empty((), dtype=torch.float64, device=self._dev)
+        loss = torch.empty(self._M, dtype=torch.float64, device=self._dev)
         ctx = self._ctx
         with ctx.stream():
             try:
-                self._launch_step(_i64_ptr(self._idx(N)), obs, win, ts, tgt, N, _f64_ptr(loss), self._workspace(N))
+                self._launch_step(_i64_ptr(self._idx(N)), obs, win, ts, tgt, N, _f64_ptr(loss), self._workspace(N), rows=rows)
             except _lib.NlcError as err:
                 if err.code != _lib.NLC_ERR_UNSUPPORTED:
                     raise
-                return self._host_steps(str(err), [(bs0, ba0, bts, bsd)])[0]
+                return self._out(self._host_steps(str(err), batches())[:, 0])
         self._scatter()
-        return loss
+        return self._out(loss)
 
-    def _launch_step(self, idx_ptr, obs, win, ts, tgt, N, loss_ptr, ws, desc=None):
-        """One ``nlc_train_step`` / ``nlc_rnn_train_step``; the Adam step count moves only once the library has accepted the call (it checks
-        everything on the host before the first launch)."""
+    def _launch_step(self, idx_ptr, obs, win, ts, tgt, N, loss_ptr, ws, desc=None, rows=0):
+        """One ``nlc_train_group_step`` / ``nlc_rnn_train_group_step`` (idx ``[M][N]``, loss ``[M]``, ``rows`` the
+        data_row_stride); the Adam step count moves only once the library has accepted the call (it checks everything on
+        the host before the first launch)."""
         ctx = self._ctx
         ctx.check(getattr(ctx.lib, self._entries[2])(
-            ctx.h, C.byref(desc if desc is not None else self._desc()), _f64_ptr(self._flat), _f64_ptr(self._m),
-            _f64_ptr(self._v), self._step + 1, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt), idx_ptr, N,
-            win.shape[1], loss_ptr, None, _f64_ptr(ws)))
+            ctx.h, C.byref(desc if desc is not None else self._desc()), self._M, rows, _f64_ptr(self._flat),
+            _f64_ptr(self._m), _f64_ptr(self._v), self._step + 1, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt),
+            idx_ptr, N, win.shape[1], loss_ptr, None, _f64_ptr(ws)))
         self._step += 1
 
     def _refused(self, rc):
@@ -245,67 +346,93 @@ class _FusedTrainer:
         return None
 
     def _host_loss_and_grad(self, bs0, ba0, bts, bsd):
-        self.model.zero_grad()
-        loss = self._ref_loss(bs0, ba0, bts, bsd)
-        loss.backward()
-        return loss.detach()
+        self._check_members()
+        stacked = self._stacked(bs0)
+        out = []
+        for i, mdl in enumerate(self.models):
+            mdl.zero_grad()
+            loss = self._ref_loss(*self._member_data(i, stacked, bs0, ba0, bts, bsd), i=i)
+            loss.backward()
+            out.append(loss.detach())
+        return self._out(torch.stack(out))
 
     def _host_steps(self, why, batches):
-        """Iterations the fused kernels refused, on the grad-mode path with a transient torch.optim.Adam that starts from
-        the trainer's step count and moments and hands them back: the trainer keeps one optimiser state."""
+        """Iterations the fused kernels refused (``batches[i]``: member i's), on the grad-mode path member by member with a
+        transient torch.optim.Adam that starts from the trainer's step count and the member's moments and hands them back:
+        the trainer keeps one optimiser state.  Returns the ``(M, iterations)`` losses."""
         self._host_path(why)
-        opt = self._adam()
-        self._export_state(opt)
-        out = [self._fallback_step(*b, opt=opt) for b in batches]
-        st = opt.state.get(self._params[0])
-        if st is not None:
-            with torch.no_grad():
-                for p, m, v in zip(self._params, self._views(self._m), self._views(self._v)):
-                    m.copy_(opt.state[p]["exp_avg"])
-                    v.copy_(opt.state[p]["exp_avg_sq"])
-            self._step = int(st["step"])
-        return out
+        out, step = [], self._step
+        for i, mine in enumerate(batches):
+            opt = self._adam(i)
+            self._export_state(opt, i)
+            out.append([self._fallback_step(*b, opt=opt, i=i) for b in mine])
+            st = opt.state.get(self._mparams[i][0])
+            if st is not None:
+                with torch.no_grad():
+                    for p, m, v in zip(self._mparams[i], self._views(self._m, i), self._views(self._v, i)):
+                        m.copy_(opt.state[p]["exp_avg"])
+                        v.copy_(opt.state[p]["exp_avg_sq"])
+                step = int(st["step"])
+        self._step = step  # every member made the same number of steps from the same count
+        if not out[0]:
+            return torch.empty(self._M, 0, dtype=torch.float64, device=self._dev)
+        return torch.stack([torch.stack(o) for o in out])
 
-    def _fallback_step(self, bs0, ba0, bts, bsd, opt=None):
-        opt = self._fallback if opt is None else opt
+    def _fallback_step(self, bs0, ba0, bts, bsd, opt=None, i=0):
+        opt = self._fallback[i] if opt is None else opt
         for grp in opt.param_groups:
             grp["lr"] = self.lr
         opt.zero_grad()
-        loss = self._ref_loss(bs0, ba0, bts, bsd)
+        loss = self._ref_loss(bs0, ba0, bts, bsd, i=i)
         loss.backward()
         if self.clip_grad_norm > 0:
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip_grad_norm)
+            torch.nn.utils.clip_grad_norm_(self.models[i].parameters(), self.clip_grad_norm)
         opt.step()
         return loss.detach()
 
     def run(self, s0, a0, sn, ts, permutation, batch_size=16):
         """Every full batch of ``permutation`` (train_utils.py:388-408 with ``bsd = bsn - bs0``): returns the (iters,) losses
-        on the device.  Fused: the dataset stays where it is, each iteration is one ``nlc_train_step`` on its slice of the
-        permutation, nothing crosses to the host until the end."""
+        on the device.  Fused: the dataset stays where it is, each iteration is one ``nlc_train_group_step`` on its slice of
+        the permutation, nothing crosses to the host until the end."""
         bs = int(batch_size)
-        iters = int(permutation.shape[0]) // bs
+        M = self._M
+        perm = torch.as_tensor(permutation).to(self._dev, torch.int64)
+        if perm.dim() == 1:
+            perm = perm.unsqueeze(0).expand(M, -1)  # one permutation for every member
+        elif not (self._grouped and perm.dim() == 2 and perm.shape[0] == M):
+            raise ValueError(f"{self._name}.run: permutation must be (L,)" + (f" or ({M}, L)" if self._grouped else ""))
+        iters = int(perm.shape[1]) // bs
+        stacked = self._stacked(s0)
 
         def host(why=None):
-            s0_, a0_, sn_, ts_ = (torch.as_tensor(t).to(self._dev) for t in (s0, a0, sn, ts))
-            perm = torch.as_tensor(permutation).to(self._dev)
             batches = []
-            for i in range(iters):
-                ind = perm[i * bs : i * bs + bs]
-                batches.append((s0_[ind], a0_[ind], ts_[ind], sn_[ind] - s0_[ind]))
-            out = [self._fallback_step(*b) for b in batches] if why is None else self._host_steps(why, batches)
-            return torch.stack(out) if out else torch.empty(0, dtype=torch.float64, device=self._dev)
+            for i in range(M):
+                s0_, a0_, sn_, ts_ = (torch.as_tensor(t).to(self._dev) for t in self._member_data(i, stacked, s0, a0, sn, ts))
+                mine = []
+                for k in range(iters):
+                    ind = perm[i, k * bs : k * bs + bs]
+                    mine.append((s0_[ind], a0_[ind], ts_[ind], sn_[ind] - s0_[ind]))
+                batches.append(mine)
+            if why is not None:
+                return self._out(self._host_steps(why, batches))
+            self._check_members()
+            if iters == 0:
+                return self._out(torch.empty(M, 0, dtype=torch.float64, device=self._dev))
+            return self._out(torch.stack([torch.stack([self._fallback_step(*b, i=i) for b in mine])
+                                          for i, mine in enumerate(batches)]))
 
         if not self.fused:
             return host()
         why = self._sync_model() if iters > 0 else None
         if why is not None:
             return host(why)
-        obs, win, tsd, sn_d = self._data(s0, a0, ts, sn)
-        tgt = sn_d - obs
-        perm = torch.as_tensor(permutation).to(self._dev, torch.int64).contiguous()
-        losses = torch.empty(iters, dtype=torch.float64, device=self._dev)
         if iters == 0:
-            return losses
+            return self._out(torch.empty(M, 0, dtype=torch.float64, device=self._dev))
+        obs, win, tsd, sn_d, _, rows = self._group_data(s0, a0, ts, sn)
+        tgt = sn_d - obs
+        # iteration k's index array [M][bs]: member m's slice k of its permutation
+        idx = perm[:, : iters * bs].reshape(M, iters, bs).transpose(0, 1).contiguous()
+        losses = torch.empty(iters, M, dtype=torch.float64, device=self._dev)
         ws = self._workspace(bs)
         self._gather()
         desc = self._desc()
@@ -313,7 +440,8 @@ class _FusedTrainer:
         with ctx.stream():
             for i in range(iters):
                 try:
-                    self._launch_step(_i64_ptr(perm, i * bs), obs, win, tsd, tgt, bs, _f64_ptr(losses, i), ws, desc)
+                    self._launch_step(_i64_ptr(idx, i * M * bs), obs, win, tsd, tgt, bs, _f64_ptr(losses, i * M), ws, desc,
+                                      rows=rows)
                 except _lib.NlcError as err:
                     # the library checks the shape on the host before any launch, and the shape is the same for every
                     # iteration: only the first can be refused, with nothing launched
@@ -321,63 +449,101 @@ class _FusedTrainer:
                         raise
                     return host(str(err))
         self._scatter()
-        return losses
+        return self._out(losses.t().contiguous())
 
     # ------------------------------------------------------------------ optimiser state
-    def _adam(self):
-        return torch.optim.Adam(self.model.parameters(), lr=self.lr, betas=self.betas, eps=self.eps,
+    def _adam(self, i=0):
+        return torch.optim.Adam(self.models[i].parameters(), lr=self.lr, betas=self.betas, eps=self.eps,
                                 weight_decay=self.weight_decay)
 
-    def _export_state(self, opt):
-        """The trainer's step count and moments as ``opt.state`` (copies)."""
+    def _export_state(self, opt, i=0):
+        """The trainer's step count and member ``i``'s moments as ``opt.state`` (copies)."""
         if self._step > 0:
             sdt = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32
-            for p, m, v in zip(self._params, self._views(self._m), self._views(self._v)):
+            for p, m, v in zip(self._mparams[i], self._views(self._m, i), self._views(self._v, i)):
                 opt.state[p] = {"step": torch.tensor(float(self._step), dtype=sdt), "exp_avg": m.clone(),
                                 "exp_avg_sq": v.clone()}
 
+    def _state_dicts(self):
+        if not self.fused:
+            return [opt.state_dict() for opt in self._fallback]
+        out = []
+        for i in range(self._M):
+            opt = self._adam(i)
+            self._export_state(opt, i)
+            out.append(opt.state_dict())
+        return out
+
     def state_dict(self):
         """``torch.optim.Adam(model.parameters(), ...).state_dict()`` of the same optimiser state."""
-        if not self.fused:
-            return self._fallback.state_dict()
-        opt = self._adam()
-        self._export_state(opt)
-        return opt.state_dict()
+        return self._state_dicts()[0]
 
     def load_state_dict(self, sd):
         """Take over a ``torch.optim.Adam`` state (hyper-parameters of its first group, step and moments).  An
         ``amsgrad`` or ``maximize`` state is refused: the trainer's update has neither."""
-        for grp in sd.get("param_groups", []):
-            for flag in ("amsgrad", "maximize"):
-                if grp.get(flag):
-                    raise ValueError(f"{self._name}.load_state_dict: an Adam state with {flag}=True is not supported "
-                                     "(the trainer runs plain Adam)")
-        if not self.fused:
-            self._fallback.load_state_dict(sd)
-            grp = self._fallback.param_groups[0]
-            self.lr = float(grp["lr"])
-            return
-        opt = self._adam()
-        opt.load_state_dict(sd)
-        grp = opt.param_groups[0]
-        self.lr, self.betas, self.eps = float(grp["lr"]), tuple(float(b) for b in grp["betas"]), float(grp["eps"])
-        self.weight_decay = float(grp["weight_decay"])
-        steps = {int(opt.state[p]["step"]) for p in self._params if p in opt.state}
+        self._load_state_dicts([sd])
+
+    def _load_state_dicts(self, sds):
+        """One state per member; nothing of the trainer changes unless all of them can be taken."""
+        if len(sds) != self._M:
+            raise ValueError(f"{self._name}.load_state_dict: {len(sds)} states for {self._M} members")
+        for sd in sds:
+            for grp in sd.get("param_groups", []):
+                for flag in ("amsgrad", "maximize"):
+                    if grp.get(flag):
+                        raise ValueError(f"{self._name}.load_state_dict: an Adam state with {flag}=True is not supported "
+                                         "(the trainer runs plain Adam)")
+        opts = [self._adam(i) for i in range(self._M)]
+        hypers, steps = set(), set()
+        for i, (opt, sd) in enumerate(zip(opts, sds)):
+            opt.load_state_dict(sd)
+            grp = opt.param_groups[0]
+            hypers.add((float(grp["lr"]), tuple(float(b) for b in grp["betas"]), float(grp["eps"]), float(grp["weight_decay"])))
+            mine = {int(opt.state[p]["step"]) for p in self._mparams[i] if p in opt.state}
+            steps |= mine if mine else {0}
         if len(steps) > 1:
-            raise ValueError(f"{self._name} keeps one Adam step count for all parameters")
-        self._step = steps.pop() if steps else 0
+            raise ValueError(f"{self._name} keeps one Adam step count for all parameters" +
+                             (" of all members" if self._grouped else ""))
+        if len(hypers) > 1:
+            raise ValueError(f"{self._name}.load_state_dict: the members' Adam hyper-parameters differ (one lr, betas, eps "
+                             "and weight_decay for the group)")
+        (self.lr, self.betas, self.eps, self.weight_decay), = hypers
+        if not self.fused:
+            self._fallback = opts
+            return
+        self._step = steps.pop()
         with torch.no_grad():
-            for p, m, v in zip(self._params, self._views(self._m), self._views(self._v)):
-                st = opt.state.get(p)
-                m.copy_(st["exp_avg"] if st else torch.zeros_like(m))
-                v.copy_(st["exp_avg_sq"] if st else torch.zeros_like(v))
+            for i, opt in enumerate(opts):
+                for p, m, v in zip(self._mparams[i], self._views(self._m, i), self._views(self._v, i)):
+                    st = opt.state.get(p)
+                    m.copy_(st["exp_avg"] if st else torch.zeros_like(m))
+                    v.copy_(st["exp_avg_sq"] if st else torch.zeros_like(v))
+
+
+class _Group:
+    """What a group class changes in ``_FusedTrainer``: the constructor takes the members, calls take stacked data and
+    ``(M, L)`` permutations and return the leading M, the optimiser state is a list of M."""
+
+    _grouped = True
+
+    def __init__(self, models, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
+        self._init(models, lr, betas, eps, weight_decay, clip_grad_norm)
+
+    def state_dict(self):
+        """A list of M ``torch.optim.Adam`` state dicts, one per member."""
+        return self._state_dicts()
+
+    def load_state_dict(self, sds):
+        """A list of M ``torch.optim.Adam`` states; ValueError when their step counts or hyper-parameters differ (the group
+        keeps one of each) or one has ``amsgrad`` / ``maximize``."""
+        self._load_state_dicts(list(sds))
 
 
 class NLTrainer(_FusedTrainer):
     """``tr = NLTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)`` for a
-    ``NeuralLaplaceModel``; the fused step takes Fourier models (``nlc_train_step``)."""
+    ``NeuralLaplaceModel``; the fused step takes Fourier models (``nlc_train_group_step``, M = 1)."""
 
-    _entries = ("nlc_train_workspace_bytes", "nlc_train_loss_grad", "nlc_train_step")
+    _entries = ("nlc_train_group_workspace_bytes", "nlc_train_group_loss_grad", "nlc_train_group_step")
 
     def _unsupported(self, model):
         if model.ilt_algorithm != "fourier":
@@ -387,11 +553,32 @@ class NLTrainer(_FusedTrainer):
 
 class RNNTrainer(_FusedTrainer):
     """``tr = RNNTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)`` for a
-    ``DeltaTRNN`` or an ``RNN`` (``nlc_rnn_train_step``): the methods and semantics of ``NLTrainer``.  An ``RNN`` ignores
-    ``ts`` as its forward does; the reference's loop still passes it, so every method accepts it."""
+    ``DeltaTRNN`` or an ``RNN`` (``nlc_rnn_train_group_step``, M = 1): the methods and semantics of ``NLTrainer``.  An
+    ``RNN`` ignores ``ts`` as its forward does; the reference's loop still passes it, so every method accepts it."""
 
-    _entries = ("nlc_rnn_train_workspace_bytes", "nlc_rnn_train_loss_grad", "nlc_rnn_train_step")
+    _entries = ("nlc_rnn_train_group_workspace_bytes", "nlc_rnn_train_group_loss_grad", "nlc_rnn_train_group_step")
 
     @property
     def _reads_ts(self):
         return bool(self.model._time_input)
+
+
+class NLTrainerGroup(_Group, NLTrainer):
+    """``grp = NLTrainerGroup(models, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)``: M
+    ``NeuralLaplaceModel`` s of one descriptor (run_exp_multi.py:105-110: the delays and seeds of one env) trained by the
+    same three launches, each member bit-identical to its own ``NLTrainer``.
+
+    * ``grp.loss_and_grad(bs0, ba0, bts, bsd)`` / ``grp.step(...)`` -- ``(M,)`` losses; a 2-D ``bs0`` (N, d) is one batch
+      shared by the members, a 3-D one (M, N, d) gives each its own (the others then lead with M too);
+    * ``grp.run(s0, a0, sn, ts, permutations, batch_size=16)`` -- ``(M, iters)`` losses; ``permutations`` (M, L), or (L,) to
+      share; the datasets shared or stacked by the same rule;
+    * ``grp.state_dict()`` / ``grp.load_state_dict(list)`` -- a list of M ``torch.optim.Adam`` states;
+    * ``grp.lr``, ``grp.fused``, ``grp.models``.
+
+    The members must agree on all the descriptor holds (class, shapes, buffers by value, settings), at construction and at
+    every call: ValueError names the first member and field that differ.  One lr, betas, eps, weight decay and step count."""
+
+
+class RNNTrainerGroup(_Group, RNNTrainer):
+    """``grp = RNNTrainerGroup(models, ...)``: M ``DeltaTRNN`` s or M ``RNN`` s of one descriptor; the methods and
+    semantics of ``NLTrainerGroup``."""

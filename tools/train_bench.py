@@ -12,7 +12,18 @@ Each (batch size, variant) measurement is a child process of its own under --ste
 runs out of time ends the tool (nothing more is started on the GPU).  `--kernel-ms` adds the mean time of each kernel of the
 fused step from the library's event profiling (200 step()s).
 
+`--group M [M ...]` measures grouped training instead (NLTrainerGroup / RNNTrainerGroup, run_exp_multi.py:105-110): for both
+families and every M, run() of a group of M differently seeded models at the first --batches size (16) over one shared
+dataset with a permutation per member; a warm-up run, then --repeats timed runs of --run-iters iterations in one child
+process per (family, M).  Per M: iterations / s (median and the min .. max spread over the repeats) and the aggregate
+member-iterations / s = M x that; M = 1 is timed twice, as the group class and as this commit's single trainer.
+`--parent-tree DIR` names a built checkout of the parent commit (git worktree + its build()): the tool then times that tree's
+own `tools/train_bench.py --only run` --repeats times per family between this commit's measurements, in the same session, and
+records `parent_single`, `m1_over_parent` (M = 1 of this commit against it) and `aggregate_over_parent` per M.  Writes
+profiles/train_bench_group.json unless --out says otherwise.
+
     python tools/train_bench.py [--model nl|delta_t_rnn] [--batches 16 256] [--ref-iters 200] [--step-iters 1000] [--run-iters 10000] [--out FILE]
+    python tools/train_bench.py --group 1 8 64 256 [--repeats 3] [--run-iters 10000] [--parent-tree DIR]
 """
 
 import argparse
@@ -42,17 +53,17 @@ def make_trainer(model):
     return nlc.RNNTrainer(model) if MODEL == "delta_t_rnn" else nlc.NLTrainer(model)
 
 
-def make_model():
+def make_model(seed=0):
     st = onl.ENV_STATS[ENV]
     if MODEL == "delta_t_rnn":
         from oracle import rnn_model as orn
 
-        sd = orn.make_synthetic_state_dict(0, D, NU, RNN_H, st["state_std"], [st["act_high"] / 2])
+        sd = orn.make_synthetic_state_dict(seed, D, NU, RNN_H, st["state_std"], [st["act_high"] / 2])
         m = nlc.DeltaTRNN(D, NU, hidden_units=RNN_H, state_mean=np.zeros(D), state_std=np.ones(D), action_mean=np.array([0]),
                           action_std=np.array([1.0]), normalize=True, normalize_time=True).double()
         m.load_state_dict(sd)
         return m.to("cuda")
-    sd = onl.make_synthetic_state_dict(0, D, NU, H, S, st["state_std"], [st["act_high"] / 2], tame=True)
+    sd = onl.make_synthetic_state_dict(seed, D, NU, H, S, st["state_std"], [st["act_high"] / 2], tame=True)
     m = nlc.NeuralLaplaceModel(D, NU, D, hidden_units=H, s_recon_terms=S, ilt_algorithm="fourier", state_mean=np.zeros(D),
                                state_std=np.ones(D), action_mean=np.array([0]), action_std=np.array([1.0]), normalize=True,
                                normalize_time=True).double()
@@ -133,6 +144,30 @@ def time_run(bs, iters, warm):
     return iters / dt
 
 
+def time_group(bs, iters, warm, M, repeats):
+    """run() of a group of M (M = 0: the single trainer) over one shared dataset, a permutation per member: iterations / s of
+    each of `repeats` timed runs after one warm-up run of `warm` iterations."""
+    s0, a0, sn, ts = dataset(bs * iters)
+    n = max(M, 1)
+    perms = torch.stack([torch.randperm(s0.shape[0], generator=torch.Generator().manual_seed(i)) for i in range(n)]).cuda()
+    models = [make_model(seed=i) for i in range(n)]
+    if M == 0:
+        tr, perms = make_trainer(models[0]), perms[0]
+    else:
+        tr = (nlc.RNNTrainerGroup if MODEL == "delta_t_rnn" else nlc.NLTrainerGroup)(models)
+    assert tr.fused
+    tr.run(s0, a0, sn, ts, perms[..., : bs * warm], batch_size=bs)
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        losses = tr.run(s0, a0, sn, ts, perms, batch_size=bs)
+        torch.cuda.synchronize()
+        out.append(iters / (time.perf_counter() - t0))
+        assert bool(torch.isfinite(losses).all())
+    return out
+
+
 def kernel_ms(bs, iters=200, warm=20):
     """Mean milliseconds per launch of each kernel of step() (the library's event pairs around every launch)."""
     tr = make_trainer(make_model())
@@ -175,6 +210,9 @@ def main():
     ap.add_argument("--model", choices=sorted(WORKLOADS), default="nl")
     ap.add_argument("--kernel-ms", action="store_true")
     ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds each child measurement may take")
+    ap.add_argument("--group", type=int, nargs="+", default=None, metavar="M", help="grouped training: members per group")
+    ap.add_argument("--repeats", type=int, default=3, help="timed runs per --group measurement")
+    ap.add_argument("--parent-tree", default=None, help="--group: a built checkout of the parent commit to time beside this one")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     global MODEL
@@ -182,6 +220,9 @@ def main():
     torch.manual_seed(0)
     if args.child:
         bs, variant = int(args.child[0]), args.child[1]
+        if variant.startswith("group"):
+            print("RESULT " + json.dumps(time_group(bs, args.run_iters, args.warmup, int(variant[5:]), args.repeats)))
+            return
         fn = {"ref": lambda: time_ref(bs, args.ref_iters, args.warmup), "step": lambda: time_step(bs, args.step_iters, args.warmup),
               "run": lambda: time_run(bs, args.run_iters, args.warmup), "kernel_ms": lambda: kernel_ms(bs)}[variant]
         print("RESULT " + json.dumps(fn()))
@@ -189,9 +230,54 @@ def main():
 
     def measure(bs, variant):
         cmd = [sys.executable, os.path.abspath(__file__), "--model", MODEL, "--ref-iters", str(args.ref_iters), "--step-iters",
-               str(args.step_iters), "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--child", str(bs), variant]
+               str(args.step_iters), "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--repeats",
+               str(args.repeats), "--child", str(bs), variant]
         out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
         return json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+    def spread(runs):
+        runs = sorted(runs)
+        return {"it_s": runs[len(runs) // 2], "it_s_min": runs[0], "it_s_max": runs[-1]}
+
+    def measure_parent(bs):
+        """run() of the parent tree's single trainer through that tree's own tool (its package, its library)."""
+        tree = os.path.abspath(args.parent_tree)
+        cmd = [sys.executable, os.path.join(tree, "tools", "train_bench.py"), "--model", MODEL, "--batches", str(bs), "--only",
+               "run", "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--step-timeout", str(args.step_timeout)]
+        runs = []
+        for _ in range(args.repeats):
+            out = subprocess.run(cmd, cwd=tree, timeout=args.step_timeout + 60, check=True, capture_output=True, text=True).stdout
+            runs.append(json.loads(out.splitlines()[-1])["batches"][str(bs)]["run_it_s"])
+        return spread(runs)
+
+    if args.group:
+        bs = args.batches[0]
+        res = {"device": torch.cuda.get_device_name(0), "batch": bs, "run_iters": args.run_iters, "repeats": args.repeats,
+               "families": {}}
+        for MODEL in sorted(WORKLOADS):
+            fam = {"workload": WORKLOADS[MODEL], "groups": {}}
+            for M in [0] + list(args.group):  # 0: the single trainer, in the same session
+                r = spread(measure(bs, f"group{M}"))
+                if M == 0:
+                    fam["single"] = r
+                    if args.parent_tree:
+                        fam["parent_single"] = measure_parent(bs)
+                        print(f"# {MODEL} parent single: {fam['parent_single']}", file=sys.stderr, flush=True)
+                else:
+                    r["member_it_s"] = M * r["it_s"]
+                    r["aggregate_over_single"] = r["member_it_s"] / fam["single"]["it_s"]
+                    if args.parent_tree:
+                        r["aggregate_over_parent"] = r["member_it_s"] / fam["parent_single"]["it_s"]
+                        if M == 1:
+                            fam["m1_over_parent"] = r["it_s"] / fam["parent_single"]["it_s"]
+                    fam["groups"][str(M)] = r
+                print(f"# {MODEL} M={M or 'single'}: {r}", file=sys.stderr, flush=True)
+            res["families"][MODEL] = fam
+        line = json.dumps(res)
+        print(line)
+        with open(args.out or os.path.join(REPO, "profiles", "train_bench_group.json"), "w") as f:
+            f.write(line + "\n")
+        return
 
     res = {"workload": WORKLOADS[MODEL], "device": torch.cuda.get_device_name(0), "batches": {}}
     for bs in args.batches:
