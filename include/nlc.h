@@ -475,7 +475,11 @@ int nlc_mppi_rollout(nlc_ctx* ctx, const double* state_host, int state_per_sampl
                      uint64_t counter);
 /* NLC_DYN_EXTERNAL / cost_external: nlc_mppi_rollout stops after the perturbation / after the rollout; once the
  * caller has completed buf->cost_total (rollout cost + perturbation cost, :339-344) this computes the softmax
- * partials. */
+ * partials.
+ * Non-finite costs (this call and the weights inside nlc_mppi_rollout alike): a +inf cost weighs exactly 0 at every level
+ * of the fold -- also when a whole 16-sample tile, 64-tile chunk, episode or shard is +inf -- so the partials are those of
+ * the population without these samples, as the reference's one-level softmax gives them.  A NaN or -inf cost makes
+ * eta_r NaN; a shard whose costs are all +inf has (beta_r, eta_r, S_r) = (+inf, 0, 0). */
 int nlc_mppi_weights(nlc_ctx* ctx, const nlc_mppi_buffers* buf);
 /* Phase 2: merge G shard partials (gathered_dev: (G, E, 2+T*nu); pass buf->partials and G=1 on one GPU; NULL: gather
  * them with the ctx's own communicator, see the multi-GPU note below),
@@ -483,7 +487,10 @@ int nlc_mppi_weights(nlc_ctx* ctx, const nlc_mppi_buffers* buf);
  * (:217-224) into action_host (E*u_per_command*nu) -- the call waits until the ACTION is in host memory (see "host_spin":
  * cost_nz / omega may still be in flight on the stream; nlc_synchronize before reading them from the host) -- and/or into
  * buf->action on the device.  With action_host == NULL nothing is copied back and the call does not synchronise.
- * Returns NLC_AGAIN (> 0, not an error) when a sharded command had to be re-run and the caller owns the collective. */
+ * Returns NLC_AGAIN (> 0, not an error) when a sharded command had to be re-run and the caller owns the collective.
+ * Non-finite costs: a shard with beta_r = +inf is merged with scale exactly 0; +inf samples get cost_nz = omega = 0 and the
+ * action is finite whenever one cost of the population is.  A NaN or -inf cost anywhere, or +inf costs everywhere
+ * (eta = 0), give a NaN action and NaN U, as in the reference: poisoned costs are never turned into a finite action. */
 int nlc_mppi_finish(nlc_ctx* ctx, const double* gathered_dev, int G, int rank, const nlc_mppi_buffers* buf,
                     double* action_host);
 /* Multi-GPU: the one exchange of a K-sharded command is the all-gather of buf->partials ((2+T*nu) doubles per rank and

@@ -157,6 +157,10 @@ hipError_t launch_weights(const WeightArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------ merge shard partials, update U (:213-224)
 // gathered[g] = (beta_g, eta_g, S_g[T*nu]).  beta = min beta_g, scale_g = exp(-(beta_g - beta)/lambda),
 // eta = sum scale_g eta_g, dU = sum scale_g S_g / eta   (SURVEY §8e).  Every rank runs this identically.
+// scale_g = 0 for a shard whose beta_g is +inf (all its costs are; non-finite costs: nlc_mppi_dev.h).
+__device__ __forceinline__ double merge_scale(double beta_g, double beta, double lambda_) {
+  return beta_g != INFINITY ? exp(-(beta_g - beta) / lambda_) : 0.0;
+}
 __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
   __shared__ double s_scale_self, s_eta;
   const int TN = a.T * a.nu;
@@ -192,12 +196,12 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeArgs a) {
   double beta = INFINITY;
   for (int g = 0; g < a.G; ++g) beta = fmin(beta, gat[g * gs]);
   double eta = 0.0;
-  for (int g = 0; g < a.G; ++g) eta += exp(-(gat[g * gs] - beta) / a.lambda_) * gat[g * gs + 1];
+  for (int g = 0; g < a.G; ++g) eta += merge_scale(gat[g * gs], beta, a.lambda_) * gat[g * gs + 1];
   if (blockIdx.x == 0) {
     double* U = a.U + e * TN;
     for (int i = threadIdx.x; i < TN; i += 256) {
       double acc = 0.0;
-      for (int g = 0; g < a.G; ++g) acc += exp(-(gat[g * gs] - beta) / a.lambda_) * gat[g * gs + 2 + i];
+      for (int g = 0; g < a.G; ++g) acc += merge_scale(gat[g * gs], beta, a.lambda_) * gat[g * gs + 2 + i];
       const double u = U[i] + (1.0 / eta) * acc;  // omega = (1/eta) w, :214-216
       U[i] = u;
       if (i < a.u_per_command * a.nu) {

@@ -88,10 +88,17 @@ __device__ __forceinline__ double wave_sum(double v) {
 // Two levels, so that a 16-sample rollout tile can fold its own samples the moment its costs are final (the fused planner
 // body does, inside its launch) and every path produces the same bits:
 //   tile b (kWeightTile consecutive samples of episode e):   beta_b = min c,  w_s = exp(-(c_s - beta_b)/lambda),
+//                                                            w_s = 0 where c_s = +inf,
 //                                                            eta_b = sum w_s,  S_b[t,j] = sum_s w_s eps[s,t,j]
 //   rank (all nblk tiles of the episode):  beta = min beta_b,  scale_b = exp(-(beta_b - beta)/lambda),
+//                                          scale_b = 0 where beta_b = +inf,
 //                                          eta = sum scale_b eta_b,  S = sum scale_b S_b          -> partials (beta, eta, S)
 // -- the same rescaling the shard merge applies between ranks.  cost_nz / omega come from merge_kernel.
+// Non-finite costs.  The one-level formula gives a +inf cost the weight exp(-inf) = 0 whenever one cost is finite.  Here a
+// tile, a chunk or a shard whose costs are ALL +inf has beta_b = +inf, and exp(-(inf - inf)/lambda) would be NaN, which the
+// next level's scale 0 does not remove (0 * NaN): hence the two explicit zeros above and merge_kernel's third.  They are
+// selects on `== +inf`: no bit of a finite-cost result changes.  A NaN or -inf cost still ends in a NaN action, and so does a
+// population whose costs are all +inf (eta = 0), as in the one-level formula.
 // tile_part layout: (E, nblk, 2 + T*nu) = (beta_b, eta_b, S_b[T*nu]).
 //
 // weight_tile: ONE wavefront.  `cost`: the cost of sample (lane & 15) of the tile in every lane (any value where !valid).
@@ -104,7 +111,7 @@ __device__ __forceinline__ void weight_tile(const WeightArgs& a, int64_t e, int6
   const int ns = (int)(left < kWeightTile ? left : kWeightTile);
   double beta = valid ? cost : INFINITY;
   for (int o = 8; o > 0; o >>= 1) beta = fmin(beta, __shfl_xor(beta, o, 64));
-  const double w = valid ? exp(-(1.0 / a.lambda_) * (cost - beta)) : 0.0;  // _ensure_non_zero :12-13
+  const double w = (valid && cost != INFINITY) ? exp(-(1.0 / a.lambda_) * (cost - beta)) : 0.0;  // _ensure_non_zero :12-13
   double eta = w;
   for (int o = 8; o > 0; o >>= 1) eta += __shfl_xor(eta, o, 64);
   double* out = a.tile_part + (e * a.nblk + b) * (2 + TN);
@@ -149,8 +156,10 @@ __device__ __forceinline__ double weight_chunk(const WeightArgs& a, int64_t e, i
   const int i = i0 + lane;
   const bool on = i < 1 + TN;
   __syncthreads();  // (the previous chunk's s_scale / s_acc have been read)
-  if (tid < kWeightChunk && j * kWeightChunk + tid < a.nblk)
-    s_scale[tid] = exp(-(1.0 / a.lambda_) * (M::ld(part + (int64_t)(j * kWeightChunk + tid) * W) - beta));
+  if (tid < kWeightChunk && j * kWeightChunk + tid < a.nblk) {
+    const double bb = M::ld(part + (int64_t)(j * kWeightChunk + tid) * W);
+    s_scale[tid] = bb != INFINITY ? exp(-(1.0 / a.lambda_) * (bb - beta)) : 0.0;  // an all-+inf tile: eta_b = S_b = 0
+  }
   __syncthreads();
   const int b0 = j * kWeightChunk + 16 * wv;
   double acc = 0.0;

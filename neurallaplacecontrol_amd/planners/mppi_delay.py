@@ -33,8 +33,8 @@ from torch.distributions.multivariate_normal import MultivariateNormal
 
 from .. import _lib, _recognise
 from ..envs import EnvCost, NLDynamics, OracleDynamics
-from ..sharding import (all_ranks_agree, check_same_on_all_ranks, gather_partials, merge_partials_torch, replicate_from_rank0, shard_range,
-                        share_bytes_from_rank0, slice_noise)
+from ..sharding import (all_ranks_agree, check_same_on_all_ranks, gather_partials, merge_partials_torch, replicate_from_rank0, shard_partials_torch,
+                        shard_range, share_bytes_from_rank0, slice_noise)
 
 
 def _backend_is_rccl(group):
@@ -626,9 +626,7 @@ class MPPIDelay:
             self._omega = (1.0 / self._cost_nz.sum()) * self._cost_nz
             dU = (self._omega.view(-1, 1, 1) * self._noise).sum(dim=0)
         else:
-            beta_r = cost.min()
-            w = torch.exp(-(cost - beta_r) / lam)
-            part = torch.cat((beta_r.view(1), w.sum().view(1), (w.view(-1, 1, 1) * self._noise).sum(dim=0).reshape(-1)))
+            part = shard_partials_torch(cost, self._noise, lam)
             gathered = torch.empty(self.G, 2 + T * nu, dtype=dt, device=dev)
             beta, eta, S = merge_partials_torch(gather_partials(part, gathered, self.pg), lam)
             self._cost_nz = torch.exp(-(cost - beta) / lam)

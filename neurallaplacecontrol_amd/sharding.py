@@ -33,13 +33,25 @@ def gather_partials(partials, gathered, group):
     return gathered
 
 
+def shard_partials_torch(cost, noise, lambda_):
+    """One rank's row (beta_r, eta_r, S_r[t, j]) of its (K_local,) costs and (K_local, T, nu) noise as tensor ops
+    (MPPIDelay._torch_command; weight_tile / weight_rank do the same on the HIP path).  A +inf cost weighs exactly 0, as in
+    the one-level formula -- also when the whole shard is +inf, where exp(-(inf - inf)) would be NaN."""
+    beta_r = cost.min()
+    w = torch.exp(-(cost - beta_r) / lambda_)
+    w = torch.where(cost == float("inf"), torch.zeros_like(w), w)
+    return torch.cat((beta_r.view(1), w.sum().view(1), (w.view(-1, 1, 1) * noise).sum(dim=0).reshape(-1)))
+
+
 def merge_partials_torch(gathered, lambda_):
     """The shard merge of SURVEY 8e as tensor ops (the planners the HIP kernels are not built for, MPPIDelay._torch_command;
     merge_kernel does the same on the HIP path): rows (beta_r, eta_r, S_r[t, j]) of every rank -> beta = min beta_r,
-    scale_r = exp(-(beta_r - beta) / lambda), eta = sum scale_r eta_r, S = sum scale_r S_r.  Returns (beta, eta, S)."""
+    scale_r = exp(-(beta_r - beta) / lambda) (0 for a shard whose beta_r is +inf: all its costs are), eta = sum scale_r eta_r,
+    S = sum scale_r S_r.  Returns (beta, eta, S)."""
     beta_r, eta_r, S_r = gathered[:, 0], gathered[:, 1], gathered[:, 2:]
     beta = beta_r.min()
     scale = torch.exp(-(beta_r - beta) / lambda_)
+    scale = torch.where(beta_r == float("inf"), torch.zeros_like(scale), scale)
     return beta, (scale * eta_r).sum(), (scale.view(-1, 1) * S_r).sum(dim=0)
 
 

@@ -113,16 +113,19 @@ def mppi_command(
 
 
 def shard_partials(cost, eps, lambda_=1.0):
-    """Per-rank partials (beta_r, eta_r, S_r[t,j]) of SURVEY §8e for one K-shard."""
+    """Per-rank partials (beta_r, eta_r, S_r[t,j]) of SURVEY §8e for one K-shard.  A +inf cost weighs 0 as in the plain
+    formula of mppi_command, also in a shard whose costs are all +inf (there exp(-(inf - inf)) would be NaN)."""
     beta = torch.min(cost)
     w = torch.exp(-(1.0 / lambda_) * (cost - beta))
+    w = torch.where(cost == float("inf"), torch.zeros_like(w), w)
     return torch.cat((beta.view(1), w.sum().view(1), torch.einsum("k,ktj->tj", w, eps).reshape(-1)))
 
 
 def merge_partials(parts, lambda_=1.0):
-    """Merge gathered (G, 2+T*nu) partials: beta=min, rescale by exp(-(beta_r-beta)/lambda)."""
+    """Merge gathered (G, 2+T*nu) partials: beta=min, rescale by exp(-(beta_r-beta)/lambda) (0 for an all-+inf shard)."""
     beta = parts[:, 0].min()
     scale = torch.exp(-(parts[:, 0] - beta) / lambda_)
+    scale = torch.where(parts[:, 0] == float("inf"), torch.zeros_like(scale), scale)
     eta = (scale * parts[:, 1]).sum()
     dU = (scale.view(-1, 1) * parts[:, 2:]).sum(0) / eta
     return beta, eta, dU
