@@ -19,7 +19,7 @@ thread_local std::string g_create_error;
 //   g = 128 (hidden_units 256; 64 KB of images: two workgroups per CU instead of one): better at every size (0.079 vs
 //           0.289 ms at 16 windows, 10.9 vs 11.7 ms at 655360).
 bool gru_use_coop(const nlc_ctx* c, int64_t n_windows) {
-  if (c->opt_gru_coop >= 0) return c->opt_gru_coop != 0;
+  if (c->opt.gru_coop >= 0) return c->opt.gru_coop != 0;
   if (c->g == 128) return true;
   return n_windows <= (c->g == 32 ? 8192 : 50000);
 }
@@ -45,6 +45,28 @@ bool is_device_ptr(const void* p) {
     return false;
   }
   return at.type == hipMemoryTypeDevice;
+}
+
+int hold_doubles(nlc_ctx* c, double*& p, size_t n, const double* upload, size_t* have) {
+  if (!have || n > *have) {
+    if (p) hipFree(p);
+    p = nullptr;
+    if (have) *have = 0;
+    NLC_HIP(c, hipMalloc((void**)&p, n * sizeof(double)));
+    if (have) *have = n;
+  }
+  if (upload) NLC_HIP(c, hipMemcpy(p, upload, n * sizeof(double), hipMemcpyHostToDevice));
+  return NLC_OK;
+}
+
+int hold_pinned_doubles(nlc_ctx* c, double*& p, size_t n, size_t* have) {
+  if (n <= *have) return NLC_OK;
+  if (p) hipHostFree(p);
+  p = nullptr;
+  *have = 0;
+  NLC_HIP(c, hipHostMalloc((void**)&p, n * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+  *have = n;
+  return NLC_OK;
 }
 
 }  // namespace host
@@ -113,14 +135,8 @@ extern "C" void nlc_destroy(nlc_ctx* c) {
   if (c->b1fold_fwd) hipFree(c->b1fold_fwd);
   if (c->small) hipFree(c->small);
   if (c->pinned) hipHostFree(c->pinned);
-  if (c->stage_ev) hipEventDestroy(c->stage_ev);
-  for (hipEvent_t e : c->dh_ev)
-    if (e) hipEventDestroy(e);
-  if (c->ev_fork) hipEventDestroy(c->ev_fork);
-  for (hipEvent_t e : c->ev_join) hipEventDestroy(e);
-  for (hipStream_t s2 : c->aux_streams) hipStreamDestroy(s2);
-  for (hipEvent_t e : c->ev_gru) hipEventDestroy(e);
-  if (c->gru_stream) hipStreamDestroy(c->gru_stream);
+  c->dh.destroy();
+  c->side.destroy();
   for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
   hipStreamDestroy(c->own_stream);
   delete c;
@@ -140,87 +156,86 @@ extern "C" int nlc_set_option(nlc_ctx* c, const char* name, double value) {
   const std::string n(name);
   if (n == "rollout_variant") {
     if (value < 0 || value > 3) return fail(c, NLC_ERR_BAD_ARG, "rollout_variant must be 0 (auto), 1, 2 or 3");
-    c->opt_rollout_variant = (int)value;
-    c->fused_lost = false;  // an explicit choice re-arms the fused body after a timeout
+    c->opt.rollout_variant = (int)value;
+    c->fused.rearm();
   } else if (n == "horizon_chunks") {
     if (value < 1 || value > 8 || value != (int)value) return fail(c, NLC_ERR_BAD_ARG, "horizon_chunks must be 1 .. 8");
-    c->opt_horizon_chunks = (int)value;
+    c->opt.horizon_chunks = (int)value;
   } else if (n == "dehoog_gru_chunks") {
     if (value < 0 || value > 8 || value != (int)value) return fail(c, NLC_ERR_BAD_ARG, "dehoog_gru_chunks must be 0 .. 8");
-    c->opt_dehoog_gru_chunks = (int)value;
+    c->opt.dehoog_gru_chunks = (int)value;
   } else if (n == "dehoog_gru_lds_pad") {
     if (value < 0 || value > 120000) return fail(c, NLC_ERR_BAD_ARG, "dehoog_gru_lds_pad must be in 0 .. 120000 bytes");
-    c->opt_dehoog_gru_lds_pad = (int)value;
+    c->opt.dehoog_gru_lds_pad = (int)value;
   } else if (n == "dehoog_chain") {
     if (value != -1 && value != 0 && value != 1 && value != 2) return fail(c, NLC_ERR_BAD_ARG, "dehoog_chain must be -1 (auto), 0, 1 or 2");
-    c->opt_dehoog_chain = (int)value;
+    c->opt.dehoog_chain = (int)value;
   } else if (n == "dehoog_chain_phases") {
     if (value != 1 && value != 2 && value != 3) return fail(c, NLC_ERR_BAD_ARG, "dehoog_chain_phases must be 1, 2 or 3");
-    c->opt_dehoog_chain_phases = (int)value;
+    c->opt.dehoog_chain_phases = (int)value;
   } else if (n == "dehoog_streams") {
     if (value < 0 || value > 4 || value != (int)value) return fail(c, NLC_ERR_BAD_ARG, "dehoog_streams must be 0 (auto), 1, 2, 3 or 4");
-    c->opt_dehoog_streams = (int)value;
+    c->opt.dehoog_streams = (int)value;
   } else if (n == "fused_tile_step_ratio") {
     if (value < 0 || value > 64) return fail(c, NLC_ERR_BAD_ARG, "fused_tile_step_ratio must be in 0 .. 64 (0 = static schedule)");
-    c->opt_fused_tile_step_ratio = value;
+    c->opt.fused.tile_step_ratio = value;
   } else if (n == "host_spin") {
     if (value != 0 && value != 1 && value != 2) return fail(c, NLC_ERR_BAD_ARG, "host_spin must be 0, 1 or 2");
-    c->opt_host_spin = (int)value;
-    c->wait_hist_n = c->wait_hist_at = 0;
-    c->nap_margin_us = 0.0;
+    c->opt.host_spin = (int)value;
+    c->wait.reset();
   } else if (n == "host_spin_margin_us") {
     if (value < 0 || value > 1.0e6) return fail(c, NLC_ERR_BAD_ARG, "host_spin_margin_us must be in 0 .. 1e6");
-    c->opt_host_spin_margin_us = value;
+    c->opt.host_spin_margin_us = value;
   } else if (n == "fused_blocks_per_cu") {
     if (value != 0 && value != 3 && value != 4) return fail(c, NLC_ERR_BAD_ARG, "fused_blocks_per_cu must be 0 (auto), 3 or 4");
-    c->opt_fused_blocks_per_cu = (int)value;
+    c->opt.fused.blocks_per_cu = (int)value;
   } else if (n == "fused_inline") {
     if (value < 0 || value > 3) return fail(c, NLC_ERR_BAD_ARG, "fused_inline must be 0, 1 (= 3), or the bit mask 1 weights | 2 sampling");
-    c->opt_fused_inline = (int)value == 1 ? 3 : (int)value;
+    c->opt.fused_inline = (int)value == 1 ? 3 : (int)value;
   } else if (n == "fused_spin_limit") {
     if (value < 1 || value > 4.0e9) return fail(c, NLC_ERR_BAD_ARG, "fused_spin_limit must be in 1 .. 4e9");
-    c->opt_fused_spin_limit = (int64_t)value;
+    c->opt.fused_spin_limit = (int64_t)value;
   } else if (n == "linear_fused") {
-    c->opt_linear_fused = value != 0.0;
+    c->opt.linear_fused = value != 0.0;
   } else if (n == "test_lin_coeff_scale") {
-    c->opt_test_lin_coeff_scale = value;
+    c->opt.test_lin_coeff_scale = value;
     c->has_mppi = false;  // folded at nlc_mppi_configure
   } else if (n == "fused_keep_sync") {
-    c->opt_fused_keep_sync = value != 0.0;
+    c->opt.fused_keep_sync = value != 0.0;
   } else if (n == "fused_test_drop_tile") {
     if (value < -1) return fail(c, NLC_ERR_BAD_ARG, "fused_test_drop_tile must be >= -1");
-    c->opt_fused_test_drop_tile = (int)value;
+    c->opt.fused_test_drop_tile = (int)value;
   } else if (n == "fused_roll_cap") {
     if (value < 0) return fail(c, NLC_ERR_BAD_ARG, "fused_roll_cap must be >= 0 (0 = auto)");
-    c->opt_fused_roll_cap = (int)value;
+    c->opt.fused.roll_cap = (int)value;
   } else if (n == "fused_chain_first_tiles") {
     if (value < -1 || value > 64) return fail(c, NLC_ERR_BAD_ARG, "fused_chain_first_tiles must be in -1..64 (-1 = auto)");
-    c->opt_fused_chain_first_tiles = (int)value;
+    c->opt.fused.chain_first_tiles = (int)value;
   } else if (n == "fused_partner_tiles") {
     if (value < -2 || value > 64) return fail(c, NLC_ERR_BAD_ARG, "fused_partner_tiles must be in -2..64 (-2 = auto, -1 = never)");
-    c->opt_fused_partner_tiles = (int)value;
+    c->opt.fused.partner_tiles = (int)value;
   } else if (n == "repfunc_split") {
     if (value != 0 && value != 1) return fail(c, NLC_ERR_BAD_ARG, "repfunc_split must be 0 or 1");
-    c->opt_repfunc_split = (int)value;
+    c->opt.repfunc_split = (int)value;
   } else if (n == "gru_coop") {
     if (value != 0 && value != 1 && value != -1) return fail(c, NLC_ERR_BAD_ARG, "gru_coop must be -1 (auto), 0 or 1");
-    c->opt_gru_coop = (int)value;
+    c->opt.gru_coop = (int)value;
   } else if (n == "gru_gemm") {
     // 0: FP64 MFMAs (default); 1: the encoder's hidden-state GEMMs as int8-sliced fixed-point products (kernels_gru_i8.hip;
     // hidden_units = 128: the stand-alone encoder launches that take the wave-sized form; the one-launch planner body keeps its FP64
     // encoder role)
     if (value != 0 && value != 1) return fail(c, NLC_ERR_BAD_ARG, "gru_gemm must be 0 (FP64 MFMA) or 1 (int8-sliced)");
-    c->opt_gru_gemm = (int)value;
+    c->opt.gru_gemm = (int)value;
     if (c->has_model) c->gru.use_i8 = (c->gru.i8_stream != nullptr && value == 1) ? 1 : 0;
   } else if (n == "dbg_gap_us") {
     if (value < 0 || value > 1.0e5) return fail(c, NLC_ERR_BAD_ARG, "dbg_gap_us must be in 0 .. 1e5");
-    c->opt_dbg_gap_us = value;
+    c->opt.dbg_gap_us = value;
   } else if (n == "dbg_l2_mb") {
     if (value < 0 || value > 4096) return fail(c, NLC_ERR_BAD_ARG, "dbg_l2_mb must be in 0 .. 4096");
-    c->opt_dbg_l2_mb = value;
+    c->opt.dbg_l2_mb = value;
   } else if (n == "fused_max_samples") {
     if (value < 0) return fail(c, NLC_ERR_BAD_ARG, "fused_max_samples must be >= 0");
-    c->opt_fused_max_samples = (int64_t)value;
+    c->opt.fused_max_samples = (int64_t)value;
   } else {
     return fail(c, NLC_ERR_BAD_ARG, "unknown option: " + n);
   }
@@ -232,15 +247,15 @@ extern "C" int nlc_get_stat(nlc_ctx* c, const char* name, double* out) {
   if (!name || !out) return fail(c, NLC_ERR_BAD_ARG, "NULL stat name / out");
   const std::string n(name);
   if (n == "rollout_body") *out = (double)c->last_body;
-  else if (n == "fused_timeouts") *out = (double)c->fused_timeouts;
-  else if (n == "fused_fallbacks") *out = (double)c->fused_fallbacks;
-  else if (n == "fused_lost") *out = c->fused_lost ? 1.0 : 0.0;
-  else if (n == "last_giveup_command") *out = (double)c->last_giveup_command;
+  else if (n == "fused_timeouts") *out = (double)c->fused.timeouts;
+  else if (n == "fused_fallbacks") *out = (double)c->fused.fallbacks;
+  else if (n == "fused_lost") *out = c->fused.lost ? 1.0 : 0.0;
+  else if (n == "last_giveup_command") *out = (double)c->fused.last_giveup_command;
   else if (n == "commands") *out = (double)c->commands;
   else if (n == "comm_world") *out = c->comm ? (double)c->comm_world : 0.0;
   else if (n == "comm_rank") *out = c->comm ? (double)c->comm_rank : -1.0;
-  else if (n == "fused_blocks_per_cu") *out = (double)c->fused_blocks_per_cu;
-  else if (n == "fused_spin_limit") *out = (double)c->opt_fused_spin_limit;
+  else if (n == "fused_blocks_per_cu") *out = (double)c->fused.blocks_per_cu;
+  else if (n == "fused_spin_limit") *out = (double)c->opt.fused_spin_limit;
   else if (n == "model_nt3") *out = c->has_model ? (double)c->net.nt3 : 0.0;
   else if (n == "gru_gemm") *out = (c->has_model && c->gru.use_i8) ? 1.0 : 0.0;  // 1: the encoder launches run kernels_gru_i8.hip
   else if (n == "gru_i8_launches") *out = (double)nlc::gru_i8_launch_count();  // process-wide

@@ -158,7 +158,7 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   G.bo[0] = bo[0];
   G.bo[1] = bo[1];
   if (i8_ok) G.i8_stream = (const signed char*)(base + o_i8);
-  G.use_i8 = (i8_ok && c->opt_gru_gemm == 1) ? 1 : 0;  // (nlc_get_stat "gru_gemm" tells whether the option took)
+  G.use_i8 = (i8_ok && c->opt.gru_gemm == 1) ? 1 : 0;  // (nlc_get_stat "gru_gemm" tells whether the option took)
 
   NlNetArgs& N = c->net;
   N = NlNetArgs{};

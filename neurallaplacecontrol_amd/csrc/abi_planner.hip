@@ -61,25 +61,16 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
   NLC_HIP(c, hipSetDevice(c->device));
   const size_t un = (size_t)E * d->T * d->nu;
   for (int i = 0; i < 2; ++i) {
-    if (c->U[i]) hipFree(c->U[i]);
-    c->U[i] = nullptr;
-    NLC_HIP(c, hipMalloc((void**)&c->U[i], un * sizeof(double)));
+    if (int rc = hold_doubles(c, c->U[i], un)) return rc;
     // on the ctx's stream and waited for below: hipMemset runs asynchronously on the NULL stream, which is not
     // ordered against a non-blocking stream -- it could land after the nlc_mppi_set_U copy that follows configure
     NLC_HIP(c, hipMemsetAsync(c->U[i], 0, un * sizeof(double), c->stream));
   }
   NLC_HIP(c, hipStreamSynchronize(c->stream));
   c->ucur = 0;
-  if (c->small) hipFree(c->small);
-  c->small = nullptr;
-  NLC_HIP(c, hipMalloc((void**)&c->small, (un + 2 * (size_t)E) * sizeof(double)));
-  const size_t pin_need = (size_t)E * d->d + (size_t)E * d->B * d->nu + un + 8;
-  if (pin_need > c->pinned_n) {
-    if (c->pinned) hipHostFree(c->pinned);
-    c->pinned = nullptr;
-    NLC_HIP(c, hipHostMalloc((void**)&c->pinned, pin_need * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-    c->pinned_n = pin_need;
-  }
+  if (int rc = hold_doubles(c, c->small, un + 2 * (size_t)E)) return rc;
+  c->pin = plan::pin_layout(E, d->d, d->B, d->nu, d->T);
+  if (int rc = hold_pinned_doubles(c, c->pinned, c->pin.total, &c->pinned_n)) return rc;
   std::memset(c->pinned, 0, c->pinned_n * sizeof(double));
   c->pd = *d;
   c->pd.E = E;
@@ -96,10 +87,7 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
       for (int j = 0; j < 2 * S; ++j) acc += c->W1s_host[(size_t)r * 2 * S + j] * sph[j];
       bf[r] = acc;
     }
-    if (c->b1fold) hipFree(c->b1fold);
-    c->b1fold = nullptr;
-    NLC_HIP(c, hipMalloc((void**)&c->b1fold, h * sizeof(double)));
-    NLC_HIP(c, hipMemcpy(c->b1fold, bf.data(), h * sizeof(double), hipMemcpyHostToDevice));
+    if (int rc = hold_doubles(c, c->b1fold, bf.size(), bf.data())) return rc;
     if (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST) {
       // coefficient fragments of the LIN rollout instances: lane -> (dim = lane & 15, slot 4 g + (lane >> 4)), as Cp
       std::vector<double> tab;
@@ -113,27 +101,19 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
           cp[(size_t)g * 64 + lane] = tab[2 * S + el.second] / c->tn;
           cp[(size_t)(ng + g) * 64 + lane] = -tab[3 * S + el.second] / c->tn;
         }
-      if (c->opt_test_lin_coeff_scale != 1.0) {  // tests only: the sweep's tolerance must catch this
+      if (c->opt.test_lin_coeff_scale != 1.0) {  // tests only: the sweep's tolerance must catch this
         size_t at = 0;
         for (size_t i = 0; i < cp.size(); ++i)
           if (std::fabs(cp[i]) > std::fabs(cp[at])) at = i;
-        cp[at] *= c->opt_test_lin_coeff_scale;  // (the largest weight: Stehfest's span many orders of magnitude)
+        cp[at] *= c->opt.test_lin_coeff_scale;  // (the largest weight: Stehfest's span many orders of magnitude)
       }
-      if (c->cp_lin) hipFree(c->cp_lin);
-      c->cp_lin = nullptr;
-      NLC_HIP(c, hipMalloc((void**)&c->cp_lin, cp.size() * sizeof(double)));
-      NLC_HIP(c, hipMemcpy(c->cp_lin, cp.data(), cp.size() * sizeof(double), hipMemcpyHostToDevice));
+      if (int rc = hold_doubles(c, c->cp_lin, cp.size(), cp.data())) return rc;
     }
   }
   c->has_mppi = true;
-  c->dh_n = 0;  // de Hoog chain form: measured again for the new problem
-  c->dh_choice = c->dh_pending = -1;
-  for (auto& v : c->dh_ms) v[0] = v[1] = 1e30f;
-  c->wait_hist_n = c->wait_hist_at = 0;  // host_spin 2: a new problem size, a new wait to predict
-  c->nap_margin_us = 0.0;
-  c->sync_clean_ws = nullptr;
-  c->sync_dirty = false;
-  c->last.valid = false;
+  c->dh.reset();
+  c->wait.reset();
+  c->fused.new_problem();
   return NLC_OK;
   NLC_GUARD_END(c)
 }
@@ -144,7 +124,7 @@ namespace host {
 // at the widths of with_width in nlc_kernels.h) instead of the staged path
 bool linear_on_rollout_kernels(const nlc_ctx* c) {
   return c->has_model && (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST) &&
-         (c->md.h == 64 || c->md.h == 128 || c->md.h == 256) && c->opt_linear_fused != 0;
+         (c->md.h == 64 || c->md.h == 128 || c->md.h == 256) && c->opt.linear_fused != 0;
 }
 
 WsLayout ws_layout(const nlc_ctx* c) {
@@ -180,24 +160,30 @@ WsLayout ws_layout(const nlc_ctx* c) {
   return w;
 }
 
-// pinned host word a rollout workgroup of the fused planner body sets when it gives up waiting for an encoder tile
-double* fused_timeout_word(nlc_ctx* c) {
-  const nlc_mppi_desc& d = c->pd;
-  return c->pinned + (size_t)d.E * d.d + (size_t)d.E * d.B * d.nu + (size_t)d.E * d.T * d.nu;
-}
-bool fused_gave_up(nlc_ctx* c) {
-  unsigned* w = reinterpret_cast<unsigned*>(fused_timeout_word(c));
-  if (*w == 0u) return false;
-  *w = 0u;
-  return true;
-}
-// pinned word merge_kernel sets when a gathered partial row is marked invalid (kPartialInvalidEta): read and cleared here
-unsigned* merge_status_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(fused_timeout_word(c) + 2); }
-bool merge_reported_invalid(nlc_ctx* c) {
-  unsigned* w = merge_status_word(c);
+// Give-up bookkeeping of the fused body, once per look at the pinned block: reads and clears the word a rollout workgroup of
+// the fused body sets when it gives up waiting for an encoder tile (`lost_here`) and the word merge_kernel sets when a gathered
+// partial row is marked invalid (kPartialInvalidEta; `marked`: some rank gave up).  A give-up here puts the ctx on the
+// two-launch body.  `command`: index of the command the words speak of; `count_marked`: a row another rank marked is a give-up
+// this ctx saw as well (nlc_mppi_finish, which then re-runs the command; nlc_mppi_rollout records only its own).
+struct GiveUp {
+  bool lost_here, marked;
+  bool any() const { return lost_here || marked; }
+};
+static bool take_word(unsigned* w) {
   if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == 0u) return false;
   *w = 0u;
   return true;
+}
+static GiveUp take_give_up(nlc_ctx* c, int64_t command, bool count_marked) {
+  GiveUp g{};
+  g.lost_here = take_word(pin_giveup_word(c));
+  g.marked = take_word(pin_merge_status_word(c));
+  if (g.lost_here) {
+    c->fused.lost = true;
+    c->fused.timeouts += 1;
+  }
+  if (g.lost_here || (g.marked && count_marked)) c->fused.last_giveup_command = command;
+  return g;
 }
 
 WeightArgs make_weight_args(nlc_ctx* c, const nlc_mppi_buffers* buf) {
@@ -266,6 +252,63 @@ SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call) {
   a.cost_total = call.buf->cost_total;
   return a;
 }
+
+// the command's sampling / bounding, apart from the inline inputs; c->U[c->ucur] is the sequence BEFORE the shift
+PerturbArgs perturb_args(const nlc_ctx* c, const nlc_mppi_buffers* buf, int rng, uint64_t seed, uint64_t counter) {
+  const nlc_mppi_desc& d = c->pd;
+  PerturbArgs p{};
+  p.K = d.K * d.E;  // all local samples, episode-major
+  p.Kep = d.K;
+  p.E = d.E;
+  p.K_global = d.K_global;
+  p.k_offset = d.k_offset;
+  p.T = d.T;
+  p.nu = d.nu;
+  p.U_old = c->U[c->ucur];
+  p.U_new = c->U[c->ucur ^ 1];
+  p.noise = buf->noise;
+  p.perturbed = buf->perturbed;
+  p.actions = buf->actions;
+  p.u_scale = d.u_scale;
+  p.has_bounds = d.has_bounds;
+  p.sample_null_action = d.sample_null_action;
+  p.rng = rng;
+  for (int i = 0; i < NLC_MAX_NU; ++i) {
+    p.u_min[i] = d.u_min[i];
+    p.u_max[i] = d.u_max[i];
+    p.u_init[i] = d.u_init[i];
+    p.mu[i] = d.noise_mu[i];
+  }
+  for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) p.chol[i] = d.noise_chol[i];
+  p.seed = seed;
+  p.counter = counter;
+  return p;
+}
+
+// phase 2 over the partial rows of G ranks; c->U[c->ucur] is the shifted sequence.  The pinned action, the sequence word and
+// the sync block's clean-up are the caller's decisions.
+MergeArgs merge_args(nlc_ctx* c, const nlc_mppi_buffers* buf, const double* gathered, int G, int rank) {
+  const nlc_mppi_desc& d = c->pd;
+  MergeArgs m{};
+  m.Kep = d.K;
+  m.E = d.E;
+  m.T = d.T;
+  m.nu = d.nu;
+  m.G = G;
+  m.rank = rank;
+  m.u_per_command = d.u_per_command;
+  m.lambda_ = d.lambda_;
+  m.u_scale = d.u_scale;
+  m.gathered = gathered;
+  m.U = c->U[c->ucur];
+  m.cost_nz = buf->cost_nz;
+  m.omega = buf->omega;
+  m.action = buf->action ? buf->action : c->small;
+  m.beta_eta = c->small + (size_t)d.E * d.T * d.nu;
+  m.cost = buf->cost_total;
+  m.status_pinned = pin_merge_status_word(c);
+  return m;
+}
 }  // namespace host
 }  // namespace nlc
 
@@ -296,8 +339,97 @@ extern "C" int nlc_mppi_get_U(nlc_ctx* c, double* U) {
   return NLC_OK;
 }
 
+// The command's state(s) and action buffer(s) into the workspace (dynamics the library runs; not on a replay), or
+// *inline_inputs: they ride in the perturb kernel's arguments
+static int stage_inputs(nlc_ctx* c, RolloutCall& call, const double* state, const double* abuf_host, bool* inline_inputs) {
+  const nlc_mppi_desc& d = c->pd;
+  const int state_per_sample = call.state_per_sample;
+  double* state_dev = call.state_dev;
+  double* abuf_dev = call.abuf_dev;
+  if (d.E > 1) {
+    // batched episodes: the (E,d) states and (E,B,nu) action buffers usually live on the device already (a device-side
+    // env loop); hipMemcpyDefault takes either kind of pointer
+    const size_t ns = (size_t)(state_per_sample ? call.KE : d.E) * d.d;
+    NLC_HIP(c, hipMemcpyAsync(state_dev, state, ns * sizeof(double), hipMemcpyDefault, c->stream));
+    NLC_HIP(c, hipMemcpyAsync(abuf_dev, abuf_host, (size_t)d.E * d.B * d.nu * sizeof(double), hipMemcpyDefault,
+                              c->stream));
+    // a caller-owned HOST buffer may be a temporary: the copies out of it must have completed before we return
+    if (!is_device_ptr(state) || !is_device_ptr(abuf_host)) NLC_HIP(c, hipStreamSynchronize(c->stream));
+  } else if (!state_per_sample && d.B * d.nu <= kMaxInlineAbuf) {
+    *inline_inputs = true;  // state and action_buffer travel in the shift kernel's arguments (below)
+  } else {
+    // small inputs go through pinned staging (truly asynchronous copies).  The staging slots are rewritten
+    // only after the previous command's copies out of them have completed (stage_ev).
+    if (c->side.stage_ev) NLC_HIP(c, hipEventSynchronize(c->side.stage_ev));
+    double* pin_state = c->pinned + c->pin.state;
+    double* pin_abuf = c->pinned + c->pin.abuf;
+    std::memcpy(pin_abuf, abuf_host, (size_t)d.B * d.nu * sizeof(double));
+    if (state_per_sample) {
+      // (K, d) from caller-owned pageable memory: wait for the copy, the source may be a temporary
+      NLC_HIP(c, hipMemcpyAsync(state_dev, state, (size_t)d.K * d.d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      NLC_HIP(c, hipStreamSynchronize(c->stream));
+    } else {
+      std::memcpy(pin_state, state, (size_t)d.d * sizeof(double));
+      NLC_HIP(c, hipMemcpyAsync(state_dev, pin_state, (size_t)d.d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    NLC_HIP(c, hipMemcpyAsync(abuf_dev, pin_abuf, (size_t)d.B * d.nu * sizeof(double), hipMemcpyHostToDevice,
+                              c->stream));
+    if (!c->side.stage_ev) NLC_HIP(c, hipEventCreateWithFlags(&c->side.stage_ev, hipEventDisableTiming));
+    NLC_HIP(c, hipEventRecord(c->side.stage_ev, c->stream));
+  }
+  return NLC_OK;
+}
+
+// the rollout of the baseline dynamics: NODE, Delta-t RNN (encode launch + rollout launch), oracle
+static int rollout_baseline(nlc_ctx* c, RolloutCall& call) {
+  const nlc_mppi_desc& d = c->pd;
+  c->last_body = d.dynamics == NLC_DYN_NODE ? 8 : (d.dynamics == NLC_DYN_DTRNN ? 7 : 6);
+  const SampleCostArgs sc = sample_cost_args(c, call);
+  if (d.dynamics == NLC_DYN_NODE) {
+    NodeRolloutArgs r{sc};
+    r.net = c->node;
+    r.net.nsub = node_substeps(d.ts_pred / c->nd.time_div, c->nd.step_size, r.net.hsub, 8);
+    ProfScope ps(c, "node_rollout_kernel");
+    NLC_HIP(c, launch_node_rollout(r, c->node_ht, c->stream));
+  } else if (d.dynamics == NLC_DYN_DTRNN) {
+    RnnArgs g = c->rnn;
+    g.mode = 1;
+    g.perturbed = call.buf->perturbed;
+    g.abuf = call.abuf_dev;
+    g.u_scale = d.u_scale;
+    g.T = d.T;
+    g.B = d.B;
+    g.Kep = d.K;
+    g.K = call.KE;
+    g.N = call.KE * d.T;
+    g.out = call.ws + call.w.rq;
+    {
+      ProfScope ps(c, "rnn_encode_kernel");
+      NLC_HIP(c, launch_rnn_encode(g, c->rd.hidden, c->stream));
+    }
+    RnnRolloutArgs r{sc};
+    r.head = c->rnn_head;
+    r.q = g.out;
+    r.ts = d.ts_pred;
+    ProfScope ps(c, "rnn_rollout_kernel");
+    NLC_HIP(c, launch_rnn_rollout(r, c->stream));
+  } else {
+    OracleRolloutArgs r{sc};
+    r.B = d.B;
+    r.d = d.d;
+    r.delay = d.delay;
+    r.friction = d.friction;
+    r.dyn_env = d.env;
+    r.abuf = call.abuf_dev;
+    r.ts = d.ts_pred;
+    ProfScope ps(c, "oracle_rollout_kernel");
+    NLC_HIP(c, launch_oracle_rollout(r, c->stream));
+  }
+  return NLC_OK;
+}
+
 // Phase 1 of a command.  `replay`: the command's fused launch gave up (hand-off timeout) -- run it again on the two-launch
-// body from the inputs kept in c->last / still staged in the workspace (nlc_mppi_finish).
+// body from the inputs kept in c->fused.last / still staged in the workspace (nlc_mppi_finish).
 static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_sample, const double* abuf_host,
                              const nlc_mppi_buffers* buf, int rng, uint64_t seed, uint64_t counter, bool replay) {
   NLC_GUARD_BEGIN
@@ -312,13 +444,8 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
   if (!replay) c->commands += 1;
   c->last_body = 0;
   if (!replay) {  // (a device-resident caller never synchronised inside nlc_mppi_finish)
-    const bool lost_here = fused_gave_up(c), marked = merge_reported_invalid(c);
-    if (lost_here) {
-      c->fused_lost = true;  // from here on the two-launch body
-      c->fused_timeouts += 1;
-      c->last_giveup_command = c->commands - 2;  // the command before this one
-    }
-    if (lost_here || marked)  // `marked` is set on every rank of a sharded planner: they all fail here, none waits in a collective
+    // `marked` is set on every rank of a sharded planner: they all fail here, none waits in a collective
+    if (take_give_up(c, c->commands - 2 /* the command before this one */, false).any())
       return fail(c, NLC_ERR_HIP, "fused planner body: the PREVIOUS command timed out waiting inside the launch (on this or "
                                   "another rank; its action was NaN and U was left alone); later commands run the two-launch body");
   }
@@ -334,67 +461,13 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
   call.replay = replay;
   double* state_dev = call.state_dev;
   double* abuf_dev = call.abuf_dev;
-  const int64_t KE = call.KE;
   bool inline_inputs = false;
-  if (replay) {
-    inline_inputs = c->last.inline_inputs;  // otherwise the inputs are still staged in the workspace
-  } else if (!external && d.E > 1) {
-    // batched episodes: the (E,d) states and (E,B,nu) action buffers usually live on the device already (a device-side
-    // env loop); hipMemcpyDefault takes either kind of pointer
-    const size_t ns = (size_t)(state_per_sample ? KE : d.E) * d.d;
-    NLC_HIP(c, hipMemcpyAsync(state_dev, state, ns * sizeof(double), hipMemcpyDefault, c->stream));
-    NLC_HIP(c, hipMemcpyAsync(abuf_dev, abuf_host, (size_t)d.E * d.B * d.nu * sizeof(double), hipMemcpyDefault,
-                              c->stream));
-    // a caller-owned HOST buffer may be a temporary: the copies out of it must have completed before we return
-    if (!is_device_ptr(state) || !is_device_ptr(abuf_host)) NLC_HIP(c, hipStreamSynchronize(c->stream));
-  } else if (!external && !state_per_sample && d.B * d.nu <= kMaxInlineAbuf) {
-    inline_inputs = true;  // state and action_buffer travel in the shift kernel's arguments (below)
-  } else if (!external) {
-    // small inputs go through pinned staging (truly asynchronous copies).  The staging slots are rewritten
-    // only after the previous command's copies out of them have completed (stage_ev).
-    if (c->stage_ev) NLC_HIP(c, hipEventSynchronize(c->stage_ev));
-    double* pin_state = c->pinned;
-    double* pin_abuf = c->pinned + d.d;
-    std::memcpy(pin_abuf, abuf_host, (size_t)d.B * d.nu * sizeof(double));
-    if (state_per_sample) {
-      // (K, d) from caller-owned pageable memory: wait for the copy, the source may be a temporary
-      NLC_HIP(c, hipMemcpyAsync(state_dev, state, (size_t)d.K * d.d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      NLC_HIP(c, hipStreamSynchronize(c->stream));
-    } else {
-      std::memcpy(pin_state, state, (size_t)d.d * sizeof(double));
-      NLC_HIP(c, hipMemcpyAsync(state_dev, pin_state, (size_t)d.d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    NLC_HIP(c, hipMemcpyAsync(abuf_dev, pin_abuf, (size_t)d.B * d.nu * sizeof(double), hipMemcpyHostToDevice,
-                              c->stream));
-    if (!c->stage_ev) NLC_HIP(c, hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
-    NLC_HIP(c, hipEventRecord(c->stage_ev, c->stream));
-  }
+  if (replay)
+    inline_inputs = c->fused.last.inline_inputs;  // otherwise the inputs are still staged in the workspace
+  else if (!external)
+    if (int rc = stage_inputs(c, call, state, abuf_host, &inline_inputs)) return rc;
   PerturbArgs& p = call.p;
-  p.K = KE;
-  p.Kep = d.K;
-  p.E = d.E;
-  p.K_global = d.K_global;
-  p.k_offset = d.k_offset;
-  p.T = d.T;
-  p.nu = d.nu;
-  p.U_old = c->U[c->ucur];
-  p.U_new = c->U[c->ucur ^ 1];
-  p.noise = buf->noise;
-  p.perturbed = buf->perturbed;
-  p.actions = buf->actions;
-  p.u_scale = d.u_scale;
-  p.has_bounds = d.has_bounds;
-  p.sample_null_action = d.sample_null_action;
-  p.rng = rng;
-  for (int i = 0; i < NLC_MAX_NU; ++i) {
-    p.u_min[i] = d.u_min[i];
-    p.u_max[i] = d.u_max[i];
-    p.u_init[i] = d.u_init[i];
-    p.mu[i] = d.noise_mu[i];
-  }
-  for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) p.chol[i] = d.noise_chol[i];
-  p.seed = seed;
-  p.counter = counter;
+  p = perturb_args(c, buf, rng, seed, counter);
   if (inline_inputs) {
     p.n_state_in = d.d;
     p.n_abuf_in = d.B * d.nu;
@@ -404,7 +477,7 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
     std::memcpy(p.abuf_in, abuf_host, (size_t)d.B * d.nu * sizeof(double));
   }
   if (!replay) {
-    nlc_ctx::LastCommand& L = c->last;
+    FusedState::LastCommand& L = c->fused.last;
     L.valid = !external;
     L.inline_inputs = inline_inputs;
     L.fused = false;
@@ -430,48 +503,7 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
     return NLC_OK;  // the caller runs the horizon loop, then nlc_mppi_weights
   }
   if (d.dynamics == NLC_DYN_NL) return rollout_nl(c, call);
-  c->last_body = d.dynamics == NLC_DYN_NODE ? 8 : (d.dynamics == NLC_DYN_DTRNN ? 7 : 6);
-  const SampleCostArgs sc = sample_cost_args(c, call);
-  if (d.dynamics == NLC_DYN_NODE) {
-    NodeRolloutArgs r{sc};
-    r.net = c->node;
-    r.net.nsub = node_substeps(d.ts_pred / c->nd.time_div, c->nd.step_size, r.net.hsub, 8);
-    ProfScope ps(c, "node_rollout_kernel");
-    NLC_HIP(c, launch_node_rollout(r, c->node_ht, c->stream));
-  } else if (d.dynamics == NLC_DYN_DTRNN) {
-    RnnArgs g = c->rnn;
-    g.mode = 1;
-    g.perturbed = buf->perturbed;
-    g.abuf = abuf_dev;
-    g.u_scale = d.u_scale;
-    g.T = d.T;
-    g.B = d.B;
-    g.Kep = d.K;
-    g.K = KE;
-    g.N = KE * d.T;
-    g.out = call.ws + call.w.rq;
-    {
-      ProfScope ps(c, "rnn_encode_kernel");
-      NLC_HIP(c, launch_rnn_encode(g, c->rd.hidden, c->stream));
-    }
-    RnnRolloutArgs r{sc};
-    r.head = c->rnn_head;
-    r.q = g.out;
-    r.ts = d.ts_pred;
-    ProfScope ps(c, "rnn_rollout_kernel");
-    NLC_HIP(c, launch_rnn_rollout(r, c->stream));
-  } else {
-    OracleRolloutArgs r{sc};
-    r.B = d.B;
-    r.d = d.d;
-    r.delay = d.delay;
-    r.friction = d.friction;
-    r.dyn_env = d.env;
-    r.abuf = abuf_dev;
-    r.ts = d.ts_pred;
-    ProfScope ps(c, "oracle_rollout_kernel");
-    NLC_HIP(c, launch_oracle_rollout(r, c->stream));
-  }
+  if (int rc = rollout_baseline(c, call)) return rc;
   return d.cost_external ? NLC_OK : run_weights(c, buf);
   NLC_GUARD_END(c)
 }
@@ -502,12 +534,7 @@ int native_all_gather(nlc_ctx* c, const nlc_mppi_buffers* buf, int G, int rank, 
   if (G != c->comm_world || rank != c->comm_rank) return fail(c, NLC_ERR_BAD_ARG, "G / rank differ from the communicator's");
   if (!buf->partials) return fail(c, NLC_ERR_BAD_ARG, "NULL buf->partials");
   const size_t per_rank = (size_t)d.E * (size_t)(2 + d.T * d.nu);
-  if (c->comm_gather_n < per_rank * (size_t)G) {
-    if (c->comm_gather) NLC_HIP(c, hipFree(c->comm_gather));
-    c->comm_gather = nullptr;
-    NLC_HIP(c, hipMalloc((void**)&c->comm_gather, per_rank * (size_t)G * sizeof(double)));
-    c->comm_gather_n = per_rank * (size_t)G;
-  }
+  if (int rc = hold_doubles(c, c->comm_gather, per_rank * (size_t)G, nullptr, &c->comm_gather_n)) return rc;
   ProfScope ps(c, "rccl_all_gather");
   const int rc = rccl()->AllGather(buf->partials, c->comm_gather, per_rank, kNcclFloat64, c->comm, c->stream);
   if (rc != 0) return fail(c, NLC_ERR_COMM, std::string("ncclAllGather: ") + rccl()->GetErrorString(rc));
@@ -528,13 +555,13 @@ inline double now_us() {
 // profiling: hipStreamSynchronize (which, measured, busy-waits as well: profiles/r4_host_spin_contention.json).
 int wait_for_action(nlc_ctx* c, bool spin, const unsigned long long* seq_word) {
   if (spin) {
-    const unsigned long long want = c->host_seq;
+    const unsigned long long want = c->wait.seq;
     const double t0 = now_us();
-    if (c->opt_host_spin == 2 && c->wait_hist_n >= 2) {
-      double pred = c->wait_hist_us[0];
-      for (int i = 1; i < c->wait_hist_n; ++i) pred = pred < c->wait_hist_us[i] ? pred : c->wait_hist_us[i];
-      double margin = pred * 0.15 > c->opt_host_spin_margin_us ? pred * 0.15 : c->opt_host_spin_margin_us;
-      if (c->nap_margin_us > margin) margin = c->nap_margin_us;  // grown by earlier oversleeps (below)
+    if (c->opt.host_spin == 2 && c->wait.hist_n >= 2) {
+      double pred = c->wait.hist_us[0];
+      for (int i = 1; i < c->wait.hist_n; ++i) pred = pred < c->wait.hist_us[i] ? pred : c->wait.hist_us[i];
+      double margin = pred * 0.15 > c->opt.host_spin_margin_us ? pred * 0.15 : c->opt.host_spin_margin_us;
+      if (c->wait.nap_margin_us > margin) margin = c->wait.nap_margin_us;  // grown by earlier oversleeps (below)
       const double nap = pred - margin;
       if (nap >= 50.0 && __atomic_load_n(seq_word, __ATOMIC_ACQUIRE) != want) {
         timespec req;
@@ -544,17 +571,17 @@ int wait_for_action(nlc_ctx* c, bool spin, const unsigned long long* seq_word) {
         // the timer's wake-up latency is the host's, not ours to know: if the action was already there when we woke, the nap
         // was too long -- wake earlier from now on; while it is not, drift back towards the configured margin
         if (__atomic_load_n(seq_word, __ATOMIC_ACQUIRE) == want)
-          c->nap_margin_us = margin * 1.5 + 20.0;
+          c->wait.nap_margin_us = margin * 1.5 + 20.0;
         else
-          c->nap_margin_us = margin * 0.995;
+          c->wait.nap_margin_us = margin * 0.995;
       }
     }
     for (unsigned long long it = 0; it < 400000000ull; ++it) {  // ~ seconds: then fall back to the runtime's wait
       // acquire: the action words the kernel stored BEFORE the sequence number are read after it
       if (__atomic_load_n(seq_word, __ATOMIC_ACQUIRE) == want) {
-        c->wait_hist_us[c->wait_hist_at] = now_us() - t0;
-        c->wait_hist_at = (c->wait_hist_at + 1) % 8;
-        if (c->wait_hist_n < 8) c->wait_hist_n += 1;
+        c->wait.hist_us[c->wait.hist_at] = now_us() - t0;
+        c->wait.hist_at = (c->wait.hist_at + 1) % 8;
+        if (c->wait.hist_n < 8) c->wait.hist_n += 1;
         return NLC_OK;
       }
 #if defined(__x86_64__)
@@ -581,37 +608,20 @@ extern "C" int nlc_mppi_finish(nlc_ctx* c, const double* gathered, int G, int ra
   const bool native = gathered == nullptr;
   if (native)
     if (int rc = native_all_gather(c, buf, G, rank, &gathered)) return rc;
-  MergeArgs m{};
-  m.Kep = d.K;
-  m.E = d.E;
-  m.T = d.T;
-  m.nu = d.nu;
-  m.G = G;
-  m.rank = rank;
-  m.u_per_command = d.u_per_command;
-  m.lambda_ = d.lambda_;
-  m.u_scale = d.u_scale;
-  m.gathered = gathered;
-  m.U = c->U[c->ucur];
-  m.cost_nz = buf->cost_nz;
-  m.omega = buf->omega;
-  m.action = buf->action ? buf->action : c->small;
-  m.beta_eta = c->small + (size_t)d.E * d.T * d.nu;
   if (!buf->cost_total) return fail(c, NLC_ERR_BAD_ARG, "NULL buf->cost_total");
-  m.cost = buf->cost_total;
+  MergeArgs m = merge_args(c, buf, gathered, G, rank);
   // the returned action is stored by the kernel straight into pinned (host-coherent) memory: the only thing left
   // on the host's critical path is the wait for it
-  double* pin_act = c->pinned + (size_t)d.E * d.d + (size_t)d.E * d.B * d.nu;
+  double* pin_act = c->pinned + c->pin.action;
   m.action_pinned = action_host ? pin_act : nullptr;
-  m.status_pinned = merge_status_word(c);
-  unsigned long long* seq_word = reinterpret_cast<unsigned long long*>(fused_timeout_word(c) + 1);
-  const bool spin = action_host && c->opt_host_spin && d.E == 1 && !c->profiling;
+  unsigned long long* seq_word = pin_seq_word(c);
+  const bool spin = action_host && c->opt.host_spin && d.E == 1 && !c->profiling;
   auto launch_merge_now = [&]() -> int {
     if (spin) {
       m.seq_pinned = seq_word;
-      m.seq = ++c->host_seq;
+      m.seq = ++c->wait.seq;
     }
-    if (c->sync_dirty && buf->workspace && !c->opt_fused_keep_sync) {
+    if (c->fused.sync_dirty && buf->workspace && !c->opt.fused_keep_sync) {
       // last launch of the command: leave the fused body's tickets / flags zeroed for the next one
       m.zero_words = reinterpret_cast<unsigned*>((double*)buf->workspace + ws_layout(c).sync);
       m.n_zero_words = (int64_t)fused_sync_words(d.T, d.K * d.E);
@@ -619,8 +629,8 @@ extern "C" int nlc_mppi_finish(nlc_ctx* c, const double* gathered, int G, int ra
     ProfScope ps(c, "merge_kernel");
     NLC_HIP(c, launch_merge(m, c->stream));
     if (m.zero_words) {
-      c->sync_clean_ws = buf->workspace;
-      c->sync_dirty = false;
+      c->fused.sync_clean_ws = buf->workspace;
+      c->fused.sync_dirty = false;
     }
     return NLC_OK;
   };
@@ -635,23 +645,17 @@ extern "C" int nlc_mppi_finish(nlc_ctx* c, const double* gathered, int G, int ra
   //     all-gather, so merge_kernel on EVERY rank has skipped the update and set the merge-status word.
   // Every rank therefore takes the same decision: re-run the command on the two-launch body from the inputs the ctx keeps
   // (the control sequence's ping-pong partner is untouched), gather again, merge again.
-  const bool lost_here = fused_gave_up(c);
-  const bool marked = merge_reported_invalid(c);
-  if (lost_here) {
-    c->fused_lost = true;
-    c->fused_timeouts += 1;
-  }
-  if (lost_here || marked) {
-    c->last_giveup_command = c->commands - 1;
-    if (G > 1 && !marked)  // (a sharded command whose weights were folded outside the launch: the peers cannot know)
+  const GiveUp gu = take_give_up(c, c->commands - 1 /* this command */, true);
+  if (gu.any()) {
+    if (G > 1 && !gu.marked)  // (a sharded command whose weights were folded outside the launch: the peers cannot know)
       return fail(c, NLC_ERR_HIP, "fused planner body: a workgroup timed out waiting inside the launch and the shard's partials "
                                   "were not marked; command lost (later commands run the two-launch body)");
-    if (d.cost_external || !c->last.valid || !buf->workspace || !buf->partials)
+    if (d.cost_external || !c->fused.last.valid || !buf->workspace || !buf->partials)
       return fail(c, NLC_ERR_HIP, "fused planner body: a workgroup timed out waiting inside the launch; command lost "
                                   "(later commands run the two-launch body)");
-    c->fused_fallbacks += 1;
+    c->fused.fallbacks += 1;
     c->ucur ^= 1;  // back to the control sequence before this command's shift
-    const nlc_ctx::LastCommand L = c->last;
+    const FusedState::LastCommand L = c->fused.last;
     if (int rc = mppi_rollout_impl(c, L.state_in, L.state_per_sample, L.abuf_in, buf, L.rng, L.seed, L.counter, true)) return rc;
     m.U = c->U[c->ucur];
     if (G == 1) {
@@ -666,7 +670,7 @@ extern "C" int nlc_mppi_finish(nlc_ctx* c, const double* gathered, int G, int ra
     }
     if (int rc = launch_merge_now()) return rc;
     if (int rc = wait_for_action(c, spin, seq_word)) return rc;
-    if (merge_reported_invalid(c)) return fail(c, NLC_ERR_STATE, "partials still marked invalid after the re-run");
+    if (take_word(pin_merge_status_word(c))) return fail(c, NLC_ERR_STATE, "partials still marked invalid after the re-run");
   }
   std::memcpy(action_host, pin_act, na * sizeof(double));
   return NLC_OK;

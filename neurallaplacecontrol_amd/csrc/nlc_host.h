@@ -24,6 +24,7 @@
 
 #include "nlc_kernels.h"
 #include "nlc_pack.h"
+#include "nlc_plan.h"
 
 namespace nlc {
 int nl_pick_nt3(int need);
@@ -47,6 +48,125 @@ struct DeviceArena {
     host.resize(off);
     host.insert(host.end(), v.begin(), v.end());
     return off;
+  }
+};
+
+// ---- the planner's state, by group (members of nlc_ctx)
+
+// nlc_set_option; defaults as documented in include/nlc.h
+struct PlannerOptions {
+  int rollout_variant = 0;          // 0 auto, 1 wave-per-tile, 2 latency-split (two launches), 3 fused one-launch body
+  int repfunc_split = 1;            // staged de Hoog planner: latency-split representation kernel (h = 128)
+  int gru_coop = -1;                // stand-alone GRU encodes: cooperative (one tile per workgroup) kernel 1 / 0, -1 auto
+  int gru_gemm = 0;                 // 1: encoder hidden-state GEMMs on the INT8 matrix pipe (kernels_gru_i8.hip), g == 64 only
+  int horizon_chunks = 1;           // Fourier planner, wave-per-tile body (K > 8192): GRU encode of later horizon chunks beside the rollout of earlier ones
+  int dehoog_gru_chunks = 0;        // staged de Hoog planner: GRU encode in this many horizon chunks beside the step chain (0 / 1: one launch up front)
+  int dehoog_gru_lds_pad = 49152;   // unused dynamic LDS of those chunk launches (bytes): 32 KB + 48 KB -> two workgroups per CU
+  int dehoog_chain = -1;            // de Hoog planner: the step chain as one persistent launch (kernels_dehoog_chain.hip): -1 auto, 0 / 1
+  int dehoog_chain_phases = 3;      // tools only: 1 / 2 = only the representation / QD phase of the chain kernel runs (timing)
+  int dehoog_streams = 0;           // staged de Hoog planner: parts of the population on streams of their own (0 auto)
+  int linear_fused = 1;             // fixed Talbot / Stehfest models: LIN instances of the rollout kernels (0: the staged path)
+  int host_spin = 1;                // nlc_mppi_finish with a host action pointer: 1 spin on a pinned word the merge kernel
+                                    // stores, 2 sleep through the predicted wait first, 0 hipStreamSynchronize
+  double host_spin_margin_us = 150.0;  // host_spin 2: the host wakes this long (or 15 % of the predicted wait) before the predicted end
+  // fused one-launch body.  fused.blocks_per_cu: 0 auto (3 while chains sit on at most half of the CUs, else 4), 3 or 4;
+  // fused.roll_cap: 0 auto (one chain per 16-sample tile, at most one per CU); fused.chain_first_tiles: tiles per wave a chain's
+  // workgroup encodes before it starts walking (-1 auto); fused.partner_tiles: tiles per wave after which a chain's CU partner
+  // sleeps (-1: never, -2 auto); fused.tile_step_ratio > 0: the adaptive partner rule (measured slower:
+  // profiles/r3_fused_small_shard.md), 0 = static schedule
+  nlc::plan::FusedKnobs fused;
+  int64_t fused_max_samples = 4096; // auto: populations up to this size take the fused body (one chain per CU at most)
+  int fused_inline = 3;             // sampling / bounding and the weight reduction inside the launch
+  int64_t fused_spin_limit = 1 << 18;  // polls (~2 us each) before a waiting wave of the fused body gives up (~0.5 s)
+  int fused_keep_sync = 0;          // tools only: the merge kernel leaves the sync block as the launch left it (timeline dumps)
+  int fused_test_drop_tile = -1;    // tests only: this encoder tile is never published (forces the timeout path)
+  double test_lin_coeff_scale = 1.0;  // tests only: the largest w_re / t coefficient of the LIN fragments is scaled by this
+  // tools only (tools/rollout_giveback.py): something BETWEEN the encoder launch and the rollout launch of the two-launch body
+  double dbg_gap_us = 0.0;          // one wavefront spinning on the constant 100 MHz counter for this long (an idle GPU)
+  double dbg_l2_mb = 0.0;           // a read sweep over this many MB of scratch (evicts the L2s)
+};
+
+// the fused one-launch body's occupancy cache, sync-block bookkeeping and give-up record
+struct FusedState {
+  int blocks_per_cu = -1;        // occupancy of the fused kernel's 4-per-CU instance (queried once per hidden width)
+  int blocks_per_cu3 = -1;       // ... of its 3-per-CU instance
+  int occ_h = 0;                 // hidden width the two occupancies were queried for
+  bool lost = false;             // a fused command gave up (hand-off timeout): later commands take the two-launch body
+  int64_t fallbacks = 0;         // commands re-run on the two-launch body after such a timeout
+  int64_t timeouts = 0;          // fused launches of THIS ctx that gave up (re-run or lost)
+  int64_t last_giveup_command = -1;  // value of nlc_ctx::commands (0-based) at the last give-up seen by this ctx, -1 = none
+  const void* sync_clean_ws = nullptr;  // workspace whose fused sync block the last merge kernel left zeroed
+  bool sync_dirty = false;       // a fused launch has used the sync block since
+  // the last command's inputs, kept for a re-run on the two-launch body (nlc_mppi_finish, after a fused timeout)
+  struct LastCommand {
+    bool valid = false, inline_inputs = false, fused = false;
+    int state_per_sample = 0, rng = 0;
+    uint64_t seed = 0, counter = 0;
+    double state_in[NLC_MAX_D] = {0};
+    double abuf_in[nlc::kMaxInlineAbuf] = {0};
+  } last;
+  // nlc_mppi_configure: nothing of the previous problem's commands is left to clean up after or to replay.  The occupancy
+  // cache (a property of the model's width), `lost` and the counters (of the ctx's life) stay.
+  void new_problem() {
+    sync_clean_ws = nullptr;
+    sync_dirty = false;
+    last.valid = false;
+  }
+  // nlc_set_option "rollout_variant": an explicit choice re-arms the fused body after a timeout
+  void rearm() { lost = false; }
+};
+
+// de Hoog planner, "dehoog_chain" and "dehoog_streams" both on auto: the chain's form is measured over the planner's first
+// commands (abi_planner_nl.hip; the decision rule is nlc_plan.h dehoog_pick)
+struct DehoogCalib {
+  int n = 0, choice = -1, pending = -1, pending_round = 0;
+  double t0 = 0.0;
+  float ms[3][2] = {{1e30f, 1e30f}, {1e30f, 1e30f}, {1e30f, 1e30f}};  // [candidate][round & 1]: the last two rounds
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  // nlc_mppi_configure: measured again for the new problem (the event pair is kept)
+  void reset() {
+    n = 0;
+    choice = pending = -1;
+    for (auto& v : ms) v[0] = v[1] = 1e30f;
+  }
+  void destroy() {
+    for (hipEvent_t& e : ev) {
+      if (e) hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
+// host_spin: the wait for the action in nlc_mppi_finish
+struct HostWait {
+  unsigned long long seq = 0;  // sequence number of the last command handed to the spin protocol (never reset: the pinned word
+                               // keeps the last one stored)
+  double hist_us[8] = {0};     // the last waits for the action (their minimum predicts the next one)
+  int hist_n = 0, hist_at = 0;
+  double nap_margin_us = 0.0;  // host_spin 2: the margin in use (grows when a nap overshoots the action's arrival)
+  // nlc_mppi_configure, nlc_set_option "host_spin": a new problem size or mode, a new wait to predict
+  void reset() {
+    hist_n = hist_at = 0;
+    nap_margin_us = 0.0;
+  }
+};
+
+// streams and events beside the ctx's stream, created on first use and kept until nlc_destroy
+struct SideStreams {
+  hipStream_t gru_stream = nullptr;      // GRU encode in horizon chunks (low priority)
+  std::vector<hipEvent_t> ev_gru;        // ... latents of chunk ch are there
+  std::vector<hipStream_t> aux_streams;  // staged step chain: parts 1 .. P-1 of the population
+  hipEvent_t ev_fork = nullptr;
+  std::vector<hipEvent_t> ev_join;
+  hipEvent_t stage_ev = nullptr;         // recorded after the staged H2D copies of a command
+  void destroy() {
+    if (stage_ev) hipEventDestroy(stage_ev);
+    if (ev_fork) hipEventDestroy(ev_fork);
+    for (hipEvent_t e : ev_join) hipEventDestroy(e);
+    for (hipStream_t s : aux_streams) hipStreamDestroy(s);
+    for (hipEvent_t e : ev_gru) hipEventDestroy(e);
+    if (gru_stream) hipStreamDestroy(gru_stream);
+    *this = SideStreams{};
   }
 };
 
@@ -99,82 +219,30 @@ struct nlc_ctx {
   double* small = nullptr;    // action (<= T*nu) + beta_eta (2)
   double tn = 0.0;
   int nblk = 0;
+  double* cp_lin = nullptr;             // [2][2 nt3][64] device: w_re / t and -w_im / t coefficient fragments (configure time)
+  std::vector<std::pair<int, int>> slot_elems;  // (dim, term) of every layer-3 slot (nlc_pack.h), kept from nlc_set_model
+  int64_t commands = 0;                 // nlc_mppi_rollout calls since nlc_create
+  int last_body = 0;                    // body phase 1 of the last command ran on (nlc_get_stat "rollout_body")
 
   bool profiling = false;
   std::vector<nlc::host::ProfEntry> prof;
   std::vector<hipEvent_t> event_pool;
 
-  // pinned host staging for the per-command small transfers (state, action_buffer, action)
+  // pinned host block of the configured planner (nlc_plan.h): staging for the per-command small transfers, the action, and the
+  // control words the kernels store
   double* pinned = nullptr;
   size_t pinned_n = 0;
-  hipEvent_t stage_ev = nullptr;  // recorded after the staged H2D copies of a command
-  // planner options (nlc_set_option)
-  int opt_rollout_variant = 0;          // 0 auto, 1 wave-per-tile, 2 latency-split (two launches), 3 fused one-launch body
-  int opt_fused_roll_cap = 0;           // 0 auto (one chain per 16-sample tile, at most one per CU)
-  int opt_repfunc_split = 1;            // staged de Hoog planner: latency-split representation kernel (h = 128)
-  int opt_gru_coop = -1;                // stand-alone GRU encodes: cooperative (one tile per workgroup) kernel 1 / 0, -1 auto
-  int opt_fused_chain_first_tiles = -1; // tiles per wave a chain's workgroup encodes before it starts walking (-1 auto)
-  int opt_fused_partner_tiles = -2;     // tiles per wave after which a chain's CU partner sleeps (-1: never, -2 auto)
-  int64_t opt_fused_max_samples = 4096; // auto: populations up to this size take the fused body (one chain per CU at most)
-  int fused_blocks_per_cu = -1;         // occupancy of the fused kernel's 4-per-CU instance (queried once)
-  int fused_blocks_per_cu3 = -1;        // ... of its 3-per-CU instance
-  int fused_occ_h = 0;                  // hidden width the two occupancies were queried for
-  int opt_fused_blocks_per_cu = 0;      // 0 auto (3 while chains sit on at most half of the CUs, else 4), 3 or 4
-  bool fused_lost = false;              // a fused command gave up (hand-off timeout): later commands take the two-launch body
-  int64_t fused_fallbacks = 0;          // commands re-run on the two-launch body after such a timeout
-  int64_t fused_timeouts = 0;           // fused launches of THIS ctx that gave up (re-run or lost)
-  int64_t commands = 0;                 // nlc_mppi_rollout calls since nlc_create
-  int64_t last_giveup_command = -1;     // value of `commands` (0-based) at the last give-up seen by this ctx, -1 = none
-  int last_body = 0;                    // body phase 1 of the last command ran on (nlc_get_stat "rollout_body")
-  // tools only (tools/rollout_giveback.py): something BETWEEN the encoder launch and the rollout launch of the two-launch body
-  double opt_dbg_gap_us = 0.0;          // one wavefront spinning on the constant 100 MHz counter for this long (an idle GPU)
-  double opt_dbg_l2_mb = 0.0;           // a read sweep over this many MB of scratch (evicts the L2s)
+  nlc::plan::PinLayout pin{};
+  // the planner's state by group; each group's reset rule is its own (who calls which: nlc_mppi_configure, nlc_set_option,
+  // nlc_destroy)
+  nlc::host::PlannerOptions opt;
+  nlc::host::FusedState fused;
+  nlc::host::DehoogCalib dh;
+  nlc::host::HostWait wait;
+  nlc::host::SideStreams side;
+  // tools only (options "dbg_gap_us" / "dbg_l2_mb")
   double* dbg_scratch = nullptr;
-  size_t dbg_scratch_bytes = 0;
-  int opt_gru_gemm = 0;                 // 1: encoder hidden-state GEMMs on the INT8 matrix pipe (kernels_gru_i8.hip), g == 64 only
-  int opt_horizon_chunks = 1;           // Fourier planner, wave-per-tile body (K > 8192): GRU encode of later horizon chunks beside the rollout of earlier ones
-  int opt_dehoog_gru_chunks = 0;        // staged de Hoog planner: GRU encode in this many horizon chunks beside the step chain (0 / 1: one launch up front)
-  int opt_dehoog_gru_lds_pad = 49152;   // unused dynamic LDS of those chunk launches (bytes): 32 KB + 48 KB -> two workgroups per CU
-  hipStream_t gru_stream = nullptr;
-  std::vector<hipEvent_t> ev_gru;
-  int opt_dehoog_chain = -1;            // de Hoog planner: the step chain as one persistent launch (kernels_dehoog_chain.hip): -1 auto, 0 / 1
-  // de Hoog planner, both knobs on auto: the chain's form is measured over the planner's first commands (abi_planner_nl.hip)
-  int dh_n = 0, dh_choice = -1, dh_pending = -1, dh_pending_round = 0;
-  double dh_t0 = 0.0;
-  float dh_ms[3][2] = {{1e30f, 1e30f}, {1e30f, 1e30f}, {1e30f, 1e30f}};  // [candidate][round & 1]: the last two rounds
-  hipEvent_t dh_ev[2] = {nullptr, nullptr};
-  int opt_dehoog_chain_phases = 3;      // tools only: 1 / 2 = only the representation / QD phase of the chain kernel runs (timing)
-  int opt_dehoog_streams = 0;           // staged de Hoog planner: parts of the population on streams of their own (0 auto)
-  std::vector<hipStream_t> aux_streams;
-  hipEvent_t ev_fork = nullptr;
-  std::vector<hipEvent_t> ev_join;
-  double opt_fused_tile_step_ratio = 0.0;  // > 0: the adaptive partner rule (measured slower: profiles/r3_fused_small_shard.md); 0 = static schedule
-  int opt_host_spin = 1;                // nlc_mppi_finish with a host action pointer: 1 spin on a pinned word the merge kernel
-                                        // stores, 2 sleep through the predicted wait first, 0 hipStreamSynchronize
-  unsigned long long host_seq = 0;      // sequence number of the last command handed to the spin protocol
-  double opt_host_spin_margin_us = 150.0;  // host_spin 2: the host wakes this long (or 15 % of the predicted wait) before the predicted end
-  double wait_hist_us[8] = {0};         // host_spin: the last waits for the action (their minimum predicts the next one)
-  int wait_hist_n = 0, wait_hist_at = 0;
-  double nap_margin_us = 0.0;           // host_spin 2: the margin in use (grows when a nap overshoots the action's arrival)
-  int opt_fused_inline = 3;             // fused body: sampling / bounding and the weight reduction inside the launch
-  int64_t opt_fused_spin_limit = 1 << 18;  // polls (~2 us each) before a waiting wave of the fused body gives up (~0.5 s)
-  int opt_fused_test_drop_tile = -1;    // tests only: this encoder tile is never published (forces the timeout path)
-  double opt_test_lin_coeff_scale = 1.0;  // tests only: the largest w_re / t coefficient of the LIN fragments is scaled by this
-  int opt_linear_fused = 1;             // fixed Talbot / Stehfest models: LIN instances of the rollout kernels
-                                        // (0: the staged path)
-  double* cp_lin = nullptr;             // [2][2 nt3][64] device: w_re / t and -w_im / t coefficient fragments (configure time)
-  std::vector<std::pair<int, int>> slot_elems;  // (dim, term) of every layer-3 slot (nlc_pack.h), kept from nlc_set_model
-  int opt_fused_keep_sync = 0;          // tools only: the merge kernel leaves the sync block as the launch left it (timeline dumps)
-  const void* sync_clean_ws = nullptr;  // workspace whose fused sync block the last merge kernel left zeroed
-  bool sync_dirty = false;              // a fused launch has used the sync block since
-  // the last command's inputs, kept for a re-run on the two-launch body (nlc_mppi_finish, after a fused timeout)
-  struct LastCommand {
-    bool valid = false, inline_inputs = false, fused = false;
-    int state_per_sample = 0, rng = 0;
-    uint64_t seed = 0, counter = 0;
-    double state_in[NLC_MAX_D] = {0};
-    double abuf_in[nlc::kMaxInlineAbuf] = {0};
-  } last;
+  size_t dbg_scratch_n = 0;
   // optional native collective (nlc_comm_init): an RCCL communicator over the ranks of a K-sharded planner
   void* comm = nullptr;
   int comm_world = 0, comm_rank = 0;
@@ -262,6 +330,11 @@ struct Blob {
 };
 
 bool is_device_ptr(const void* p);
+// "this device buffer must hold n doubles": frees what p held, allocates, and uploads n doubles from `upload` when given (a
+// synchronous copy).  With `have` (the buffer's size so far) the buffer only grows: nothing happens while n <= *have.
+int hold_doubles(nlc_ctx* c, double*& p, size_t n, const double* upload = nullptr, size_t* have = nullptr);
+// its twin for mapped, coherent pinned host memory; grows only
+int hold_pinned_doubles(nlc_ctx* c, double*& p, size_t n, size_t* have);
 bool gru_use_coop(const nlc_ctx* c, int64_t n_windows);
 
 // ---- abi_ilt.hip
@@ -293,10 +366,10 @@ struct WsLayout {
   size_t tile_part, chunk_part, pa, state0, abuf, xcarry, ccarry, fre, fim, dx, tconst, rq, sync, total;
 };
 WsLayout ws_layout(const nlc_ctx* c);
-double* fused_timeout_word(nlc_ctx* c);
-bool fused_gave_up(nlc_ctx* c);
-unsigned* merge_status_word(nlc_ctx* c);
-bool merge_reported_invalid(nlc_ctx* c);
+// the control words of the pinned block (nlc_plan.h PinLayout)
+inline unsigned* pin_giveup_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned + c->pin.giveup); }
+inline unsigned long long* pin_seq_word(nlc_ctx* c) { return reinterpret_cast<unsigned long long*>(c->pinned + c->pin.seq); }
+inline unsigned* pin_merge_status_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned + c->pin.merge_status); }
 WeightArgs make_weight_args(nlc_ctx* c, const nlc_mppi_buffers* buf);
 int run_weights(nlc_ctx* c, const nlc_mppi_buffers* buf);
 

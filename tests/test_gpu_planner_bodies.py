@@ -206,6 +206,54 @@ def test_fused_timeout_reruns_command_on_two_launch_body(nlc):
         bad.ctx.get_stat("no_such_counter")
 
 
+@pytest.mark.parametrize("kind", ["oracle", "nl_fused"])
+def test_reconfigured_ctx_equals_fresh_ctx(nlc, kind):
+    """One context, two problems: a planner of K = 32, T = 3, B = 1 runs two commands, then a planner of K = 80, T = 5, B = 2
+    takes over the SAME context (nlc_mppi_configure on a live ctx: the pinned block and its control words, the fused body's sync
+    bookkeeping, the kept inputs of the last command and the host-wait history are the first problem's) and runs two commands.
+    Actions, U and cost_total equal, bit for bit, those of the second problem on a context of its own.  Oracle pendulum
+    dynamics, and an h = 64 Fourier model on the one-launch fused body."""
+    from oracle import nl_model as onl
+
+    env = "oderl-pendulum"
+    st = onl.ENV_STATS[env]
+    d, nu, A = st["d"], st["nu"], st["act_high"]
+    if kind == "nl_fused":
+        # (building the model's modules draws their initial weights from torch's global generator, which later tests of the
+        # suite take their unseeded start states from: leave it where it was)
+        with torch.random.fork_rng(devices=[0]):
+            model = build_model(nlc, onl.make_synthetic_state_dict(0, d, nu, 64, 17, st["state_std"], [A / 2], tame=True))
+        dyn, opts, body = nlc.NLDynamics(model, 0.05), {"rollout_variant": 3}, "fused"
+    else:
+        dyn, opts, body = nlc.OracleDynamics(env, 0.05, 0), None, "oracle"
+
+    def make(K, T):
+        return nlc.MPPIDelay(dyn, nlc.EnvCost(env), d, nlc.noise_sigma(nu), K, T, "cpu", lambda_=1.0, u_min=torch.tensor(-A),
+                             u_max=torch.tensor(A), u_scale=A, noise_rng="philox", seed=7, planner_options=opts,
+                             U_init=torch.zeros(T, nu, dtype=torch.float64))
+
+    def run(p, B):
+        state, ab, outs = nlc.initial_state(env), torch.zeros(B, nu, dtype=torch.float64), []
+        for _ in range(2):
+            a = p.command(state, ab)
+            outs.append((a.clone(), p.U.clone(), p.cost_total.clone()))
+            assert p.rollout_body == body
+            ab = torch.roll(ab, -1, 0)
+            ab[-1] = a
+        return outs
+
+    first = make(32, 3)
+    run(first, 1)
+    moved = make(80, 5)
+    moved.ctx = first.ctx  # (the options of `first` are already set there)
+    fresh = make(80, 5)
+    for step, (got, want) in enumerate(zip(run(moved, 2), run(fresh, 2))):
+        for g, w in zip(got, want):
+            assert torch.equal(g, w), step
+    assert int(moved.ctx.get_stat("commands")) == 4 and int(fresh.ctx.get_stat("commands")) == 2
+    assert moved.fused_timeouts == 0
+
+
 @pytest.mark.parametrize("algo,S,K,h", [("fixed_tablot", 17, 2500, 128), ("stehfest", 12, 700, 128), ("fixed_tablot", 9, 16500, 128),
                                         ("fixed_tablot", 11, 900, 64), ("stehfest", 8, 16400, 64), ("fixed_tablot", 13, 300, 256)])
 def test_linear_ilt_models_on_rollout_kernels_vs_staged_path(nlc, algo, S, K, h):
