@@ -333,7 +333,7 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
       ProfScope ps(c, "nl_repfunc_kernel");
       NLC_HIP(c, launch_nl_repfunc(rf, c->stream));
     }
-    IltArgs ia{th, ph, ts, out, N, dd, S, c->md.ilt.alpha, std::log(c->md.ilt.tol), c->md.ilt.scale, nullptr, nullptr, c->md.time_div, 1, 0, 0, 0};
+    IltArgs ia{th, ph, ts, out, N, dd, S, c->md.ilt.alpha, std::log(c->md.ilt.tol), c->md.ilt.scale, nullptr, nullptr, c->md.time_div, 1, 0, 0};
     ia.lin_wr = tab + 2 * S;
     ia.lin_wi = tab + 3 * S;
     hipError_t le;
@@ -370,7 +370,7 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
       NLC_HIP(c, launch_nl_repfunc(rf, c->stream));
     }
     IltArgs ia{nullptr, nullptr, ts, out, N, c->md.d, c->S, c->md.ilt.alpha, std::log(c->md.ilt.tol), c->md.ilt.scale,
-               fre, fim, c->md.time_div, 1, 0, 0, 0};
+               fre, fim, c->md.time_div, 1, 0, 0};
     ProfScope ps(c, "ilt_dehoog_kernel");
     NLC_HIP(c, launch_ilt_dehoog(ia, c->stream));
     return NLC_OK;

@@ -196,7 +196,7 @@ int launch_staged_steps(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc,
   rf.slot_major = 1;
   rf.split = c->md.h == 128 && c->opt.repfunc_split != 0;
   IltArgs ia{nullptr, nullptr, tconst, ws + w.dx, KE, d.d, c->S, c->md.ilt.alpha, std::log(c->md.ilt.tol),
-             c->md.ilt.scale, rf.fre, rf.fim, 1.0, 0, 0, 0, 0, c->eidx_dev};
+             c->md.ilt.scale, rf.fre, rf.fim, 1.0, 0, 0, 0, c->eidx_dev};
   StepTailArgs st{sc};
   st.d = d.d;
   st.x = r.xcarry;

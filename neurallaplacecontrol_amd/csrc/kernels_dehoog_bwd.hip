@@ -18,10 +18,10 @@
 // row at the memory counters in round 4, i.e. 92 GB for the bench's 3.3 M rows in 19.8-22.2 ms = 4.2-4.7 TB/s, which is what a
 // read + write stream attains on this chip (tools/ubench_hbm_copy.hip: 4.5-5.5): at 33 terms the kernel is bound by its own tape.
 // Round 5 took the 8 KB that were NOT tape out of that figure: the rows' inputs and gradients go through an LDS image of the
-// wavefront's 64 rows as whole lines (NLC_DHB_LDS_IO below; before, 64 lines per load instruction and eight useful bytes per
+// wavefront's 64 rows as whole lines (io_th / io_ph below; before, 64 lines per load instruction and eight useful bytes per
 // 32-byte sector of every gradient store), and the terms a_k are rebuilt in the epilogue instead of taped: forward + backward
 // 22.3 -> 17.1 ms at 3.3 M rows; then the e columns of odd r are rebuilt from their even neighbours instead of taped
-// (NLC_DHB_SKIP_ODD_E: 136 of 594 entries not written, and 63 fewer spilled VGPRs): **14.5-15.1 ms**, 0.78 -> 0.58 ms at 81 920
+// (136 of 594 entries not written, and 63 fewer spilled VGPRs): **14.5-15.1 ms**, 0.78 -> 0.58 ms at 81 920
 // rows (same box, interleaved; gradients bit-identical to round 4 at every step; the epilogue rebuilds q_1^(k) = a_(k+1) / a_k
 // instead of reading column 1 a second time).  Checkpointed columns with recomputation do
 // not pay on top of that: DESIGN.md section 9b.
@@ -34,56 +34,45 @@
 #include "nlc_device.h"
 #include "nlc_kernels.h"
 
-// sweep iterations per prefetch chunk of the backward pass (two chunks of tape values are register-resident; measured on the
-// MI355X at 3.3 M rows, M = 16: 8 -> 23.5 ms with 197 spilled VGPRs, 4 -> 21.5 ms with 93, no prefetch 25.6 ms)
-#ifndef NLC_DHB_GROUP
-#define NLC_DHB_GROUP 4
-#endif
 // Round 5: the rows' inputs and gradients travel through an LDS image of the wavefront's 64 rows -- (64, S) doubles each for
 // theta and phi, read from and written to HBM as whole contiguous lines (a wavefront's 64 consecutive rows ARE one contiguous
 // block of 64 S doubles); the gradients overwrite the image in place (term k of a row is read, then written, by the same lane)
 // and leave as whole lines.  Before, every lane read and wrote its own row with a stride of S doubles: 64 lines per instruction,
 // eight useful bytes per 32-byte sector on the way out.  And the terms a_k are not taped any more: the epilogue rebuilds them from
-// theta / phi (the same three operations), 2 x 33 entries = 1 KB per row less on the tape.  0 = the round-4 form.
-#ifndef NLC_DHB_LDS_IO
-#define NLC_DHB_LDS_IO 1
-#endif
+// theta / phi (the same three operations), 2 x 33 entries = 1 KB per row less on the tape.
 // Round 5: the e columns of ODD r are not taped (except their first entry, the continued fraction's coefficient): the backward
 // sweep rebuilds e_r^(i) = (q_r^(i+1) - q_r^(i)) + e_(r-1)^(i+1) from the q column it loads anyway and the EVEN column below it
 // (zero below column 1) -- the forward's own three operands in the forward's own order, so the rebuilt values are the taped ones
-// bit for bit.  136 of the 594 entries per row are not written (2.1 KB), column 1 needs no e loads at all.  0 = tape every column.
-#ifndef NLC_DHB_SKIP_ODD_E
-#define NLC_DHB_SKIP_ODD_E 1
-#endif
+// bit for bit.  136 of the 594 entries per row are not written (2.1 KB), column 1 needs no e loads at all.
 
 namespace nlc {
 
 namespace {
 
+// sweep iterations per prefetch chunk of the backward pass (two chunks of tape values are register-resident; measured on the
+// MI355X at 3.3 M rows, M = 16: 8 -> 23.5 ms with 197 spilled VGPRs, 4 -> 21.5 ms with 93, no prefetch 25.6 ms)
+constexpr int kDhbGroup = 4;
+
 struct DhLayout {
   int M;
-  // Round 5: with the defaults (NLC_DHB_LDS_IO, NLC_DHB_SKIP_ODD_E) the terms a_k and the odd e columns are not taped, and the slab
-  // is laid out without them: q columns | even e columns | first entry of every odd e column | A | B -- 466 entries per row at M = 16
-  // instead of 627 (0.49 GB of scratch for 1024 resident wavefronts instead of 0.66).
-  static constexpr bool kCompact = NLC_DHB_LDS_IO && NLC_DHB_SKIP_ODD_E;
+  // Round 5: the terms a_k and the odd e columns are not taped, and the slab is laid out without them: q columns | even e columns |
+  // first entry of every odd e column | A | B -- 466 entries per row at M = 16 instead of 627 (0.49 GB of scratch for 1024 resident
+  // wavefronts instead of 0.66).
   // value tape
   __host__ __device__ constexpr int q(int r, int i) const { return (r - 1) * (2 * M + 2 - r) + i; }                 // r = 1..M, i = 0..2(M-r)+1
   __host__ __device__ constexpr int even_before(int n) const { return n * (2 * M + 1) - 2 * n * (n + 1); }            // entries of the even columns 2 .. 2n
   __host__ __device__ constexpr int e(int r, int i) const {                                                          // r = 1..M, i = 0..2(M-r)
-    if (!kCompact) return M * (M + 1) + (r - 1) * (2 * M + 1 - r) + i;
     if ((r & 1) == 0) return M * (M + 1) + even_before((r - 2) / 2) + i;
     return M * (M + 1) + even_before(M / 2) + (r - 1) / 2;  // odd column: only i == 0 is taped
   }
-  __host__ __device__ constexpr int e_end() const { return kCompact ? M * (M + 1) + even_before(M / 2) + (M + 1) / 2 : M * (M + 1) + M * M; }
-  __host__ __device__ constexpr int a_n() const { return kCompact ? 0 : 2 * M + 1; }
-  __host__ __device__ constexpr int a(int i) const { return e_end() + i; }                                            // i = 0..2M (not compact)
-  __host__ __device__ constexpr int A(int i) const { return e_end() + a_n() + (i + 1); }                             // i = -1..2M-1
-  __host__ __device__ constexpr int B(int i) const { return e_end() + a_n() + (2 * M + 1) + (i + 1); }               // i = -1..2M-1
-  __host__ __device__ constexpr int entries() const { return e_end() + a_n() + 2 * (2 * M + 1); }
+  __host__ __device__ constexpr int e_end() const { return M * (M + 1) + even_before(M / 2) + (M + 1) / 2; }
+  __host__ __device__ constexpr int A(int i) const { return e_end() + (i + 1); }                                     // i = -1..2M-1
+  __host__ __device__ constexpr int B(int i) const { return e_end() + (2 * M + 1) + (i + 1); }                       // i = -1..2M-1
+  __host__ __device__ constexpr int entries() const { return e_end() + 2 * (2 * M + 1); }
 };
-static_assert(!DhLayout::kCompact || DhLayout{16}.entries() == 466, "compact tape layout at M = 16");
-static_assert(!DhLayout::kCompact || (DhLayout{16}.e(4, 0) - DhLayout{16}.e(2, 0) == 2 * 14 + 1 && DhLayout{16}.e(16, 0) + 1 == DhLayout{16}.e(1, 0) &&
-                                      DhLayout{5}.e(5, 0) + 1 == DhLayout{5}.A(-1) && DhLayout{1}.entries() == 2 + 0 + 1 + 6),
+static_assert(DhLayout{16}.entries() == 466, "compact tape layout at M = 16");
+static_assert(DhLayout{16}.e(4, 0) - DhLayout{16}.e(2, 0) == 2 * 14 + 1 && DhLayout{16}.e(16, 0) + 1 == DhLayout{16}.e(1, 0) &&
+                  DhLayout{5}.e(5, 0) + 1 == DhLayout{5}.A(-1) && DhLayout{1}.entries() == 2 + 0 + 1 + 6,
               "compact tape layout: columns are contiguous and disjoint");
 
 // Tape accesses go through a wave-uniform (SGPR) slab pointer that is laundered at every access: the entry offsets are
@@ -124,12 +113,9 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
   const int64_t nblk = (rows_total + 63) / 64;
   const Tape tp{(tape_ptr)(reinterpret_cast<double*>(a.scratch) + (size_t)blockIdx.x * L.entries() * 128), lane};
   const cplx one = {1.0, 0.0}, zero = {0.0, 0.0};
-#if NLC_DHB_LDS_IO
   __shared__ double io_th[64 * S], io_ph[64 * S];  // the wavefront's rows: theta / phi in, the two gradients out (in place)
-#endif
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int64_t row = blk * 64 + lane;
-#if NLC_DHB_LDS_IO
     // one wavefront = one workgroup: the image is private to it, program order + s_waitcnt order its accesses (no barrier)
     const int64_t base = blk * 64 * S;
     // (both copy loops have a WAVE-UNIFORM trip count and a per-lane predicate inside.  A per-lane loop condition -- `for (i = lane;
@@ -149,20 +135,14 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
-#endif
     if (row >= rows_total) continue;  // (no barriers in this kernel: a lane may skip)
     const double t = a.t[row / a.d] / a.t_div;
     const double Tt = a.scale * t;
     const double gamma = a.alpha - a.log_tol / (a.scale * Tt);
     const double ang = kPi * (t / Tt);
     const cplx z = {cos(ang), sin(ang)};
-#if NLC_DHB_LDS_IO
     const double* th = io_th + lane * S;
     const double* ph = io_ph + lane * S;
-#else
-    const double* th = a.theta + row * S;
-    const double* ph = a.phi + row * S;
-#endif
 
     // ---------------------------------------------------------------- forward, taped
     // a_k = F_k = R e^{i theta}, R = tan(phi/2 + pi/4); a_0 enters halved.  Column 1: q_1^(i) = a_{i+1} / a_i
@@ -178,7 +158,6 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
         cplx ak = {rad * cs, rad * sn};
         if (k == 0) ak = cscale(ak, 0.5);
         if (k == 0) a0 = ak;
-        if (!NLC_DHB_LDS_IO) tp.st(L.a(k), ak);
         if (k > 0) {
           Q[k - 1] = cdiv(ak, prev);
           tp.st(L.q(1, k - 1), Q[k - 1]);
@@ -222,7 +201,7 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
       for (int i = 0; i < mr; ++i) {
         const cplx qhi = Q[i + 1];
         const cplx ei = cadd(csub(qhi, qlo), E[i + 1]);
-        if (!NLC_DHB_SKIP_ODD_E || (r & 1) == 0 || i == 0) tp.st(L.e(r, i), ei);
+        if ((r & 1) == 0 || i == 0) tp.st(L.e(r, i), ei);
         if (r != M && i >= 1) {
           Q[i - 1] = cdiv(cmul(qlo, ei), elo);
           tp.st(L.q(r + 1, i - 1), Q[i - 1]);
@@ -230,7 +209,7 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
         E[i] = ei;
         qlo = qhi;
         elo = ei;
-        if ((i & (NLC_DHB_GROUP - 1)) == NLC_DHB_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+        if ((i & (kDhbGroup - 1)) == kDhbGroup - 1) __builtin_amdgcn_sched_barrier(0);
       }
       feed(2 * r, cneg(E[0]));
       // (keeps the columns apart: the compiler otherwise interleaves them and the live ranges explode)
@@ -303,7 +282,7 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
     }
     // Tape values are fetched in chunks of kChunk sweep iterations, one chunk AHEAD of the chunk being computed (two register
     // buffers), and the next column's recurrence operands one column ahead.
-    constexpr int kChunk = NLC_DHB_GROUP;
+    constexpr int kChunk = kDhbGroup;
     UnfeedOps uo_even = unfeed_load(2 * M - 1), uo_odd = uo_even;  // column M: dbar_2M is g_dend, dbar_(2M-1) needs step 2M-1
 #pragma unroll
     for (int r = M; r >= 1; --r) {
@@ -313,9 +292,9 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
       cplx qn[2][kChunk], en[2][kChunk];  // qn[b][j] = q_r^(i+1), en[b][j] = e_r^(i+1) for sweep iteration i = c kChunk + j
       // first chunk + the sweep's first entries
       cplx e_i = tp.ld(L.e(r, 0)), q_i = tp.ld(L.q(r, 0));
-      // odd columns (NLC_DHB_SKIP_ODD_E): e_r is rebuilt, so the q buffers run TWO entries ahead (qn = q_r^(i+2), q_roll =
+      // odd columns: e_r is rebuilt, so the q buffers run TWO entries ahead (qn = q_r^(i+2), q_roll =
       // q_r^(i+1)) and the e buffers hold the even column below, en = e_(r-1)^(i+2)
-      const bool odd = NLC_DHB_SKIP_ODD_E && (r & 1) != 0;
+      const bool odd = (r & 1) != 0;
       cplx q_roll = (odd && 1 <= mr) ? tp.ld(L.q(r, 1)) : zero;
       auto load_q = [&](int i) -> cplx {  // the q entry iteration i's buffer slot holds
         const int at = odd ? i + 2 : i + 1;
@@ -412,7 +391,7 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
     //   F_k = R (cos theta + i sin theta), R = tan(phi/2 + pi/4), dR/dphi = (1 + R^2) / 2;  a_0 = F_0 / 2
     cplx h_prev = zero;
     // (rad, sn, cs) of term k + 1 are computed one iteration ahead: a_(k+1) / a_k IS q_1^(k), by the forward's own division, so
-    // column 1 is not read a second time here (NLC_DHB_LDS_IO; the image still holds theta / phi of every term > k)
+    // column 1 is not read a second time here (the LDS image still holds theta / phi of every term > k)
     double rad_n = m::tan_0_halfpi(ph[0] / 2.0 + kPi / 4.0), sn_n, cs_n;
     m::sincos_bounded(th[0], &sn_n, &cs_n);
 #pragma unroll
@@ -424,15 +403,10 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
       }
       cplx gF = k == 0 ? g_a0_seed : h_prev;
       if (k <= 2 * M - 1) {
-#if NLC_DHB_LDS_IO
         cplx ak = {rad * cs, rad * sn};  // a_k as the forward built it (same operations)
         if (k == 0) ak = cscale(ak, 0.5);
         const cplx ak1 = {rad_n * cs_n, rad_n * sn_n};
         const cplx q1k = cdiv(ak1, ak);
-#else
-        const cplx ak = tp.ld(L.a(k));
-        const cplx q1k = tp.ld(L.q(1, k));
-#endif
         const cplx h = cdiv(W[k], cconj(ak));
         gF = csub(gF, cmul(h, cconj(q1k)));
         h_prev = h;
@@ -440,15 +414,9 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
       if (k == 0) gF = cscale(gF, 0.5);
       const double g_th = rad * (gF.im * cs - gF.re * sn);
       const double g_ph = (gF.re * cs + gF.im * sn) * (0.5 * (1.0 + rad * rad));
-#if NLC_DHB_LDS_IO
       io_th[lane * S + k] = g_th;  // in place: term k of this row is not read again
       io_ph[lane * S + k] = g_ph;
-#else
-      a.gtheta[row * S + k] = g_th;
-      a.gphi[row * S + k] = g_ph;
-#endif
     }
-#if NLC_DHB_LDS_IO
     // (lanes past the last row skipped the body with `continue`: in a partial block they do not reach this point, the live
     // lanes copy the whole image out)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -462,7 +430,6 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
-#endif
   }
 }
 

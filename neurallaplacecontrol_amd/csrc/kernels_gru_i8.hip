@@ -60,10 +60,6 @@ __device__ __forceinline__ constexpr int i8_next2(int p) { return (p + 2) % 36; 
 // one tile of the stream: hand the staged block on, fetch the block after next, run `body` on the current block, barrier
 template <class F>
 __device__ __forceinline__ void i8_op(WeightStream& ws, int parity, int next2, F body) {
-#if NLC_I8_DBG == 3  // tools only (timing): no staging, no barrier -- every tile reads the first block (wrong results)
-  body((const char*)ws.lds);
-  return;
-#endif
   ws.put(parity ^ 1);
   ws.fetch(next2);
   body((const char*)(ws.lds + parity * kI8Block));
@@ -145,18 +141,11 @@ __device__ __forceinline__ double gru_encode_tile_i8(const GruArgs& a, WeightStr
     const v4d hold = {H[(4 * j + 0) * 64 + lane], H[(4 * j + 1) * 64 + lane], H[(4 * j + 2) * 64 + lane], H[(4 * j + 3) * 64 + lane]};
     // (tried: both halves of the gate math side by side, four chains in lockstep behind empty asms -- no change, 2.49 ms: the
     // partner wave covers the FP64 latency)
-#if NLC_I8_DBG == 4  // tools only (timing): no gate math
-    const v4d hn = pre[0] + pre[1] + pre[2] + pre[3] + hold;
-#else
     const v4d hn = gru_gates(pre[0], pre[1], pre[2], pre[3], hold);
-#endif
 #pragma unroll
     for (int r = 0; r < 4; ++r) H[(4 * j + r) * 64 + lane] = hn[r];
   };
   auto digits_of = [&](i8::v4i (&S)[i8::kDigits], const double* __restrict__ H) {  // the whole state, from its image
-#if NLC_I8_DBG == 5  // tools only (timing): no digit cut
-    return;
-#endif
 #pragma unroll
     for (int j = 0; j < GT; ++j)
       i8::slice_chunk(S, j, v4d{H[(4 * j + 0) * 64 + lane], H[(4 * j + 1) * 64 + lane], H[(4 * j + 2) * 64 + lane], H[(4 * j + 3) * 64 + lane]});
@@ -301,10 +290,7 @@ __device__ __forceinline__ double gru_encode_tile_i8(const GruArgs& a, WeightStr
   return nan_if_bad_window(bad_input, o[0][0] + a.bo[q < 2 ? q : 0]);
 }
 
-#ifndef NLC_I8_WAVES  // tools only: 1 = one wavefront per SIMD (512 registers, one workgroup per CU)
-#define NLC_I8_WAVES 2
-#endif
-__global__ __launch_bounds__(256, NLC_I8_WAVES) void gru_encode_i8_kernel(const GruArgs a) {
+__global__ __launch_bounds__(256, 2) void gru_encode_i8_kernel(const GruArgs a) {
   constexpr int G = 64, KS = G / 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = lane >> 4, c = lane & 15;
@@ -320,10 +306,6 @@ __global__ __launch_bounds__(256, NLC_I8_WAVES) void gru_encode_i8_kernel(const 
   // 64 KB of state images + 14.5 KB of weight staging: two workgroups per CU (160 KB)
   __shared__ double Hs[4][2][KS * 64];
   __shared__ __attribute__((aligned(16))) char Wst[2 * kI8Block];
-#if NLC_I8_WAVES == 1
-  __shared__ double pad_[4096];  // + 32 KB: a second workgroup does not fit the CU
-  if (a.N < 0) pad_[threadIdx.x] = 0.0;
-#endif
   WeightStream ws{a.i8_stream, Wst, (int)threadIdx.x, {}, {}};
   const double o = gru_encode_tile_i8<G>(a, ws, lane, wc, kk, tt, Hs[wave][0], Hs[wave][1]);
   if (valid && q < 2) {

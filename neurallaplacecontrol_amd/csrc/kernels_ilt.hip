@@ -11,15 +11,10 @@
 //                       VALU bound, not HBM bound.
 #include <atomic>
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "nlc_device.h"
 #include "nlc_kernels.h"
-
-#ifndef NLC_ILT_EXPERIMENTS
-#define NLC_ILT_EXPERIMENTS 0
-#endif
 
 namespace nlc {
 
@@ -163,8 +158,6 @@ hipError_t launch_ilt_linear_bwd(const IltLinBwdArgs& a, hipStream_t s) {
 // no scratch, wait counts 14-18): 0.192-0.209 ms against 0.188-0.194 ms for this kernel on the same box, and this kernel
 // at S = 16 (2048-B passes) moves its bytes only 6 % faster than at S = 17 -- line straddling is not what holds the
 // stream at 84 % of the bare read rate.
-// DBG: 0 = product; 1 / 2 = timing experiments (memory only / arithmetic only), instantiated by the tools build only
-// (-DNLC_ILT_EXPERIMENTS=1)
 // ITERS > 0: passes per tile known at compile time -> the pass loop is fully unrolled (straight-line code is
 // what lets the compiler keep counted s_waitcnt vmcnt(N) instead of draining the pipeline); 0: runtime loop.
 //
@@ -266,7 +259,7 @@ __device__ __forceinline__ double ilt_row_scale(const IltArgs& a, double t) {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 4 waves per SIMD (<= 128 VGPRs) where the unrolled tile fits without spilling, 3 otherwise
-template <int DBG, int ITERS, bool LIN = false>
+template <int ITERS, bool LIN = false>
 __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_fourier_kernel(const IltArgs a) {
   extern __shared__ double val[];  // [rows][SP]
   const int S = a.S;
@@ -303,10 +296,6 @@ __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_
       pp += blk * rows * S;
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
-        if (DBG == 2) {
-          th[u] = ph[u] = a.alpha * (double)threadIdx.x;
-          continue;
-        }
         th[u] = __builtin_nontemporal_load(tp + (int64_t)act * u);
         ph[u] = __builtin_nontemporal_load(pp + (int64_t)act * u);
         // issue order = the loop's refill order, so the wait counts at the loop head agree on both entries
@@ -330,18 +319,10 @@ __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_
       for (int i = 0; i < ITERS; ++i) {
         const int u = i % UB;
         double xt, xp;
-        if (DBG == 1) {
-          xt = th[u];
-          xp = ph[u];
-        } else {
-          ilt_args(th[u], ph[u], psi, &xt, &xp);
-        }
+        ilt_args(th[u], ph[u], psi, &xt, &xp);
         asm volatile("" : "+v"(xt), "+v"(xp));  // slot u is consumed here ...
         __builtin_amdgcn_sched_barrier(0);
-        if (DBG == 2) {  // timing experiment: arithmetic only (run-time values, nothing to fold)
-          th[u] = a.alpha * (double)(threadIdx.x + i) + (double)blk * 1e-7;
-          ph[u] = a.alpha * (double)(threadIdx.x + 3 * i);
-        } else if (i + UB < ITERS) {            // ... and refilled into the same registers
+        if (i + UB < ITERS) {                   // ... and refilled into the same registers
           th[u] = __builtin_nontemporal_load(tp + (int64_t)act * (i + UB));
           ph[u] = __builtin_nontemporal_load(pp + (int64_t)act * (i + UB));
         } else {
@@ -349,7 +330,7 @@ __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_
           ph[u] = __builtin_nontemporal_load(pn + actn * (i + UB - ITERS));
         }
         __builtin_amdgcn_sched_barrier(0);
-        const double v = DBG == 1 ? xt + xp : ilt_term2(K, xt, xp, L);
+        const double v = ilt_term2(K, xt, xp, L);
         if (active) val[(rloc + rpp * i) * SP + k] = v;
         __builtin_amdgcn_sched_barrier(0);  // keep the refill of slot u next to its use: no load clustering
       }
@@ -396,7 +377,7 @@ __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_
           const int r = rloc + rpp * i;
           const double t_u = th[u], p_u = ph[u];
           fetch(u, i + UB);
-          const double v = DBG == 1 ? t_u + p_u : ilt_term(K, t_u, p_u, L);
+          const double v = ilt_term(K, t_u, p_u, L);
           if (r < rows_here) val[r * SP + k] = v;
         }
       }
@@ -509,12 +490,11 @@ __device__ __forceinline__ void ilt_lds_load_tile(const char* g_lane, unsigned l
   }
 }
 
-// DBG (tools build only): 1 = loads + the plain sum of what they brought (memory only), 2 = arithmetic on run-time values, no loads
 // DEPTH: (theta, phi) region pairs per wavefront = tiles it keeps in flight.  1: eight wavefronts per CU, each requesting the next
 // tile's arrays as it reads the current ones out; 2 (S <= 17): four wavefronts per CU with two region pairs each -- a landed tile
 // no longer waits for its wavefront to finish the tile before it, at half the FP64 issue rate (one wavefront per SIMD), which
 // this kernel can afford (arithmetic-only 0.043 ms of 0.16).
-template <int S, bool GEN, int DBG, int DEPTH>
+template <int S, bool GEN, int DEPTH>
 __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_fourier_rows_kernel(const IltArgs a) {
   static_assert(S % 2 == 1, "row stride S doubles must be odd: conflict-free row-wise reads, 16-byte tile sizes");
   extern __shared__ __attribute__((aligned(16))) char rows_lds[];
@@ -554,16 +534,7 @@ __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_four
   unsigned rem = (unsigned)(row - n * d);
   double t_prev = __builtin_nan(""), sc = 0.0;  // the row scale e^{gamma t}/T is rebuilt only when the row's t changes
 
-  if (DBG == 2) {
-    for (int64_t tile = w0; tile < nfull; tile += W) {
-      const double acc = ilt_row_sum<S, GEN>(K, tab, [&](int k, double* th, double* ph) {
-        *th = a.alpha * (double)(lane + k) + (double)tile * 1e-7;
-        *ph = a.alpha * (double)(lane + 3 * k);
-      });
-      __builtin_nontemporal_store(row_scale(0.125) * acc, a.x + row);
-      row += step;
-    }
-  } else if (w0 < nfull) {
+  if (w0 < nfull) {
     // queue of this wavefront's vector-memory loads, oldest first, at the head of iteration n:
     //   theta_n (LPT)  phi_n (LPT)            [+ the store of x_(n-1), which no wait below depends on]
     // The row's t is requested at the head of the iteration that uses it and consumed behind a wait of its own: its register must
@@ -615,17 +586,10 @@ __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_four
       for (int k = 0; k < S; ++k) ph[k] = lrow_p[k];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       req_phi(nxt, has_next, par);                    // queue: [..,] t_n, theta_(n+DEPTH), phi_(n+DEPTH)
-      double acc;
-      if (DBG == 1) {
-        acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < S; ++k) acc += th[k] + ph[k];
-      } else {
-        acc = ilt_row_sum<S, GEN>(K, tab, [&](int k, double* t_o, double* p_o) {
-          *t_o = th[k];
-          *p_o = ph[k];
-        });
-      }
+      const double acc = ilt_row_sum<S, GEN>(K, tab, [&](int k, double* t_o, double* p_o) {
+        *t_o = th[k];
+        *p_o = ph[k];
+      });
       asm volatile("s_waitcnt vmcnt(%1)" : "+v"(t_row) : "n"(2 * LPT) : "memory");  // t_n: the next tile's loads are behind it
       if (t_row != t_prev) {  // (planning and training batches share one t: skipped after the first tile)
         sc = row_scale(t_row);
@@ -640,7 +604,7 @@ __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_four
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last iteration's stand-in loads
   }
   // the ragged last tile (fewer than 64 rows): the wavefront whose turn it would be reads its rows straight from memory
-  if (DBG != 2 && nfull * 64 < rows_total && nfull % W == w0) {
+  if (nfull * 64 < rows_total && nfull % W == w0) {
     const int64_t r = nfull * 64 + lane;
     if (r < rows_total) {
       const double* rt = a.theta + r * S;
@@ -669,17 +633,17 @@ static bool lds_attr_once(F* fn, size_t shmem, std::atomic<unsigned long long>& 
 }
 // true when the row-per-lane kernel takes the launch: an odd term count 3 .. 33 (row-wise LDS reads are conflict-free for an
 // odd stride; the reference's default 17, its de Hoog ablation's 33, fixed Talbot's 17) and 16-byte aligned inputs
-template <int S, bool GEN, int DBG, int DEPTH = 1>
+template <int S, bool GEN, int DEPTH>
 static bool launch_rows_instance(const IltArgs& a, hipStream_t s, hipError_t* err) {
   constexpr int SLOT = (64 * S * 8 + 1023) / 1024 * 1024;
   constexpr size_t shmem = (size_t)4 * DEPTH * 2 * SLOT + 2 * S * 8;  // four wavefronts' theta / phi slots + the (phase, weight) table
   static std::atomic<unsigned long long> attr_done{0};
-  if (!lds_attr_once(ilt_fourier_rows_kernel<S, GEN, DBG, DEPTH>, shmem, attr_done)) return false;
+  if (!lds_attr_once(ilt_fourier_rows_kernel<S, GEN, DEPTH>, shmem, attr_done)) return false;
   const int64_t tiles = (a.N * a.d + 63) / 64;
   const int per_cu = (S <= 17 && DEPTH == 1) ? 2 : 1;  // workgroups of four wavefronts per CU (launch bounds, LDS)
   int64_t grid = (tiles + 3) / 4;
   if (grid > 256 * per_cu) grid = 256 * per_cu;
-  hipLaunchKernelGGL((ilt_fourier_rows_kernel<S, GEN, DBG, DEPTH>), dim3((unsigned)grid), dim3(256), shmem, s, a);
+  hipLaunchKernelGGL((ilt_fourier_rows_kernel<S, GEN, DEPTH>), dim3((unsigned)grid), dim3(256), shmem, s, a);
   *err = hipGetLastError();
   return true;
 }
@@ -688,34 +652,12 @@ static bool launch_ilt_fourier_rows(const IltArgs& a, hipStream_t s, hipError_t*
   if (a.lin_wr != nullptr && a.lin_wi == nullptr) return false;
   if ((((uintptr_t)a.theta) | ((uintptr_t)a.phi)) & 15) return false;  // 16-byte loads
   const bool gen = a.lin_wr != nullptr || a.scale != 2.0;
-#if NLC_ILT_EXPERIMENTS
-  static const int dbg_env = [] {
-    const char* ev = std::getenv("NLC_ILT_DBG");
-    return ev ? std::atoi(ev) : 0;
-  }();
-  static const int rows_env = [] {
-    const char* ev = std::getenv("NLC_ILT_ROWS");
-    return ev ? std::atoi(ev) : 1;
-  }();
-  if (!rows_env) return false;
-  static const int depth_env = [] {
-    const char* ev = std::getenv("NLC_ILT_DEPTH");
-    return ev ? std::atoi(ev) : 2;
-  }();
-  if (a.S == 17 && !gen && depth_env == 1) {
-    if (dbg_env == 1) return launch_rows_instance<17, false, 1, 1>(a, s, err);
-    if (dbg_env == 2) return launch_rows_instance<17, false, 2, 1>(a, s, err);
-    return launch_rows_instance<17, false, 0, 1>(a, s, err);
-  }
-  if (a.S == 17 && !gen && dbg_env == 1) return launch_rows_instance<17, false, 1, 2>(a, s, err);
-  if (a.S == 17 && !gen && dbg_env == 2) return launch_rows_instance<17, false, 2, 2>(a, s, err);
-#endif
   switch (a.S) {
   // two tiles in flight per wavefront where two region pairs fit four wavefronts' LDS (S <= 17): 0.160 -> 0.154 ms at S = 17
-#define NLC_ROWS_CASE(SS)                                                                                    \
-  case SS:                                                                                                   \
-    return gen ? launch_rows_instance<SS, true, 0, (SS <= 17 ? 2 : 1)>(a, s, err)                            \
-               : launch_rows_instance<SS, false, 0, (SS <= 17 ? 2 : 1)>(a, s, err);
+#define NLC_ROWS_CASE(SS)                                                                                 \
+  case SS:                                                                                                \
+    return gen ? launch_rows_instance<SS, true, (SS <= 17 ? 2 : 1)>(a, s, err)                            \
+               : launch_rows_instance<SS, false, (SS <= 17 ? 2 : 1)>(a, s, err);
     NLC_ROWS_CASE(3) NLC_ROWS_CASE(5) NLC_ROWS_CASE(7) NLC_ROWS_CASE(9) NLC_ROWS_CASE(11) NLC_ROWS_CASE(13) NLC_ROWS_CASE(15)
     NLC_ROWS_CASE(17) NLC_ROWS_CASE(19) NLC_ROWS_CASE(21) NLC_ROWS_CASE(23) NLC_ROWS_CASE(25) NLC_ROWS_CASE(27) NLC_ROWS_CASE(29)
     NLC_ROWS_CASE(31) NLC_ROWS_CASE(33)
@@ -733,9 +675,6 @@ hipError_t launch_ilt_fourier(const IltArgs& a_in, hipStream_t s) {
     hipError_t e2 = hipSuccess;
     if (launch_ilt_fourier_rows(a, s, &e2)) return e2;
   }
-#if NLC_ILT_EXPERIMENTS
-  if (a.lin_wr != nullptr && std::getenv("NLC_ILT_LINEAR_ROWS")) return hipErrorInvalidValue;  // time the one-thread-per-row kernel
-#endif
   // rows per block tile = rpp * iters: one thread per row for the final sum (<= 256), LDS tile under 60 KiB
   const int SP = a.S | 1;
   a.rpp = 256 / a.S;
@@ -747,55 +686,28 @@ hipError_t launch_ilt_fourier(const IltArgs& a_in, hipStream_t s) {
   const int rows = a.rpp * a.iters;
   const int64_t nblk = (rows_total + rows - 1) / rows;
   // persistent grid: 1024-4096 blocks measured the same within run-to-run noise (round 1)
-  int64_t cap = 2048;
-  a.dbg = 0;
-#if NLC_ILT_EXPERIMENTS
-  // tools build only (make EXTRA_kernels_ilt=-DNLC_ILT_EXPERIMENTS=1): grid size and the two timing variants of the
-  // kernel (1 memory-only, 2 arithmetic-only) from the environment, read once
-  static const int64_t cap_env = [] {
-    const char* ev = std::getenv("NLC_ILT_GRID");
-    return (ev && std::atoll(ev) > 0) ? (int64_t)std::atoll(ev) : (int64_t)2048;
-  }();
-  static const int dbg_env = [] {
-    const char* ev = std::getenv("NLC_ILT_DBG");
-    return ev ? std::atoi(ev) : 0;
-  }();
-  cap = cap_env;
-  a.dbg = dbg_env;
-#endif
+  const int64_t cap = 2048;
   const unsigned grid = (unsigned)(nblk < cap ? nblk : cap);
   const size_t shmem = (size_t)rows * SP * sizeof(double);
-#define NLC_ILT_LAUNCH(D)                                                                              \
-  switch (a.iters) {                                                                                   \
-    case 8: hipLaunchKernelGGL((ilt_fourier_kernel<D, 8>), dim3(grid), dim3(256), shmem, s, a); break;   \
-    case 16: hipLaunchKernelGGL((ilt_fourier_kernel<D, 16>), dim3(grid), dim3(256), shmem, s, a); break; \
-    case 24: hipLaunchKernelGGL((ilt_fourier_kernel<D, 24>), dim3(grid), dim3(256), shmem, s, a); break; \
-    case 32: hipLaunchKernelGGL((ilt_fourier_kernel<D, 32>), dim3(grid), dim3(256), shmem, s, a); break; \
-    default: hipLaunchKernelGGL((ilt_fourier_kernel<D, 0>), dim3(grid), dim3(256), shmem, s, a); break;  \
-  }
   if (a.lin_wr != nullptr) {
     // fixed Talbot / Stehfest: the same stream with per-term phase and weight from the algorithm's tables
     if (a.lin_wi == nullptr) return hipErrorInvalidValue;
     switch (a.iters) {
-      case 8: hipLaunchKernelGGL((ilt_fourier_kernel<0, 8, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      case 16: hipLaunchKernelGGL((ilt_fourier_kernel<0, 16, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      case 24: hipLaunchKernelGGL((ilt_fourier_kernel<0, 24, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      case 32: hipLaunchKernelGGL((ilt_fourier_kernel<0, 32, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      default: hipLaunchKernelGGL((ilt_fourier_kernel<0, 0, true>), dim3(grid), dim3(256), shmem, s, a); break;
+      case 8: hipLaunchKernelGGL((ilt_fourier_kernel<8, true>), dim3(grid), dim3(256), shmem, s, a); break;
+      case 16: hipLaunchKernelGGL((ilt_fourier_kernel<16, true>), dim3(grid), dim3(256), shmem, s, a); break;
+      case 24: hipLaunchKernelGGL((ilt_fourier_kernel<24, true>), dim3(grid), dim3(256), shmem, s, a); break;
+      case 32: hipLaunchKernelGGL((ilt_fourier_kernel<32, true>), dim3(grid), dim3(256), shmem, s, a); break;
+      default: hipLaunchKernelGGL((ilt_fourier_kernel<0, true>), dim3(grid), dim3(256), shmem, s, a); break;
     }
     return hipGetLastError();
   }
-#if NLC_ILT_EXPERIMENTS
-  if (a.dbg == 1) {
-    NLC_ILT_LAUNCH(1)
-  } else if (a.dbg == 2) {
-    NLC_ILT_LAUNCH(2)
-  } else
-#endif
-  {
-    NLC_ILT_LAUNCH(0)
+  switch (a.iters) {
+    case 8: hipLaunchKernelGGL((ilt_fourier_kernel<8>), dim3(grid), dim3(256), shmem, s, a); break;
+    case 16: hipLaunchKernelGGL((ilt_fourier_kernel<16>), dim3(grid), dim3(256), shmem, s, a); break;
+    case 24: hipLaunchKernelGGL((ilt_fourier_kernel<24>), dim3(grid), dim3(256), shmem, s, a); break;
+    case 32: hipLaunchKernelGGL((ilt_fourier_kernel<32>), dim3(grid), dim3(256), shmem, s, a); break;
+    default: hipLaunchKernelGGL((ilt_fourier_kernel<0>), dim3(grid), dim3(256), shmem, s, a); break;
   }
-#undef NLC_ILT_LAUNCH
   return hipGetLastError();
 }
 
@@ -1019,13 +931,6 @@ static bool launch_bwd_rows_instance(const IltBwdArgs& a, hipStream_t s, hipErro
 static bool launch_ilt_fourier_bwd_rows(const IltBwdArgs& a, hipStream_t s, hipError_t* err) {
   if (a.S < 3 || a.S > 33 || (a.S & 1) == 0 || a.scale != 2.0) return false;
   if ((((uintptr_t)a.theta) | ((uintptr_t)a.phi) | ((uintptr_t)a.gtheta) | ((uintptr_t)a.gphi)) & 15) return false;
-#if NLC_ILT_EXPERIMENTS
-  static const int rows_env = [] {
-    const char* ev = std::getenv("NLC_ILT_ROWS");
-    return ev ? std::atoi(ev) : 1;
-  }();
-  if (!rows_env) return false;
-#endif
   switch (a.S) {
 #define NLC_ROWS_CASE(SS) \
   case SS:                \

@@ -53,15 +53,8 @@ struct DehoogSlotTermsLane {
   __device__ __forceinline__ cplx term(int n) const { return buf[n % CH]; }
 };
 
-// diagonals per pass of dehoog_row (below): where a wavefront has its SIMD to itself / where two share one
-// (tools A/B: -DNLC_DEHOOG_SKEW_ALONE=n / -DNLC_DEHOOG_SKEW_SHARED=n, n = 1, 2, 4)
-#ifndef NLC_DEHOOG_SKEW_ALONE
-#define NLC_DEHOOG_SKEW_ALONE 4
-#endif
-#ifndef NLC_DEHOOG_SKEW_SHARED
-#define NLC_DEHOOG_SKEW_SHARED 2
-#endif
-constexpr int kDehoogSkewAlone = NLC_DEHOOG_SKEW_ALONE, kDehoogSkewShared = NLC_DEHOOG_SKEW_SHARED;
+// diagonals per pass of dehoog_row (below): where a wavefront has its SIMD to itself / where two share one (chosen among 1, 2, 4)
+constexpr int kDehoogSkewAlone = 4, kDehoogSkewShared = 2;
 
 // SRC: stage<S>(n) is called before term n whenever n % CH == 0 (it makes terms [n, n + CH) available), term(n) returns a_n.
 // Returns A_2M / B_2M, the continued fraction with the improved remainder; the caller scales Re by e^{gamma t} / T.

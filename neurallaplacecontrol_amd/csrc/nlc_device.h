@@ -44,18 +44,14 @@ __device__ __forceinline__ lptr opaque_lds(lptr p) {
 }
 __device__ __forceinline__ lptr opaque(lptr p) { return opaque_lds(p); }
 
-// NLC_GEMM_INTERLEAVE: issue order of one k-step -- 0: the MT fragment loads of the next k-step, then the MT MFMAs (rounds 1-3);
-// 1: MFMA, load, MFMA, load, ... (sched_group_barrier), every load issued in the shadow of an MFMA.  A vector load costs the
-// issuing wave ~17 clocks; a burst of MT of them in front of the k-step's first MFMA leaves the matrix pipe idle that long
-// when the SIMD holds one wave (round 4, nl_rollout_kernel at K = 16384: 1.240 -> 1.175 ms; profiles/r4_rollout_phase_clocks.md).
-#ifndef NLC_GEMM_INTERLEAVE
-#define NLC_GEMM_INTERLEAVE 1
-#endif
+// Issue order of one k-step: MFMA, load, MFMA, load, ... (sched_group_barrier), every load issued in the shadow of an MFMA.  A
+// vector load costs the issuing wave ~17 clocks; the MT fragment loads of the next k-step as a burst in front of the k-step's
+// first MFMA (rounds 1-3) left the matrix pipe idle that long when the SIMD holds one wave (round 4, nl_rollout_kernel at
+// K = 16384: 1.240 -> 1.175 ms; profiles/r4_rollout_phase_clocks.md).
 // (E: further loads the k-step carries for a LATER phase -- gemm_acc_head's `extra` -- spread over the same shadows; FRAGS = 0:
 // the last k-step, which fetches no fragments of its own)
 template <int MT, int E = 0, int FRAGS = 1, bool LDSW = false>
 __device__ __forceinline__ void gemm_kstep_order() {
-#if NLC_GEMM_INTERLEAVE
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     constexpr int kBase = E / MT, kRem = E % MT;
@@ -68,7 +64,6 @@ __device__ __forceinline__ void gemm_kstep_order() {
     if (nv == 4) __builtin_amdgcn_sched_group_barrier(kRd, 4, 0);
     if (nv >= 5) __builtin_amdgcn_sched_group_barrier(kRd, 5, 0);
   }
-#endif
 }
 
 // acc[m] (+)= sum_ks  Wp[ks][m] (x) bfrag(ks).  Wp is fragment-packed: Wp[(ks*MT + m)*64 + lane],
@@ -131,18 +126,13 @@ struct NoExtra {
   template <class KC>
   __device__ __forceinline__ void operator()(KC) const {}
 };
-// NLC_GEMM_PD: prefetch distance of the k loop in k-steps (the fragments of k-step ks + PD are issued during k-step ks).
-// Measured at the headline shape (round 4): 1 -> 1.183 ms, 2 -> 1.200, 3 -> 1.221: the fragments come back in time, more of
-// them in flight only costs.
-#ifndef NLC_GEMM_PD
-#define NLC_GEMM_PD 1
-#endif
+// The fragments of k-step ks + 1 are issued during k-step ks.  Prefetch distances measured at the headline shape (round 4):
+// 1 -> 1.183 ms, 2 -> 1.200, 3 -> 1.221: the fragments come back in time, more of them in flight only costs.
 template <int MT, int MTOT, int KS, int EPK = 0, class WP, typename BF, typename EX = NoExtra>
 __device__ __forceinline__ void gemm_acc_head(v4d (&acc)[MT], const double (&a0)[MT], WP Wp, int m0, int lane, BF bfrag,
                                               EX extra = EX{}) {
   constexpr bool LDSW = std::is_same<WP, lptr>::value;
-  constexpr int PD = NLC_GEMM_PD < KS ? NLC_GEMM_PD : 1;
-  double a[PD + 1][MT];  // ring of fragment sets: k-step ks lives in a[ks % (PD + 1)]
+  double a[2][MT];  // current / next fragment set: k-step ks lives in a[ks % 2]
   // HBM / L2: a wave-uniform base advanced per k-step (SALU) + immediate tile offsets.  LDS: ONE per-lane base for the whole
   // matrix, every fragment at a compile-time offset from it (ds_read2st64_b64 reaches 255 tiles of 512 B), no address arithmetic.
   auto p = opaque(Wp + (size_t)m0 * 64);
@@ -158,27 +148,20 @@ __device__ __forceinline__ void gemm_acc_head(v4d (&acc)[MT], const double (&a0)
   };
 #pragma unroll
   for (int m = 0; m < MT; ++m) a[0][m] = a0[m];
-  // k-steps 1 .. PD - 1 before the loop (PD = 1: none)
-  static_for<PD - 1>([&](auto jc) {
-    constexpr int j = decltype(jc)::value + 1;
-    advance();
-#pragma unroll
-    for (int m = 0; m < MT; ++m) a[j][m] = frag(std::integral_constant<int, j>{}, m);
-  });
   double b_cur = bfrag(0), b_nxt = 0.0;
   static_for<KS>([&](auto ks_c) {
     constexpr int ks = decltype(ks_c)::value;
-    if constexpr (ks + PD < KS) {
+    if constexpr (ks + 1 < KS) {
       advance();
 #pragma unroll
-      for (int m = 0; m < MT; ++m) a[(ks + PD) % (PD + 1)][m] = frag(std::integral_constant<int, ks + PD>{}, m);
+      for (int m = 0; m < MT; ++m) a[(ks + 1) % 2][m] = frag(std::integral_constant<int, ks + 1>{}, m);
     }
     if (ks + 1 < KS) b_nxt = bfrag(ks + 1);
     extra(ks_c);  // (ks as a compile-time constant)
 #pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = mfma(a[ks % (PD + 1)][m], b_cur, acc[m]);
+    for (int m = 0; m < MT; ++m) acc[m] = mfma(a[ks % 2][m], b_cur, acc[m]);
     b_cur = b_nxt;
-    if (ks + PD < KS)
+    if (ks + 1 < KS)
       gemm_kstep_order<MT, EPK, 1, LDSW>();
     else
       gemm_kstep_order<MT, EPK, 0, LDSW>();

@@ -24,13 +24,7 @@ namespace i8 {
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kDigits = 7;
-#ifndef NLC_I8_DBG
-#define NLC_I8_DBG 0
-#endif
-#ifndef NLC_I8_LMIN
-#define NLC_I8_LMIN 5
-#endif
-constexpr int kLmin = NLC_I8_LMIN;                        // digit pairs with i + j < kLmin are dropped
+constexpr int kLmin = 5;                                   // digit pairs with i + j < kLmin are dropped (nlc_pack.h: kI8Lmin)
 constexpr int kLevels = 2 * (kDigits - 1) - kLmin + 1;     // levels kLmin .. 12
 constexpr int kTop = 2 * (kDigits - 1);                   // the highest level
 constexpr int kFrac = 54;                                  // fractional bits of both operands' fixed point
@@ -115,11 +109,7 @@ __device__ __forceinline__ void tile_mfma(v4i (&acc)[kLevels], const v4i (&a)[kD
 #pragma unroll
   for (int k = 0; k < o.n; ++k) {
     const int i = o.i[k], j = o.j[k];
-#if NLC_I8_DBG == 1  // tools only (timing): no MFMAs, the operands stay live
-    asm volatile("" : "+v"(acc[i + j - kLmin]) : "v"(a[i]), "v"(b[j]));
-#else
     acc[i + j - kLmin] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i + j - kLmin], 0, 0, 0);
-#endif
   }
 }
 
@@ -132,16 +122,6 @@ constexpr bool kMergedFactorShift = kLevels % 2 == 0;
 template <bool MERGE>
 __device__ __forceinline__ v4d recombine(const v4i (&acc)[kLevels], const v4d& rs, const v4d& pre) {
   v4d out;
-#if NLC_I8_DBG == 2  // tools only (timing): the MFMAs without their recombination
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int m = acc[0][r];
-#pragma unroll
-    for (int l = 1; l < kLevels; ++l) asm volatile("" : "+v"(m) : "v"(acc[l][r]));
-    out[r] = fma((double)m, rs[r], pre[r]);
-  }
-  return out;
-#endif
   double s[4];
   if (MERGE) {
     constexpr int NP = (kLevels + 1) / 2;

@@ -26,7 +26,6 @@ struct IltArgs {
   double t_div;  // de Hoog: t is divided by this (model time normalisation); 1 otherwise
   int t_stride;  // de Hoog: 1 = one t per point, 0 = t[0] for all points
   int rpp, iters;  // rows per pass / passes per block tile (set by the launcher)
-  int dbg;         // 0 normal; timing experiments only: 1 memory-only, 2 arithmetic-only
   // de Hoog, planner path: when non-NULL, (fre, fim) are SLOT-major (8*nt3, N) arrays -- element e of every sample
   // contiguous, as the representation kernel's MFMA epilogue stores them -- and eidx[c*S + k] names the slot of term k
   // of dim c; one wavefront then owns 64 consecutive samples of ONE dim and every load is a full 512-B line

@@ -7,16 +7,6 @@
 #include "nlc_kernels.h"
 #include "nlc_rollout.h"
 
-// NLC_ROLLOUT_LDS_TABS: nl_rollout_kernel reads the network's small tables from a workgroup copy in LDS (NlTabsLds, nlc_rollout.h)
-#ifndef NLC_ROLLOUT_LDS_TABS
-#define NLC_ROLLOUT_LDS_TABS 1
-#endif
-// NLC_ROLLOUT_LDS_W2: layer 2's whole matrix in LDS as well (154 KB).  Measured (round 4, K = 16384): 1.105 -> 1.146 ms -- the
-// k loop's fragment reads are hidden behind its MFMAs either way, and the LDS reads of the other three waves are not free.  Off.
-#ifndef NLC_ROLLOUT_LDS_W2
-#define NLC_ROLLOUT_LDS_W2 0
-#endif
-
 namespace nlc {
 
 // ------------------------------------------------------------------ T-step rollout (planner)
@@ -62,18 +52,15 @@ __global__ __launch_bounds__(256) void nl_rollout_kernel(const RolloutArgs a) {
   clk.start();
   // One wave per SIMD has nobody to hide a load behind: everything a step reads that does not depend on the state -- the next
   // step's GRU latents, this step's action, noise and nominal control, the next evaluation's layer-1 tiles -- is issued one phase
-  // or one step ahead (NLC_EVAL_PIPELINE, nlc_rollout.h).
-#if NLC_ROLLOUT_LDS_TABS
-  // (layer 2's matrix too where everything fits the CU's 160 KB)
-  constexpr bool kW2 = NLC_ROLLOUT_LDS_W2 && NlTabsLds<HT, NT3, true>::kDoubles * 8 <= 160 * 1024;
-  using Tabs = NlTabsLds<HT, NT3, kW2>;
+  // or one step ahead (nl_eval_impl's PIPE, nlc_rollout.h).  The network's small tables are read from a workgroup copy in LDS.
+  // (Layer 2's whole matrix in LDS too, 154 KB, measured 1.105 -> 1.146 ms at K = 16384, round 4,
+  // profiles/r4_rollout_phase_clocks.md: the k loop's fragment reads are hidden behind its MFMAs either way, and the LDS reads
+  // of the other three waves are not free.  Not done.)
+  using Tabs = NlTabsLds<HT, NT3>;
   __shared__ double tabs_sm[Tabs::kDoubles];
   Tabs::fill(tabs_sm, n, threadIdx.x, 256);
   __syncthreads();
   const Tabs tabs{(lptr)tabs_sm};
-#else
-  const NlTabsGlobal tabs;
-#endif
   // (hidden_units 256: layer 1 alone is 192 registers -- loaded where it is used)
   using Pre = typename std::conditional<(HT <= 8), NlL1Pre<HT>, NlNoPre>::type;
   Pre l1;

@@ -100,10 +100,7 @@ inline IltSlots make_ilt_slots(int d, int S, int nt3) {
 // digits, X = sum_i d_i 256^i (d_0 .. d_5 in [-128, 127] by the 128-per-digit bias, d_6 the signed rest).
 constexpr int kI8Digits = 7;
 constexpr int kI8Frac = 54;                          // nlc_i8gemm.h: kFrac
-#ifndef NLC_I8_LMIN
-#define NLC_I8_LMIN 5
-#endif
-constexpr int kI8Lmin = NLC_I8_LMIN;                 // nlc_i8gemm.h: kLmin
+constexpr int kI8Lmin = 5;                           // nlc_i8gemm.h: kLmin
 constexpr int kI8RowExp2 = 8 * 12 - 2 * kI8Frac;     // nlc_i8gemm.h: kRowExp2 (the recombined sum is in units of 256^12 2^-108)
 inline void i8_digits(double x, signed char d[kI8Digits]) {  // |x| <= 1
   const long long X = std::llrint(std::ldexp(x, kI8Frac));

@@ -9,19 +9,10 @@
 #include "nlc_envcost.h"
 #include "nlc_kernels.h"
 
-// hidden-layer activation of the representation MLP.  The short form of nlc_math.h (tanh_pair_fast: 20 % fewer FP64
-// instructions, 1.5e-13 absolute) was measured on one box against the few-ulp tanh_pair_d (round 3, tools/bench_ab.sh with
-// -DNLC_HIDDEN_TANH_FAST=1): nl_rollout_kernel 1.234 -> 1.223 ms at K = 16384 (-0.25 % of the command), but the fused
-// small-shard body 0.673 -> 0.687 ms at K = 2048 under every static schedule (+2 %): the chains are latency-bound, not
-// instruction-bound.  Not shipped.
-#ifndef NLC_HIDDEN_TANH_FAST
-#define NLC_HIDDEN_TANH_FAST 0
-#endif
-#if NLC_HIDDEN_TANH_FAST
-#define NLC_HIDDEN_TANH_PAIR m::tanh_pair_fast
-#else
-#define NLC_HIDDEN_TANH_PAIR m::tanh_pair_d
-#endif
+// The hidden-layer activation of the representation MLP is the few-ulp m::tanh_pair_d.  The short form of nlc_math.h
+// (tanh_pair_fast: 20 % fewer FP64 instructions, 1.5e-13 absolute) was measured against it on one box (round 3):
+// nl_rollout_kernel 1.234 -> 1.223 ms at K = 16384 (-0.25 % of the command), but the fused small-shard body 0.673 -> 0.687 ms
+// at K = 2048 under every static schedule (+2 %): the chains are latency-bound, not instruction-bound.  Not done.
 
 // -DNLC_PHASE_CLOCKS=1 (tools only: tools/rollout_phase_clocks.py, a separate build of the library): shader-clock stamps at the
 // phase boundaries of one model evaluation, summed per wave in SGPRs and added to nlc_phase_clk[] when the wave retires.  The
@@ -157,21 +148,15 @@ struct FOut {
   int64_t n_rows;   // > 0: slot-major (8*nt3, n_rows) arrays -- slot 4g+q of sample `row` at (4g+q)*n_rows + row, so one
                     // store instruction writes four 128-B runs (16 consecutive samples per lane group q)
 };
-// NLC_EVAL_PIPELINE (A/B switch, tools/bench_ab.sh): where the loads that are NOT a GEMM's own k-step fragments are issued --
-// bias tiles, each GEMM's first fragments, the ILT coefficient tiles, a horizon loop's next layer 1.
-//   0  at the head of the phase that consumes them (rounds 1-3)
-//   1  inside the k loop of the GEMM BEFORE that phase, a few per k-step, scheduled into the MFMA shadows together with the
-//      k-step's own fragments (gemm_acc_head's `extra`).  One wave per SIMD has nobody to hide behind, and a vector load costs
-//      its wave ~17 issue clocks wherever no MFMA is running (tools/rollout_phase_clocks.py: moving the loads in front of the
-//      activation phase made that phase longer by exactly their issue time).
+// Where nl_eval_impl issues the loads that are NOT a GEMM's own k-step fragments -- bias tiles, each GEMM's first fragments,
+// the ILT coefficient tiles, a horizon loop's next layer 1 (its PIPE):
+//   pipelined (hidden_units <= 128, NT3 <= 17)  inside the k loop of the GEMM BEFORE the phase that consumes them, a few per k-step,
+//      scheduled into the MFMA shadows together with the k-step's own fragments (gemm_acc_head's `extra`).  One wave per SIMD
+//      has nobody to hide behind, and a vector load costs its wave ~17 issue clocks wherever no MFMA is running
+//      (tools/rollout_phase_clocks.py: moving the loads in front of the activation phase made that phase longer by exactly
+//      their issue time).
+//   otherwise  at the head of the phase that consumes them (the form of rounds 1-3; wider layers need the registers elsewhere)
 // Arithmetic, MFMA order per tile and ILT sum order are the same in both: same bits.
-// NLC_L3_SINGLE_PASS: 1 = layer 3 as one GEMM over its NT3 output tiles, 0 = two halves (round 3).
-#ifndef NLC_EVAL_PIPELINE
-#define NLC_EVAL_PIPELINE 1
-#endif
-#ifndef NLC_L3_SINGLE_PASS
-#define NLC_L3_SINGLE_PASS 0
-#endif
 // Where the SMALL tables of the network are read from (bias vectors, layer-1 fragments, ILT coefficient tiles: 23 KB at the
 // headline shape) -- every access returns a pointer the optimiser cannot see through, so nothing is hoisted out of a horizon loop.
 //   NlTabsGlobal  the packed arrays in HBM / L2 (NlNetArgs)
@@ -186,20 +171,12 @@ struct NlTabsGlobal {
   __device__ __forceinline__ gptr cp(const NlNetArgs& n) const { return opaque(n.Cp); }
   __device__ __forceinline__ const double* w2(const NlNetArgs& n) const { return n.W2p; }  // (laundered by the GEMM)
 };
-// W2: layer 2's whole fragment-packed matrix as well (h^2 doubles: 128 KB at hidden_units 128 -- with the small tables that is
-// 154 KB of the CU's 160 KB, one workgroup per CU, which the kernel's one wave per SIMD implies anyway)
-template <int HT, int NT3, bool W2 = false>
+template <int HT, int NT3>
 struct NlTabsLds {
   static constexpr int kB1 = 0, kB2 = 16 * HT, kB3 = 32 * HT, kW1 = kB3 + 16 * NT3, kCp = kW1 + 2 * HT * 64;
-  static constexpr int kW2 = kCp + 2 * NT3 * 64;
-  static constexpr int kDoubles = kW2 + (W2 ? HT * HT * 4 * 64 : 0);
+  static constexpr int kDoubles = kCp + 2 * NT3 * 64;
   lptr base;
-  __device__ __forceinline__ auto w2(const NlNetArgs& n) const {
-    if constexpr (W2)
-      return (lptr)(base + kW2);
-    else
-      return n.W2p;
-  }
+  __device__ __forceinline__ const double* w2(const NlNetArgs& n) const { return n.W2p; }  // (layer 2's matrix stays in HBM / L2)
   __device__ __forceinline__ lptr b1(const NlNetArgs&) const { return opaque_lds(base + kB1); }
   __device__ __forceinline__ lptr b2(const NlNetArgs&) const { return opaque_lds(base + kB2); }
   __device__ __forceinline__ lptr b3p(const NlNetArgs&) const { return opaque_lds(base + kB3); }
@@ -214,9 +191,6 @@ struct NlTabsLds {
     for (int i = tid; i < 16 * NT3; i += nthreads) sm[kB3 + i] = n.b3p[i];
     for (int i = tid; i < 2 * HT * 64; i += nthreads) sm[kW1 + i] = n.W1p[i];
     for (int i = tid; i < 2 * NT3 * 64; i += nthreads) sm[kCp + i] = n.Cp[i];
-    if constexpr (W2) {
-      for (int i = tid; i < HT * HT * 4 * 64; i += nthreads) sm[kW2 + i] = n.W2p[i];
-    }
   }
 };
 
@@ -253,7 +227,7 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
                                             const double* sph_row, PhaseClk* pc, PRE& pre, const TABS& tabs = TABS{}) {
   constexpr int KS = HT * 4;  // h / 4
   // (wider output layers, hidden_units 256: the registers are needed elsewhere)
-  constexpr bool PIPE = NLC_EVAL_PIPELINE != 0 && NT3 <= 17 && HT <= 8;
+  constexpr bool PIPE = NT3 <= 17 && HT <= 8;
   constexpr bool HAS_PRE = !std::is_same<PRE, NlNoPre>::value;
   auto phase = [&](int i) {
     if (NLC_PHASE_CLOCKS && pc != nullptr) pc->mark(i);
@@ -320,10 +294,8 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
       h1[m] = mfma(w1[ks * HT + m], ks == 0 ? p0 : p1, h1[m]);
       if (PIPE) {
         static_for<IPM>([&](auto e) { item2(std::integral_constant<int, km * IPM + decltype(e)::value>{}); });
-#if NLC_GEMM_INTERLEAVE
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, IPM, 0);
-#endif
       }
     });
     if (PIPE) __builtin_amdgcn_sched_barrier(0);
@@ -336,7 +308,7 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
 #pragma unroll
       for (int r = 0; r < 4; r += 2) {
         double ta, tb;
-        NLC_HIDDEN_TANH_PAIR(h1[j][r], h1[j][r + 1], &ta, &tb);
+        m::tanh_pair_d(h1[j][r], h1[j][r + 1], &ta, &tb);
         h1[j][r] = ta;
         h1[j][r + 1] = tb;
       }
@@ -346,11 +318,13 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
 
   // ---- layer 2; in its shadow: the bias tiles, first fragments and ILT coefficient tiles of layer 3's first pass.
   // Layer 3 runs in two passes over its output tiles (round 3): half the accumulators and prefetch registers live at a time.
-  constexpr int NA = NLC_L3_SINGLE_PASS ? NT3 : (NT3 + 1) / 2, NB = NT3 - NA, NB1 = NB > 0 ? NB : 1;
+  // (one GEMM over all NT3 tiles was the form before.  Every instantiated NT3 is >= 7 -- NLC_FOR_NT3 -- so both passes exist.)
+  static_assert(NT3 >= 2, "layer 3 runs in two passes");
+  constexpr int NA = (NT3 + 1) / 2, NB = NT3 - NA;
   // coefficient tiles fetched ahead per output tile (not pipelined: read where they are used, as LIN's second table always is)
   constexpr int NCP = (WRITE_F || !PIPE) ? 0 : 2;
-  v4d oa[NA], ob[NB1];
-  double a3a[NA], a3b[NB1], cpa[2 * NA], cpb[2 * NB1];
+  v4d oa[NA], ob[NB];
+  double a3a[NA], a3b[NB], cpa[2 * NA], cpb[2 * NB];
   const auto b3q = tabs.b3p(n) + q;
   gptr w3 = opaque(n.W3p);
   const auto cp = tabs.cp(n);
@@ -365,14 +339,12 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
   };
   auto item3b = [&](auto ic) {
     constexpr int i = decltype(ic)::value;
-    if constexpr (NB > 0) {
-      if constexpr (i < 4 * NB)
-        ob[i >> 2][i & 3] = b3q[16 * (NA + (i >> 2)) + 4 * (i & 3)];
-      else if constexpr (i < 5 * NB)
-        a3b[i - 4 * NB] = w3[(NA + i - 4 * NB) * 64 + lane];
-      else if constexpr (i < (5 + NCP) * NB)
-        cpb[i - 5 * NB] = cp[(2 * NA + i - 5 * NB) * 64 + lane];
-    }
+    if constexpr (i < 4 * NB)
+      ob[i >> 2][i & 3] = b3q[16 * (NA + (i >> 2)) + 4 * (i & 3)];
+    else if constexpr (i < 5 * NB)
+      a3b[i - 4 * NB] = w3[(NA + i - 4 * NB) * 64 + lane];
+    else if constexpr (i < (5 + NCP) * NB)
+      cpb[i - 5 * NB] = cp[(2 * NA + i - 5 * NB) * 64 + lane];
   };
   constexpr int N3A = (5 + NCP) * NA, N3B = (5 + NCP) * NB;
   constexpr int E2 = PIPE ? (N3A + KS - 1) / KS : 0;
@@ -385,7 +357,7 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
 #pragma unroll
     for (int r = 0; r < 4; r += 2) {
       double ta, tb;
-      NLC_HIDDEN_TANH_PAIR(h2[j][r], h2[j][r + 1], &ta, &tb);
+      m::tanh_pair_d(h2[j][r], h2[j][r + 1], &ta, &tb);
       h2[j][r] = ta;
       h2[j][r + 1] = tb;
     }
@@ -444,27 +416,20 @@ __device__ __forceinline__ v4d nl_eval_impl(const NlNetArgs& n, int lane, int q,
     if constexpr (HAS_PRE)
       static_for<EL1>([&](auto e) { pre.template item<decltype(kc)::value * EL1 + decltype(e)::value>(b1q, w1n, lane); });
   };
-  if constexpr (NB > 0) {
-    // ---- layer 3, first pass; in its shadow: the second pass's tiles
-    constexpr int E3A = PIPE ? (N3B + KS - 1) / KS : 0;
-    gemm_acc_head<NA, NT3, KS, E3A>(oa, a3a, n.W3p, 0, lane, [&](int ks) { return h2[ks >> 2][ks & 3]; }, [&](auto kc) {
-      static_for<E3A>([&](auto e) { item3b(std::integral_constant<int, decltype(kc)::value * E3A + decltype(e)::value>{}); });
-    });
-    phase(PhaseClk::kL3a);
-    epilogue(oa, cpa, std::integral_constant<int, 0>{}, std::integral_constant<int, NA>{});
-    phase(PhaseClk::kEpiA);
-    if (!PIPE) static_for<N3B>(item3b);
-    // ---- layer 3, second pass; in its shadow: the next evaluation's layer 1
-    gemm_acc_head<NB1, NT3, KS, EL1>(ob, a3b, n.W3p, NA, lane, [&](int ks) { return h2[ks >> 2][ks & 3]; }, next_l1);
-    phase(PhaseClk::kL3b);
-    epilogue(ob, cpb, std::integral_constant<int, NA>{}, std::integral_constant<int, NB>{});
-    phase(PhaseClk::kEpiB);
-  } else {
-    gemm_acc_head<NA, NT3, KS, EL1>(oa, a3a, n.W3p, 0, lane, [&](int ks) { return h2[ks >> 2][ks & 3]; }, next_l1);
-    phase(PhaseClk::kL3a);
-    epilogue(oa, cpa, std::integral_constant<int, 0>{}, std::integral_constant<int, NA>{});
-    phase(PhaseClk::kEpiA);
-  }
+  // ---- layer 3, first pass; in its shadow: the second pass's tiles
+  constexpr int E3A = PIPE ? (N3B + KS - 1) / KS : 0;
+  gemm_acc_head<NA, NT3, KS, E3A>(oa, a3a, n.W3p, 0, lane, [&](int ks) { return h2[ks >> 2][ks & 3]; }, [&](auto kc) {
+    static_for<E3A>([&](auto e) { item3b(std::integral_constant<int, decltype(kc)::value * E3A + decltype(e)::value>{}); });
+  });
+  phase(PhaseClk::kL3a);
+  epilogue(oa, cpa, std::integral_constant<int, 0>{}, std::integral_constant<int, NA>{});
+  phase(PhaseClk::kEpiA);
+  if (!PIPE) static_for<N3B>(item3b);
+  // ---- layer 3, second pass; in its shadow: the next evaluation's layer 1
+  gemm_acc_head<NB, NT3, KS, EL1>(ob, a3b, n.W3p, NA, lane, [&](int ks) { return h2[ks >> 2][ks & 3]; }, next_l1);
+  phase(PhaseClk::kL3b);
+  epilogue(ob, cpb, std::integral_constant<int, NA>{}, std::integral_constant<int, NB>{});
+  phase(PhaseClk::kEpiB);
   if constexpr (!PIPE && HAS_PRE) pre.load(n, lane, q, tabs);
   return ax[0];
 }
@@ -479,16 +444,12 @@ __device__ __forceinline__ v4d nl_eval(const NlNetArgs& n, int lane, int q, doub
 // NTW = 2 .. 6 (layer 3) MFMAs per wave -- 128 .. 192 clocks at hidden_units 128 -- while a weight fragment takes ~250 clocks from
 // the L2.  split_gemm<.., D> keeps D k-steps of fragments in flight (a ring of D x NT registers, every index a compile-time
 // constant of the unrolled loop); D = 1 is the loop of rounds 1-4 (fragments of step ks + 1 requested at step ks).  Same MFMAs in
-// the same order: bit-identical results for every D.  MEASURED (same box, K = 2048 / 8192 / cfg5; tools/split_ab.py): the
+// the same order: bit-identical results for every D.  MEASURED (same box, K = 2048 / 8192 / cfg5; profiles/r5_split_ab*.json): the
 // stand-alone split rollout and the de Hoog planner's representation launch do not move for D = 2 .. 6 (the compiler already
 // hoists ~5 k-steps of loads to the loop head; D = 4 costs cfg5 4 % through the launch's registers); the fused body's chains,
 // whose fragment loads compete with the encoder role's weight streams, gain 1.3 % at D = 4 (675.6 -> 667.1 us per launch):
 // D = 4 there, 1 elsewhere.
-#ifdef NLC_SPLIT_PREFETCH
-constexpr int kSplitPrefetch = NLC_SPLIT_PREFETCH, kSplitPrefetchFused = NLC_SPLIT_PREFETCH;
-#else
 constexpr int kSplitPrefetch = 1, kSplitPrefetchFused = 4;
-#endif
 // acc[i] += sum_ks A_frag(ks, i) * Hb[ks]: `base` = fragment (ks = 0, tile 0) of this wave's tiles, `step` doubles between k-steps,
 // off(i) = offset in doubles of the wave's i-th output tile (compile-time i), Hb = the (KS, 64) activation image in LDS.
 template <int NT, int KS, int D, class OFF>
@@ -549,13 +510,7 @@ __device__ __forceinline__ void split_gemm(v4d (&acc)[NT], gptr base, const int 
 // Same operations on the same operands in the same order: bit-identical.  Measured (K = 2048 / 8192, T = 40, same box):
 // nl_rollout_split_kernel 425.8 -> 402.9 us / 714 -> 694 us; the fused one-launch body, whose chains are paced by the encoder
 // role beside them, does not gain (675.6 -> 683.9 us: the extra live values cost registers) and keeps wave 0.
-constexpr int kSplitCostWaveStandalone = 3, kSplitCostWaveFused = 0;
-// (tools: -DNLC_SPLIT_COST_WAVE=n / -DNLC_SPLIT_PREFETCH=n override both bodies' settings for A/B builds, tools/build_split_variants.sh)
-#ifdef NLC_SPLIT_COST_WAVE
-constexpr int kCwStandalone = NLC_SPLIT_COST_WAVE, kCwFused = NLC_SPLIT_COST_WAVE;
-#else
-constexpr int kCwStandalone = kSplitCostWaveStandalone, kCwFused = kSplitCostWaveFused;
-#endif
+constexpr int kCwStandalone = 3, kCwFused = 0;
 
 // ------------------------------------------------------------------ latency-split rollout of one 16-sample tile
 // nl_rollout_kernel gives every wavefront a whole 16-sample tile, which fills the chip only when K/16 >= 1024
@@ -706,7 +661,7 @@ __device__ __forceinline__ double rollout_split_tile(const RolloutArgs& a, int64
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
           double ta, tb;
-          NLC_HIDDEN_TANH_PAIR(acc[i][r], acc[i][r + 1], &ta, &tb);
+          m::tanh_pair_d(acc[i][r], acc[i][r + 1], &ta, &tb);
           H1[(4 * (TW * wv + i) + r) * 64 + lane] = ta;
           H1[(4 * (TW * wv + i) + r + 1) * 64 + lane] = tb;
         }
@@ -728,7 +683,7 @@ __device__ __forceinline__ double rollout_split_tile(const RolloutArgs& a, int64
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
           double ta, tb;
-          NLC_HIDDEN_TANH_PAIR(acc[i][r], acc[i][r + 1], &ta, &tb);
+          m::tanh_pair_d(acc[i][r], acc[i][r + 1], &ta, &tb);
           H2[(4 * (TW * wv + i) + r) * 64 + lane] = ta;
           H2[(4 * (TW * wv + i) + r + 1) * 64 + lane] = tb;
         }
@@ -853,7 +808,7 @@ __device__ __forceinline__ void repfunc_split_mlp(const NlNetArgs& n, const doub
 #pragma unroll
       for (int r = 0; r < 4; r += 2) {
         double ta, tb;
-        NLC_HIDDEN_TANH_PAIR(acc[i][r], acc[i][r + 1], &ta, &tb);
+        m::tanh_pair_d(acc[i][r], acc[i][r + 1], &ta, &tb);
         H1[(4 * (TW * wv + i) + r) * 64 + lane] = ta;
         H1[(4 * (TW * wv + i) + r + 1) * 64 + lane] = tb;
       }
@@ -874,7 +829,7 @@ __device__ __forceinline__ void repfunc_split_mlp(const NlNetArgs& n, const doub
 #pragma unroll
       for (int r = 0; r < 4; r += 2) {
         double ta, tb;
-        NLC_HIDDEN_TANH_PAIR(acc[i][r], acc[i][r + 1], &ta, &tb);
+        m::tanh_pair_d(acc[i][r], acc[i][r + 1], &ta, &tb);
         H2[(4 * (TW * wv + i) + r) * 64 + lane] = ta;
         H2[(4 * (TW * wv + i) + r + 1) * 64 + lane] = tb;
       }
@@ -959,7 +914,7 @@ __device__ __forceinline__ void repfunc_block_mlp(const NlNetArgs& n, const doub
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
           double ta, tb;
-          NLC_HIDDEN_TANH_PAIR(acc[i][s2][r], acc[i][s2][r + 1], &ta, &tb);
+          m::tanh_pair_d(acc[i][s2][r], acc[i][s2][r + 1], &ta, &tb);
           H1[s2 * KS * 64 + (4 * (TW * wave + i) + r) * 64 + lane] = ta;
           H1[s2 * KS * 64 + (4 * (TW * wave + i) + r + 1) * 64 + lane] = tb;
         }
@@ -1012,7 +967,7 @@ __device__ __forceinline__ void repfunc_block_mlp(const NlNetArgs& n, const doub
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
           double ta, tb;
-          NLC_HIDDEN_TANH_PAIR(acc[i][s2][r], acc[i][s2][r + 1], &ta, &tb);
+          m::tanh_pair_d(acc[i][s2][r], acc[i][s2][r + 1], &ta, &tb);
           H2[s2 * KS * 64 + (4 * (TW * wave + i) + r) * 64 + lane] = ta;
           H2[s2 * KS * 64 + (4 * (TW * wave + i) + r + 1) * 64 + lane] = tb;
         }

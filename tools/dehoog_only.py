@@ -1,5 +1,4 @@
-"""Times the stand-alone de Hoog ILT kernel: N points, d=5, S in {33, 17} (NLC_ILT_DBG=1 selects the alternative
-occupancy build of the kernel)."""
+"""Times the stand-alone de Hoog ILT kernel: N points, d=5, S in {33, 17}."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,4 +22,4 @@ for S in (33, 17):
     p = ctx.profile_read()["ilt_dehoog_kernel"]
     ms = p["total_ms"] / p["launches"]
     by = N * (2 * d * S + d) * 8
-    print(f"S={S} avg ms {ms:.4f}  {by / ms / 1e6:.0f} GB/s  dbg={os.environ.get('NLC_ILT_DBG', '0')}")
+    print(f"S={S} avg ms {ms:.4f}  {by / ms / 1e6:.0f} GB/s")

@@ -4,7 +4,7 @@ import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import neurallaplacecontrol_amd as nlc
-if len(sys.argv) > 4:  # an alternative library build (e.g. -DNLC_ILT_EXPERIMENTS=1), before the first ctx exists
+if len(sys.argv) > 4:  # another build of the library, before the first ctx exists
     from neurallaplacecontrol_amd import _lib
     _lib.use_library(sys.argv[4])
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 655360
@@ -27,5 +27,5 @@ prof = ctx.profile_read()
 p = prof["ilt_fourier_kernel"] if algo == "fourier" else (prof.get("ilt_linear_kernel") or prof["ilt_linear_stream_kernel"])
 ms = p["total_ms"] / p["launches"]
 nbytes = N * (2 * d * S + d) * 8
-print(algo, "avg ms", ms, "dbg", os.environ.get("NLC_ILT_DBG", "0"))
+print(algo, "avg ms", ms)
 print("points", N, "algorithmic bytes per launch", nbytes, "=", round(nbytes / ms / 1e6), "GB/s")
