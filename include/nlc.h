@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 12
+#define NLC_ABI_VERSION 13
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -526,6 +526,51 @@ int nlc_env_step(nlc_ctx* ctx, int env, int friction, double dt, int delay, int6
                  double* reward_dev);
 /* get_obs (base_env.py:83-89): obs_dev (E, d) = torch_transform_states(state_dev (E, n)) */
 int nlc_env_obs(nlc_ctx* ctx, int env, int64_t E, const double* state_dev, double* obs_dev);
+
+/* ---- expert-data collection (mppi_dataset_collector.py:33-321): one control step of the collector's loop() / step_env()
+ * (:192-222, 241-268) for E envs side by side, recorded into the dataset (s0, a0, sn, ts) the trainers consume.  In the
+ * order of the reference: s0 = the observation the planner was given (:245-246); the expert's command plus uniform action
+ * noise, clipped (:250-254), or a uniform random action (model_name "random", :255-256); get_action /
+ * get_action_with_encode_obs_time (:20-30); the step's interval tsn by ts_grid (base_env.py:103-120); one Euler step of
+ * size tsn (base_env.py:136-173, solver "euler"); reward = diff_reward(new state, applied action) (base_env.py:164), added
+ * to the env's episode return (:269); the time channel ages by tsn (:206-208); Gaussian observation noise on the reduced
+ * state, which persists (env.set_state_, :209-210); sn, a0 = the whole buffer, ts = tsn (:266-268).
+ * Random draws are Philox4x32-10 keyed by `seed` with counter (global episode lo, hi, it, stream): they depend on the
+ * episode and the step only, never on E or on how the episodes are batched (docs/collector.md). */
+#define NLC_TS_GRID_FIXED 0   /* tsn = dt */
+#define NLC_TS_GRID_UNIFORM 1 /* tsn = rand * 2 dt  ("uniform" / "random") */
+#define NLC_TS_GRID_EXP 2     /* tsn ~ Exponential(rate 1/dt) */
+#define NLC_POLICY_PLANNER 0  /* action_dev holds the planner's commands */
+#define NLC_POLICY_RANDOM 1   /* uniform in [action_low, action_high]; action_dev is not read */
+typedef struct nlc_collect_desc {
+  int32_t env;       /* NLC_ENV_CARTPOLE / _PENDULUM / _ACROBOT */
+  int32_t friction;
+  double dt;
+  int32_t delay;     /* the applied action is buffer row B - 1 - delay */
+  int32_t B;         /* action buffer rows */
+  int64_t E;         /* envs of this launch */
+  int32_t nu;        /* action dims (must be the env's) */
+  int32_t time_channel; /* 1: encode_obs_time -- the buffer has nu + 1 columns, the last is the observation time */
+  int32_t ts_grid;   /* NLC_TS_GRID_* */
+  int32_t policy;    /* NLC_POLICY_* */
+  double action_noise; /* collect_expert_random_action_noise; < 0 = None: no noise and no clip */
+  double obs_noise;    /* observation_noise (0 = off) */
+  double action_low, action_high; /* env.action_space.low[0] / high[0] */
+  int32_t steps_per_episode; /* iter_ (:373): rows per episode */
+  uint64_t seed;
+} nlc_collect_desc;
+/* it: control step in [0, steps_per_episode); episode_base: global index of env 0's episode.  Env e writes dataset row
+ * (episode_base + e) * steps_per_episode + it (episode-major, :426-439); the four dataset pointers are the bases of
+ * arrays that hold at least (episode_base + E) * steps_per_episode rows.
+ *   state_dev (E, n), abuf_dev (E, B, nu + time_channel), ret_dev (E): updated in place (ret_dev += reward)
+ *   action_dev (E, nu) or NULL with NLC_POLICY_RANDOM
+ *   s0_dev, sn_dev (rows, d); a0_dev (rows, B, nu + time_channel); ts_dev (rows)
+ * NLC_ERR_BAD_SHAPE: E < 1 (E == 0 is refused too), B < 1, delay outside [0, B-1], nu > NLC_MAX_NU or not the env's, it or
+ * episode_base out of range; NLC_ERR_BAD_ARG: unknown ts_grid / policy, NULL pointer, NULL action_dev with
+ * NLC_POLICY_PLANNER.  Nothing is launched after a refusal. */
+int nlc_collect_step(nlc_ctx* ctx, const nlc_collect_desc* desc, int it, int64_t episode_base, double* state_dev,
+                     double* abuf_dev, const double* action_dev_or_null, double* ret_dev, double* s0_dev, double* a0_dev,
+                     double* sn_dev, double* ts_dev);
 
 /* ---- in-library kernel timing (hipEvent pairs on the launch stream) ------------------------- */
 int nlc_profile_enable(nlc_ctx* ctx, int on);

@@ -7,6 +7,7 @@ Drop-in mirrors of the reference's Python interfaces for this path (SURVEY.md §
     from neurallaplacecontrol_amd import laplace_reconstruct    # torchlaplace (external)
     from neurallaplacecontrol_amd import NLTrainer              # train_utils.py:388-408 (fused training step)
     from neurallaplacecontrol_amd import DeltaTRNN, NODE        # train_utils.py:589, :664 (baseline models)
+    from neurallaplacecontrol_amd import collect_expert_dataset # mppi_dataset_collector.py:324-443 (expert dataset)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of ``libnlc_hip.so``
 (``include/nlc.h``); importing the package does not touch the GPU.  There is no CPU fallback.
@@ -14,6 +15,7 @@ All arithmetic runs in hand-written HIP kernels behind the C ABI of ``libnlc_hip
 
 from ._lib import set_default_options  # noqa: F401
 from .envs import EnvCost, NLDynamics, OracleDynamics, initial_state, noise_sigma  # noqa: F401
+from .collector import ExpertCollector, collect_expert_dataset, replay_buffer_file_name  # noqa: F401
 from .env_loop import BatchedEnv  # noqa: F401
 from .laplace import ilt_reconstruct, laplace_reconstruct, rep_func_inputs  # noqa: F401
 from .nl_model import LaplaceRepresentationFunc, NeuralLaplaceModel, ReverseGRUEncoder  # noqa: F401
@@ -27,6 +29,9 @@ __all__ = [
     "MPPIDelay",
     "BatchedMPPIDelay",
     "BatchedEnv",
+    "ExpertCollector",
+    "collect_expert_dataset",
+    "replay_buffer_file_name",
     "NeuralLaplaceModel",
     "NLTrainer",
     "NLTrainerGroup",

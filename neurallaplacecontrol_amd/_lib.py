@@ -89,6 +89,7 @@ SYMBOLS = [
     "nlc_comm_self_test",
     "nlc_env_step",
     "nlc_env_obs",
+    "nlc_collect_step",
     "nlc_profile_enable",
     "nlc_profile_reset",
     "nlc_profile_count",
@@ -193,6 +194,31 @@ class MppiBuffers(C.Structure):
     ]
 
 
+TS_GRIDS = {"fixed": 0, "uniform": 1, "random": 1, "exp": 2}
+POLICIES = {"planner": 0, "random": 1}
+
+
+class CollectDesc(C.Structure):
+    _fields_ = [
+        ("env", C.c_int32),
+        ("friction", C.c_int32),
+        ("dt", C.c_double),
+        ("delay", C.c_int32),
+        ("B", C.c_int32),
+        ("E", C.c_int64),
+        ("nu", C.c_int32),
+        ("time_channel", C.c_int32),
+        ("ts_grid", C.c_int32),
+        ("policy", C.c_int32),
+        ("action_noise", C.c_double),
+        ("obs_noise", C.c_double),
+        ("action_low", C.c_double),
+        ("action_high", C.c_double),
+        ("steps_per_episode", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -259,6 +285,7 @@ def load_library():
         lib.nlc_node_forward.argtypes = [vp, vp, vp, dbl, i64, vp]
         lib.nlc_env_step.argtypes = [vp, i32, i32, dbl, i32, i64, i32, i32, vp, vp, vp, vp, vp]
         lib.nlc_env_obs.argtypes = [vp, i32, i64, vp, vp]
+        lib.nlc_collect_step.argtypes = [vp, P(CollectDesc), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.nlc_rep_func.argtypes = [vp, vp, i64, vp, vp]
         lib.nlc_set_option.argtypes = [vp, C.c_char_p, dbl]
         lib.nlc_get_stat.argtypes = [vp, C.c_char_p, P(dbl)]

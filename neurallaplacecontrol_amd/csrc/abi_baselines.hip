@@ -1,4 +1,5 @@
-// Host side of libnlc_hip.so, baselines unit: the env side of the evaluation loop (nlc_env_step / nlc_env_obs) and the
+// Host side of libnlc_hip.so, baselines unit: the env side of the evaluation loop (nlc_env_step / nlc_env_obs), the
+// expert-data collector's control step (nlc_collect_step) and the
 // Delta-t RNN / NODE baseline dynamics models (upload + forward).
 #include "nlc_host.h"
 
@@ -35,6 +36,62 @@ extern "C" int nlc_env_obs(nlc_ctx* c, int env, int64_t E, const double* state, 
   EnvStepArgs a{env, 0, 1, 1, 0, E, 0.0, const_cast<double*>(state), nullptr, nullptr, obs, nullptr};
   ProfScope ps(c, "env_step_kernel");
   NLC_HIP(c, launch_env_step(a, c->stream));
+  return NLC_OK;
+  NLC_GUARD_END(c)
+}
+
+// =================================================================================== expert-data collection
+extern "C" int nlc_collect_step(nlc_ctx* c, const nlc_collect_desc* d, int it, int64_t episode_base, double* state,
+                                double* abuf, const double* action, double* ret, double* s0, double* a0, double* sn,
+                                double* ts) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  NLC_GUARD_BEGIN
+  static const int env_nu[3] = {1, 1, 2};
+  if (!d) return fail(c, NLC_ERR_BAD_ARG, "NULL collect desc");
+  if (d->env < 0 || d->env > 2) return fail(c, NLC_ERR_UNSUPPORTED, "unknown env id");
+  if (d->nu < 1 || d->nu > NLC_MAX_NU) return fail(c, NLC_ERR_BAD_SHAPE, "nu must be in 1..NLC_MAX_NU");
+  if (d->nu != env_nu[d->env]) return fail(c, NLC_ERR_BAD_SHAPE, "nu does not match the env's action space");
+  if (d->E < 1) return fail(c, NLC_ERR_BAD_SHAPE, "collect: E must be >= 1");
+  if (d->B < 1 || d->delay < 0 || d->delay > d->B - 1) return fail(c, NLC_ERR_BAD_SHAPE, "collect: delay must be in [0, B - 1], B >= 1");
+  if (d->steps_per_episode < 1 || it < 0 || it >= d->steps_per_episode || episode_base < 0)
+    return fail(c, NLC_ERR_BAD_SHAPE, "collect: it must be in [0, steps_per_episode), episode_base >= 0");
+  if (d->ts_grid != NLC_TS_GRID_FIXED && d->ts_grid != NLC_TS_GRID_UNIFORM && d->ts_grid != NLC_TS_GRID_EXP)
+    return fail(c, NLC_ERR_BAD_ARG, "collect: unknown ts_grid");
+  if (d->policy != NLC_POLICY_PLANNER && d->policy != NLC_POLICY_RANDOM) return fail(c, NLC_ERR_BAD_ARG, "collect: unknown policy");
+  if (d->policy == NLC_POLICY_PLANNER && !action) return fail(c, NLC_ERR_BAD_ARG, "collect: the planner policy needs actions");
+  if (!state || !abuf || !ret || !s0 || !a0 || !sn || !ts) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
+  if (!(d->dt > 0.0) || !(d->obs_noise >= 0.0) || !(d->action_low <= d->action_high))
+    return fail(c, NLC_ERR_BAD_ARG, "collect: dt must be > 0, obs_noise >= 0, action_low <= action_high");
+  NLC_HIP(c, hipSetDevice(c->device));
+  CollectStepArgs a{};
+  a.env = d->env;
+  a.friction = d->friction;
+  a.B = d->B;
+  a.nu = d->nu;
+  a.delay = d->delay;
+  a.time_channel = d->time_channel ? 1 : 0;
+  a.ts_grid = d->ts_grid;
+  a.policy = d->policy;
+  a.steps_per_episode = d->steps_per_episode;
+  a.it = it;
+  a.E = d->E;
+  a.episode_base = episode_base;
+  a.dt = d->dt;
+  a.action_noise = d->action_noise;
+  a.obs_noise = d->obs_noise;
+  a.action_low = d->action_low;
+  a.action_high = d->action_high;
+  a.seed = d->seed;
+  a.state = state;
+  a.abuf = abuf;
+  a.action = d->policy == NLC_POLICY_PLANNER ? action : nullptr;
+  a.ret = ret;
+  a.s0 = s0;
+  a.a0 = a0;
+  a.sn = sn;
+  a.ts = ts;
+  ProfScope ps(c, "collect_step_kernel");
+  NLC_HIP(c, launch_collect_step(a, c->stream));
   return NLC_OK;
   NLC_GUARD_END(c)
 }

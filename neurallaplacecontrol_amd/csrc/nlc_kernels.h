@@ -425,6 +425,25 @@ struct EnvStepArgs {
 };
 hipError_t launch_env_step(const EnvStepArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ expert-data collection (kernels_collect.hip)
+// One control step of the collector's loop() / step_env() (mppi_dataset_collector.py:192-222, 241-268) for E envs, recorded
+// as dataset rows: see nlc_collect_step (include/nlc.h).  Device bodies shared with env_step_kernel: nlc_env_dev.h.
+struct CollectStepArgs {
+  int env, friction, B, nu, delay, time_channel, ts_grid, policy, steps_per_episode, it;
+  int64_t E, episode_base;
+  double dt, action_noise, obs_noise, action_low, action_high;
+  uint64_t seed;
+  double* state;         // (E, n) reduced state, in/out
+  double* abuf;          // (E, B, nu + time_channel) in/out
+  const double* action;  // (E, nu) the planner's commands; NULL with the random policy
+  double* ret;           // (E) episode return, += reward
+  double* s0;            // (rows, d)
+  double* a0;            // (rows, B, nu + time_channel)
+  double* sn;            // (rows, d)
+  double* ts;            // (rows)
+};
+hipError_t launch_collect_step(const CollectStepArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ MPPI sampling / weighting
 constexpr int kMaxInlineAbuf = 32;  // action_buffer doubles carried in the kernel arguments (B*nu <= 32)
 struct PerturbArgs {
