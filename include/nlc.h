@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 13
+#define NLC_ABI_VERSION 14
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -63,6 +63,13 @@ extern "C" {
  * (ctcartpole.py:60; reward branch :297-300; oracle dynamics branch oracle.py:38-44, 80-86) -- BASELINE's literal
  * "state_dim=4".  Planner only (running cost, oracle dynamics, NL dynamics); nlc_env_step keeps the three harness envs. */
 #define NLC_ENV_CARTPOLE_NOTRIG 3
+/* the non-default branches of the harness running_cost (mppi_with_model.py:146-162 -> ctcartpole.py:311-329), a bit set;
+ * cartpole envs only.  The closure's `if state_constraint / elif change_goal`: with NLC_COST_STATE_CONSTRAINT set the two
+ * goal bits are not looked at. */
+#define NLC_COST_STATE_CONSTRAINT 1 /* position error e0^2 + exp(10 e0 + 7): a soft wall on the cart (ctcartpole.py:327-329) */
+#define NLC_COST_CHANGE_GOAL 2      /* goal x = -2 instead of 0 (ctcartpole.py:313-317) */
+#define NLC_COST_GOAL_FLIPPED 4     /* with NLC_COST_CHANGE_GOAL: goal x = +2 (the global change_goal_flipped, :153-158) */
+#define NLC_COST_VARIANT_MASK 7
 
 /* rollout dynamics */
 #define NLC_DYN_NL 0     /* state + NeuralLaplaceModel(state, window, ts_pred)  (mppi_with_model.py:103-122) */
@@ -436,6 +443,15 @@ typedef struct {
                                * (:343-344) in buf->cost_total and stops before the weights; the caller adds its cost
                                * (buf->states must be given) and calls nlc_mppi_weights.  env is then used by oracle
                                * dynamics only and may be -1 with NL dynamics. */
+  int32_t cost_variant;       /* NLC_COST_* bits of the in-kernel running cost: the state_constraint / change_goal branches of
+                               * the harness closure (mppi_with_model.py:42-43, 146-162; mppi_dataset_collector.py:45-46,
+                               * 137-156) on NLC_ENV_CARTPOLE / NLC_ENV_CARTPOLE_NOTRIG.  0 = the default branch (:163).
+                               * Any bit on another env: NLC_ERR_UNSUPPORTED; bits outside NLC_COST_VARIANT_MASK:
+                               * NLC_ERR_BAD_SHAPE; both before any launch.  Ignored with cost_external.  The
+                               * latency-split and one-launch bodies evaluate a variant in compile-time instances of
+                               * their own; behind every other body one launch evaluates it on the stored rollout
+                               * (buf->states must then be given), before the importance weights.  A flipped bit
+                               * without NLC_COST_CHANGE_GOAL selects nothing. */
   double ts_pred;             /* raw dt handed to the dynamics (mppi_with_model.py:74) */
 } nlc_mppi_desc;
 
@@ -464,6 +480,12 @@ int nlc_mppi_configure(nlc_ctx* ctx, const nlc_mppi_desc* desc);
 int64_t nlc_mppi_workspace_bytes(nlc_ctx* ctx);
 int nlc_mppi_set_U(nlc_ctx* ctx, const double* U_host); /* (E,T,nu) control sequence(s), :161-164 */
 int nlc_mppi_get_U(nlc_ctx* ctx, double* U_host);
+/* The reference's running_cost reads the global change_goal_flipped on EVERY call (mppi_with_model.py:153-158, set by the
+ * evaluation loop :231-232, 251-253): sets or clears NLC_COST_GOAL_FLIPPED of the configured planner -- one host word, no
+ * launch, no reconfiguration; U, the command counter and the noise stream are untouched.  Commands from the next
+ * nlc_mppi_rollout on see it.  NLC_ERR_STATE without a configured planner or without
+ * NLC_COST_CHANGE_GOAL in its cost_variant; NLC_ERR_UNSUPPORTED on a non-cartpole env. */
+int nlc_mppi_set_goal_flipped(nlc_ctx* ctx, int flipped);
 /* Phase 1 of command(): shift U (:199-200), sample/perturb/bound (:319-335), hoisted GRU encode,
  * T-step rollout + running cost (:232-313), perturbation cost (:343-344), and this shard's
  * softmax partials (beta_r, eta_r, S_r) into buf->partials.

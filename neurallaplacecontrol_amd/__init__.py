@@ -16,7 +16,7 @@ All arithmetic runs in hand-written HIP kernels behind the C ABI of ``libnlc_hip
 from ._lib import set_default_options  # noqa: F401
 from .envs import EnvCost, NLDynamics, OracleDynamics, initial_state, noise_sigma  # noqa: F401
 from .collector import ExpertCollector, collect_expert_dataset, replay_buffer_file_name  # noqa: F401
-from .env_loop import BatchedEnv  # noqa: F401
+from .env_loop import BatchedEnv, evaluate_episodes  # noqa: F401
 from .laplace import ilt_reconstruct, laplace_reconstruct, rep_func_inputs  # noqa: F401
 from .nl_model import LaplaceRepresentationFunc, NeuralLaplaceModel, ReverseGRUEncoder  # noqa: F401
 from .node_model import NODE, xOdeFuncInXAndU  # noqa: F401
@@ -29,6 +29,7 @@ __all__ = [
     "MPPIDelay",
     "BatchedMPPIDelay",
     "BatchedEnv",
+    "evaluate_episodes",
     "ExpertCollector",
     "collect_expert_dataset",
     "replay_buffer_file_name",

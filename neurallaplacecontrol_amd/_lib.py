@@ -19,6 +19,8 @@ NLC_MAX_D = 8
 ILT_ALGOS = {"fourier": 0, "dehoog": 1, "fixed_tablot": 2, "stehfest": 3}
 # "oderl-cartpole-notrig": CTCartpole(obs_trans=False), the 4-dim state [x, xdot, theta, thetadot] (ctcartpole.py:60, 297-300)
 ENV_IDS = {"oderl-cartpole": 0, "oderl-pendulum": 1, "oderl-acrobot": 2, "oderl-cartpole-notrig": 3}
+# NLC_COST_* bits of nlc_mppi_desc.cost_variant (mppi_with_model.py:146-162; cartpole envs only)
+COST_STATE_CONSTRAINT, COST_CHANGE_GOAL, COST_GOAL_FLIPPED = 1, 2, 4
 DYN_NL, DYN_ORACLE, DYN_EXTERNAL, DYN_DTRNN, DYN_NODE = 0, 1, 2, 3, 4
 
 ERRORS = {-1: "BAD_ARG", -2: "BAD_SHAPE", -3: "HIP_ERROR", -4: "UNSUPPORTED", -5: "STATE", -6: "COMM"}
@@ -80,6 +82,7 @@ SYMBOLS = [
     "nlc_mppi_workspace_bytes",
     "nlc_mppi_set_U",
     "nlc_mppi_get_U",
+    "nlc_mppi_set_goal_flipped",
     "nlc_mppi_rollout",
     "nlc_mppi_weights",
     "nlc_mppi_finish",
@@ -175,6 +178,7 @@ class MppiDesc(C.Structure):
         ("friction", C.c_int32),
         ("E", C.c_int32),
         ("cost_external", C.c_int32),
+        ("cost_variant", C.c_int32),
         ("ts_pred", C.c_double),
     ]
 
@@ -294,6 +298,7 @@ def load_library():
         lib.nlc_mppi_workspace_bytes.restype = i64
         lib.nlc_mppi_set_U.argtypes = [vp, vp]
         lib.nlc_mppi_get_U.argtypes = [vp, vp]
+        lib.nlc_mppi_set_goal_flipped.argtypes = [vp, i32]
         lib.nlc_mppi_rollout.argtypes = [vp, vp, i32, vp, P(MppiBuffers), i32, C.c_uint64, C.c_uint64]
         lib.nlc_mppi_weights.argtypes = [vp, P(MppiBuffers)]
         lib.nlc_mppi_finish.argtypes = [vp, vp, i32, i32, P(MppiBuffers), vp]

@@ -265,8 +265,11 @@ def candidate_dynamics(fn):
         return None
 
 
-def candidate_cost(fn):
-    """An ``EnvCost`` that `fn` appears to compute (the harness closure's default branch), or None."""
+def candidate_cost(fn, variants=False):
+    """An ``EnvCost`` that `fn` appears to compute, or None.  Without ``variants`` only the harness closure's default branch
+    is proposed (the plain env cost); with it -- as the planner asks -- a closure whose free variables ``state_constraint`` /
+    ``change_goal`` are set gets the ``EnvCost`` with those flags (``mppi_with_model.py:146-162``; cartpole only), and
+    ``change_goal_flipped`` starts from the closure's module global.  ``probe_equivalence`` is the gate either way."""
     if isinstance(fn, EnvCost):
         return fn
     if not has_harness_structure(fn, "cost"):
@@ -275,17 +278,39 @@ def candidate_cost(fn):
     if not free:
         return None
     # non-default branches (state_constraint / change_goal) are NOT the plain env cost
-    for flag in ("state_constraint", "change_goal"):
-        if free.get(flag):
-            return None
+    flags = {flag: bool(free.get(flag)) for flag in ("state_constraint", "change_goal")}
+    if any(flags.values()) and not variants:
+        return None
+    if flags["state_constraint"]:
+        flags["change_goal"] = False  # the closure's if / elif
     envs = [v for v in free.values() if hasattr(v, "diff_obs_reward_") and hasattr(v, "diff_ac_reward_")]
     if len(envs) != 1:
         return None
     cls = type(envs[0]).__name__.lower()
     for hint, name in _ENV_CLASS_HINTS:
         if hint in cls:
-            return EnvCost(name)
+            try:
+                cost = EnvCost(name, **flags)  # ValueError: a variant on an env class that has none
+            except ValueError:
+                return None
+            follow_flip(flip_source(fn, cost), cost)
+            return cost
     return None
+
+
+def flip_source(fn, cost):
+    """The literal closure `fn` if the recognised `cost` must follow its module global ``change_goal_flipped`` -- a change_goal
+    cost whose closure reads that global (``mppi_with_model.py:153-158``) -- else None."""
+    if (isinstance(cost, EnvCost) and cost.change_goal and not cost.state_constraint and inspect.isfunction(fn)
+            and "change_goal_flipped" in fn.__code__.co_names):
+        return fn
+    return None
+
+
+def follow_flip(fn, cost):
+    """Copy the closure's module global ``change_goal_flipped`` (absent: False) into `cost`; no-op without a source."""
+    if fn is not None:
+        cost.change_goal_flipped = bool(fn.__globals__.get("change_goal_flipped", False))
 
 
 def probe_equivalence(make_planner, literal, candidate, state, action_buffer, K, nu, horizon=4, rtol=1e-9, atol=1e-10):

@@ -24,7 +24,7 @@ import os
 import torch
 
 from . import _lib
-from .env_loop import BatchedEnv
+from .env_loop import BatchedEnv, _same_cost_branch
 from .envs import ENV_DIMS, EnvCost, NLDynamics, OracleDynamics, noise_sigma
 
 __all__ = ["ExpertCollector", "collect_expert_dataset", "replay_buffer_file_name"]
@@ -88,7 +88,13 @@ class ExpertCollector:
 
     def __init__(self, env_name, action_delay, num_envs, *, dt=0.05, ts_grid="exp", random_action_noise=1.0,
                  observation_noise=0.0, friction=False, encode_obs_time=False, action_buffer_size=4, steps_per_episode=200,
-                 policy="planner", planner=None, seed=0, device=None, episode_base=0, storage=None):
+                 policy="planner", planner=None, seed=0, device=None, episode_base=0, storage=None,
+                 state_constraint=False, change_goal=False):
+        # the reference collector's two experiment flags (mppi_dataset_collector.py:45-46, 137-156): they select the branch of
+        # the PLANNER's running cost; the recorded reward stays the env's own (integrate_system, base_env.py:164)
+        self.cost = EnvCost(env_name, state_constraint=state_constraint, change_goal=change_goal)
+        if planner is not None and not _same_cost_branch(getattr(planner, "running_cost", None), self.cost):
+            raise ValueError("the planner's running cost is not the EnvCost of state_constraint / change_goal given here")
         self.episode_base = int(episode_base)
         # env e starts global episode episode_base + e from that episode's own reset stream (reset() re-keys per batch)
         self.env = BatchedEnv(env_name, num_envs, dt=dt, action_delay=action_delay, action_buffer_size=action_buffer_size,
@@ -228,8 +234,9 @@ def _model_name(policy, dynamics):
 
 
 def _make_planner(env_name, action_delay, num_envs, dynamics, roll_outs, time_steps, lambda_, sigma, dt, friction,
-                  encode_obs_time, seed, device):
-    """The collector's planner (``mppi_dataset_collector.py:69-74, 166-180``) over ``num_envs`` episodes."""
+                  encode_obs_time, seed, device, cost=None):
+    """The collector's planner (``mppi_dataset_collector.py:69-74, 166-180``) over ``num_envs`` episodes; ``cost``: its
+    running cost (default: the env's plain ``EnvCost``)."""
     from .planners.mppi_batch import BatchedMPPIDelay
     from .planners.mppi_delay import MPPIDelay
 
@@ -248,9 +255,10 @@ def _make_planner(env_name, action_delay, num_envs, dynamics, roll_outs, time_st
               noise_rng="philox", seed=seed, store_rollouts=False)
     sig = noise_sigma(nu, sigma)
     dev = str(device)
+    cost = cost if cost is not None else EnvCost(env_name)
     if num_envs == 1:
-        return MPPIDelay(dyn, EnvCost(env_name), nx, sig, roll_outs, time_steps, dev, **kw)
-    return BatchedMPPIDelay(dyn, EnvCost(env_name), nx, sig, num_envs, roll_outs, time_steps, dev, **kw)
+        return MPPIDelay(dyn, cost, nx, sig, roll_outs, time_steps, dev, **kw)
+    return BatchedMPPIDelay(dyn, cost, nx, sig, num_envs, roll_outs, time_steps, dev, **kw)
 
 
 def collect_expert_dataset(env_name, action_delay, collect_samples=1e6, roll_outs=1000, time_steps=40, lambda_=1.0,
@@ -262,7 +270,9 @@ def collect_expert_dataset(env_name, action_delay, collect_samples=1e6, roll_out
     attribute holds the per-episode total rewards).  With ``save_path`` (a directory)
     the tuple is also written there as CPU tensors under the reference's file name, which the reference's
     ``load_expert_irregular_data_delay_time_multi`` reads; the name carries ``model_name``, by default that of the
-    dynamics' kind ("oracle", "random", "nl", "delta_t_rnn", "node").  ``collector_kwargs`` go to :class:`ExpertCollector`."""
+    dynamics' kind ("oracle", "random", "nl", "delta_t_rnn", "node").  ``collector_kwargs`` go to :class:`ExpertCollector`,
+    ``state_constraint`` / ``change_goal`` (the reference's names, ``:45-46``) among them: the expert then plans with that
+    branch of the cartpole running cost.  The reference collector's loop never flips the goal (``:242-244`` assign a local)."""
     kw = dict(collector_kwargs)
     spe = int(kw.get("steps_per_episode", 200))
     seed = int(kw.pop("seed", 0))
@@ -286,7 +296,7 @@ def collect_expert_dataset(env_name, action_delay, collect_samples=1e6, roll_out
                               storage=None if main is None else main.storage, **kw)
         if policy == "planner":
             col.planner = _make_planner(env_name, action_delay, size, dynamics, roll_outs, time_steps, lambda_, sigma, dt,
-                                        friction, enc, seed + base, col.device)
+                                        friction, enc, seed + base, col.device, cost=col.cost)
         if main is None:
             main = col
             main.storage.reserve(total)

@@ -30,6 +30,10 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
   static const int env_d[4] = {5, 3, 6, 4}, env_nu[4] = {1, 1, 2, 1};
   if (!env_free && d->dynamics != NLC_DYN_EXTERNAL && (d->d != env_d[d->env] || d->nu != env_nu[d->env]))
     return fail(c, NLC_ERR_BAD_SHAPE, "nx / nu do not match the env's observation");
+  // the state_constraint / change_goal branches exist in the cartpole env class only (ctcartpole.py:311-329)
+  if (d->cost_variant & ~NLC_COST_VARIANT_MASK) return fail(c, NLC_ERR_BAD_SHAPE, "unknown cost_variant bits");
+  if (d->cost_variant != 0 && !d->cost_external && d->env != NLC_ENV_CARTPOLE && d->env != NLC_ENV_CARTPOLE_NOTRIG)
+    return fail(c, NLC_ERR_UNSUPPORTED, "cost_variant: only the cartpole envs have a state_constraint / change_goal cost");
   if (d->cost_external && d->dynamics == NLC_DYN_EXTERNAL)
     return fail(c, NLC_ERR_BAD_ARG, "cost_external needs fused dynamics (NLC_DYN_NL / NLC_DYN_ORACLE / NLC_DYN_DTRNN)");
   if (d->dynamics == NLC_DYN_EXTERNAL) {
@@ -205,6 +209,20 @@ WeightArgs make_weight_args(nlc_ctx* c, const nlc_mppi_buffers* buf) {
   return wa;
 }
 
+// what follows a rollout that left the running cost out: nothing for the caller's own cost (cost_external: it calls
+// nlc_mppi_weights), else the cost variant's kernel on the stored states and the importance weights
+int finish_rollout_costs(nlc_ctx* c, const nlc_mppi_buffers* buf, bool in_body) {
+  const nlc_mppi_desc& d = c->pd;
+  if (d.cost_external) return NLC_OK;
+  if (cost_variant_of(d) && !in_body) {
+    if (!buf->states) return fail(c, NLC_ERR_BAD_ARG, "this rollout body evaluates a cost_variant on buf->states");
+    VariantCostArgs v{d.K * d.E, d.T, d.nu, d.d, d.env, cost_variant_of(d), d.u_scale, buf->states, buf->perturbed, buf->cost_total};
+    ProfScope ps(c, "variant_cost_kernel");
+    NLC_HIP(c, launch_variant_cost(v, c->stream));
+  }
+  return run_weights(c, buf);
+}
+
 int run_weights(nlc_ctx* c, const nlc_mppi_buffers* buf) {
   WeightArgs wa = make_weight_args(c, buf);
   // behind a fused launch that left the fold to us: its give-up word marks the partial rows here -- the launch of
@@ -238,7 +256,7 @@ SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call) {
   a.Kep = d.K;
   a.T = d.T;
   a.nu = d.nu;
-  a.env = d.cost_external ? -1 : d.env;
+  a.env = (d.cost_external || cost_variant_of(d)) ? -1 : d.env;  // (a variant's CV bodies: cost_in_body)
   a.state_per_sample = call.state_per_sample;
   a.state0 = call.state_dev;
   a.perturbed = call.buf->perturbed;
@@ -325,6 +343,18 @@ extern "C" int nlc_mppi_set_U(nlc_ctx* c, const double* U) {
   NLC_HIP(c, hipMemcpyAsync(c->U[c->ucur], U, (size_t)c->pd.E * c->pd.T * c->pd.nu * sizeof(double), hipMemcpyHostToDevice,
                             c->stream));
   NLC_HIP(c, hipStreamSynchronize(c->stream));
+  return NLC_OK;
+}
+
+extern "C" int nlc_mppi_set_goal_flipped(nlc_ctx* c, int flipped) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  if (!c->has_mppi) return fail(c, NLC_ERR_STATE, "planner not configured");
+  if (c->pd.env != NLC_ENV_CARTPOLE && c->pd.env != NLC_ENV_CARTPOLE_NOTRIG)
+    return fail(c, NLC_ERR_UNSUPPORTED, "change_goal_flipped: only the cartpole envs have a change_goal cost");
+  if (!(c->pd.cost_variant & NLC_COST_CHANGE_GOAL))
+    return fail(c, NLC_ERR_STATE, "change_goal_flipped: the planner was not configured with NLC_COST_CHANGE_GOAL");
+  // sample_cost_args reads the descriptor at every command: the next rollout's launches carry the new bit
+  c->pd.cost_variant = flipped ? (c->pd.cost_variant | NLC_COST_GOAL_FLIPPED) : (c->pd.cost_variant & ~NLC_COST_GOAL_FLIPPED);
   return NLC_OK;
 }
 
@@ -504,7 +534,7 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
   }
   if (d.dynamics == NLC_DYN_NL) return rollout_nl(c, call);
   if (int rc = rollout_baseline(c, call)) return rc;
-  return d.cost_external ? NLC_OK : run_weights(c, buf);
+  return finish_rollout_costs(c, buf);
   NLC_GUARD_END(c)
 }
 

@@ -330,7 +330,7 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc, G
     if (int rc = launch_staged_steps(c, call, sc, r, pa, lin_tab, plan::staged_partition(KE, P), ck)) return rc;
   }
   if (timing) NLC_HIP(c, hipEventRecord(c->dh.ev[1], c->stream));
-  return d.cost_external ? NLC_OK : run_weights(c, call.buf);
+  return finish_rollout_costs(c, call.buf);  // (neither form of the step chain has an instance for a cost variant)
 }
 
 // one persistent launch for a small shard (kernels_fused.hip): GRU encode and split rollout as roles of one grid, with the
@@ -503,6 +503,9 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
   const bool fold_inside = (c->opt.fused_inline & 1) && d.E == 1 && !d.cost_external;
   if (variant == 0 && fused_ok && c->fused.blocks_per_cu >= 2 && KE <= c->opt.fused_max_samples && (!sharded || fold_inside)) variant = 3;
   if (variant == 3 && (replay || c->fused.lost)) variant = 2;
+  // the one-launch body and the latency-split body have an instance for a cost variant; the wave-per-tile body has not
+  const bool in_body = variant == 3 || variant == 2 || (variant == 0 && KE <= 8192);
+  if (in_body) cost_in_body(r, d);
   if (variant == 3) {
     bool weights_done = false;
     if (int rc2 = rollout_nl_fused(c, call, g, r, &weights_done)) return rc2;
@@ -512,5 +515,5 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
     // (launch_nl_rollout: 2 = latency-split, 1 = wave-per-tile, 0 = its own pick: split up to 8192 samples)
     c->last_body = (variant == 2 || (variant == 0 && KE <= 8192)) ? 2 : 1;
   }
-  return d.cost_external ? NLC_OK : run_weights(c, buf);
+  return finish_rollout_costs(c, buf, in_body);
 }

@@ -358,6 +358,25 @@ hipError_t launch_oracle_rollout(const OracleRolloutArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ cost variants on the stored rollout (nlc_kernels.h)
+__global__ __launch_bounds__(256) void variant_cost_kernel(const VariantCostArgs a) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.K) return;
+  double cost = 0.0;
+  for (int t = 0; t < a.T; ++t) {
+    double x[NLC_MAX_D], u[NLC_MAX_NU];
+    for (int i = 0; i < a.d; ++i) x[i] = a.states[(k * a.T + t) * a.d + i];
+    for (int j = 0; j < a.nu; ++j) u[j] = a.u_scale * a.perturbed[(k * a.T + t) * a.nu + j];
+    cost += running_cost_variant(a.env, a.variant, x, u, a.nu);
+  }
+  a.cost_total[k] = cost + a.cost_total[k];
+}
+hipError_t launch_variant_cost(const VariantCostArgs& a, hipStream_t s) {
+  if (a.K <= 0) return hipSuccess;
+  hipLaunchKernelGGL(variant_cost_kernel, dim3((unsigned)((a.K + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ env side of the evaluation loop
 // (device bodies: nlc_env_dev.h, shared with collect_step_kernel)
 __global__ __launch_bounds__(256) void env_step_kernel(const EnvStepArgs a) {

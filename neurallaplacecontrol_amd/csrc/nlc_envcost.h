@@ -4,6 +4,7 @@
 // The functions pin fp contract(off) themselves: the same bits whatever contraction their unit is built with.
 #pragma once
 #include "nlc_device.h"
+#include "nlc_cost.h"
 #include "../../include/nlc.h"
 
 namespace nlc {
@@ -54,6 +55,24 @@ __device__ __forceinline__ double running_cost(int env, const double (&x)[NLC_MA
     const double state_reward = -(ex * ex) - p2y * p2y;
     return -((state_reward + 1e-1 * vel_reward) + (-1e-4 * uu));
   }
+}
+
+// The closure's state_constraint / change_goal branches (mppi_with_model.py:146-162) on the cartpole envs; variant: NLC_COST_*
+// bits, not 0.  The double exp of the wall term costs a rollout body 30 to 40 vector registers, so only compile-time
+// instances call this (rollout_split_tile's CV: the latency-split and one-launch bodies); behind the other bodies
+// variant_cost_kernel (kernels_mppi.hip) evaluates it on the stored states.
+__device__ __forceinline__ double running_cost_variant(int env, int variant, const double* x, const double* u, int nu) {
+#pragma clang fp contract(off)
+  double uu = 0.0;
+  for (int j = 0; j < nu; ++j) uu += u[j] * u[j];
+  // ee as in running_cost, goal (cartpole_goal_x, 1), ctcartpole.py:311-339; 4-dim state: explicit angle (:297-300)
+  const bool trig = env == NLC_ENV_CARTPOLE;
+  const double sl = trig ? x[3] : 1.0 * sin(x[2]), cl = trig ? x[2] : 1.0 * cos(x[2]);
+  const double thd = trig ? x[4] : x[3];
+  const double e0 = x[0] + sl - cost::cartpole_goal_x(variant), e1 = cl - 1.0;
+  const double state_reward = cost::cartpole_state_reward(e0, e1, variant);
+  const double vel_reward = -(x[1] * x[1]) - thd * thd;
+  return -((state_reward + 0.01 * vel_reward) + (-0.01 * uu));
 }
 
 // perturbation cost of one horizon step: sum_j U[t,j] (lambda eps Sigma^-1)[j]   (planners/mppi_delay.py:335, 343).

@@ -284,7 +284,7 @@ static __device__ __attribute__((noinline)) void fused_weight_rank(const WeightA
   if (threadIdx.x == 0 && __hip_atomic_load(gave_up, NLC_RLX_AGENT) != 0u) w.partials[1] = kPartialInvalidEta;  // (thread 0 stored eta)
 }
 
-template <int HT, int NT3>
+template <int HT, int NT3, bool CV>
 __device__ __forceinline__ void fused_rollout(int tile, double* smem, unsigned* cu_state = nullptr) {
   constexpr int KS = HT * 4;
   const FusedArgs& a = *(const FusedArgs*)role_args();
@@ -316,7 +316,7 @@ __device__ __forceinline__ void fused_rollout(int tile, double* smem, unsigned* 
   // the sequential chain is the command's critical path: its waves win the issue arbitration on their SIMDs
   if (NLC_FUSED_TRACE && wv == 0) wave_add_one(a.ctl.sync + kFusedStatRollStart, lane);
   __builtin_amdgcn_s_setprio(3);
-  const double cost = rollout_split_tile<HT, NT3, PaHandoff, false, kCwFused, kSplitPrefetchFused>(a.r, (int64_t)tile, src, smem, smem + KS * 64,
+  const double cost = rollout_split_tile<HT, NT3, PaHandoff, false, kCwFused, kSplitPrefetchFused, CV>(a.r, (int64_t)tile, src, smem, smem + KS * 64,
                                                                                                      smem + 2 * KS * 64);
   __builtin_amdgcn_s_setprio(0);
   if (a.ctl.inline_weights) {
@@ -416,7 +416,8 @@ __device__ __forceinline__ void fused_encode(double* smem, int max_tiles, int yi
 // map wants ~200) but four cooperative encoder tiles per CU hide each other's latencies -- the better trade when most CUs
 // walk a chain (K > 2048 on 256 CUs).  3: 168 VGPRs, 34 spills: chains 5 % faster per horizon step; better up to one
 // chain on half the CUs (K = 1024: 0.527 vs 0.571 ms, K = 2048: 0.674 vs 0.709 ms; profiles/r3_fused_small_shard.md).
-template <int HT, int NT3, int G, int BPC>
+// CV: the instance of a cost variant (rollout_split_tile).
+template <int HT, int NT3, int G, int BPC, bool CV = false>
 __global__ __launch_bounds__(256, BPC) void nl_plan_fused_kernel(const FusedArgs av) {
   const FusedCtl& a = av.ctl;  // role assignment; the roles read av through role_args()
   constexpr int KSG = G / 4;  // GRU k-steps
@@ -476,7 +477,7 @@ __global__ __launch_bounds__(256, BPC) void nl_plan_fused_kernel(const FusedArgs
       fused_encode<G>(smem, a.chain_first_tiles, -1, 0);
       __syncthreads();  // the GRU images in LDS are dead
     }
-    fused_rollout<HT, NT3>(tile, smem, sync + kFusedCuState + cu);
+    fused_rollout<HT, NT3, CV>(tile, smem, sync + kFusedCuState + cu);
     __hip_atomic_store(sync + kFusedCuState + cu, 2u, NLC_RLX_AGENT);  // (all waves, same word) wakes this CU's sleeper
   }
 
@@ -504,7 +505,7 @@ __global__ __launch_bounds__(256, BPC) void nl_plan_fused_kernel(const FusedArgs
     tile = __builtin_amdgcn_readfirstlane(s_tile[0]);
     __syncthreads();
     if (tile == -2) break;
-    if (tile >= 0) fused_rollout<HT, NT3>(tile, smem);
+    if (tile >= 0) fused_rollout<HT, NT3, CV>(tile, smem);
   }
 
   if (NLC_FUSED_TRACE && wv == 0) wave_add_one(sync + kFusedStatExited, lane);
@@ -532,6 +533,11 @@ hipError_t fused_max_resident_blocks_ht(int bpc_built, int* blocks_per_cu) {
 
 template <int HT, int BPC>
 hipError_t launch_nl_plan_fused_bpc(const FusedArgs& a, unsigned grid, hipStream_t s) {
+  // (same launch bounds, so the same workgroups per CU as the default instance: fused_max_resident_blocks_ht holds for both)
+  if (a.r.cost_variant != 0)
+    return launch_nt3<kFusedMaxNt3>(a.r.net.nt3, [&](auto nt3) {
+      hipLaunchKernelGGL((nl_plan_fused_kernel<HT, nt3, FusedWidth<HT>::G, BPC, true>), dim3(grid), dim3(256), 0, s, a);
+    });
   return launch_nt3<kFusedMaxNt3>(a.r.net.nt3, [&](auto nt3) {
     hipLaunchKernelGGL((nl_plan_fused_kernel<HT, nt3, FusedWidth<HT>::G, BPC>), dim3(grid), dim3(256), 0, s, a);
   });

@@ -372,6 +372,23 @@ inline unsigned long long* pin_seq_word(nlc_ctx* c) { return reinterpret_cast<un
 inline unsigned* pin_merge_status_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned + c->pin.merge_status); }
 WeightArgs make_weight_args(nlc_ctx* c, const nlc_mppi_buffers* buf);
 int run_weights(nlc_ctx* c, const nlc_mppi_buffers* buf);
+// The configured cost variant, 0 with cost_external; a flipped bit without NLC_COST_CHANGE_GOAL selects nothing.
+inline int cost_variant_of(const nlc_mppi_desc& d) {
+  if (d.cost_external || !(d.cost_variant & (NLC_COST_STATE_CONSTRAINT | NLC_COST_CHANGE_GOAL))) return 0;
+  return d.cost_variant;
+}
+// A cost variant runs INSIDE the latency-split rollout and the one-launch body, on their CV
+// instances (cost_in_body puts env and the bits into the argument block).  Every other body leaves the running cost out
+// (env = -1, as for the caller's own cost with cost_external) and variant_cost_kernel evaluates it on the stored states
+// before the weights (finish_rollout_costs with in_body = false).
+template <class A>
+void cost_in_body(A& a, const nlc_mppi_desc& d) {
+  if (cost_variant_of(d)) {
+    a.env = d.env;
+    a.cost_variant = cost_variant_of(d);
+  }
+}
+int finish_rollout_costs(nlc_ctx* c, const nlc_mppi_buffers* buf, bool in_body = false);
 
 // One phase-1 call (nlc_mppi_rollout, or its re-run after a fused time-out) as the dynamics-specific parts see it
 struct RolloutCall {

@@ -282,6 +282,7 @@ struct RolloutArgs {  // (spells the fields of SampleCostArgs out: see there)
   double sigma_inv[NLC_MAX_NU * NLC_MAX_NU];
   double lambda_, u_scale;
   int noise_abs_cost;
+  int cost_variant;         // NLC_COST_* bits, read by the CV instances only (in what was padding: no argument moves)
   double tn;                // normalised prediction time (constant over the rollout)
   // horizon chunking: this launch runs steps [t_begin, t_end); state and the two cost sums are carried between
   // launches in xcarry (K, d) / ccarry (K, 2) so the GRU encode of later steps can overlap earlier rollout steps
@@ -382,6 +383,20 @@ struct OracleRolloutArgs : SampleCostArgs {
 };
 static_assert(std::is_trivially_copyable<OracleRolloutArgs>::value, "passed to its kernel by value");
 hipError_t launch_oracle_rollout(const OracleRolloutArgs& a, hipStream_t s);
+
+// ------------------------------------------------------------------ running cost of a cost variant on the stored rollout
+// nlc_mppi_desc.cost_variant: the rollout body ran with env = -1 (no running cost, as with cost_external) and left the states
+// and the perturbation cost; cost_total[k] = sum_t running_cost_variant(x[k, t], u_scale * perturbed[k, t]) + cost_total[k]
+// (the reference's order: rollout cost, then the perturbation cost, planners/mppi_delay.py:339-344).  K: all local samples.
+struct VariantCostArgs {
+  int64_t K;
+  int T, nu, d, env, variant;
+  double u_scale;
+  const double* states;     // (K, T, d)
+  const double* perturbed;  // (K, T, nu)
+  double* cost_total;       // (K)
+};
+hipError_t launch_variant_cost(const VariantCostArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ NODE baseline (train_utils.py:637-738)
 struct NodeNetArgs {

@@ -145,12 +145,12 @@ __global__ __launch_bounds__(256) void nl_rollout_kernel(const RolloutArgs a) {
 
 // ------------------------------------------------------------------ latency-split rollout (small K per GPU)
 // one workgroup per 16-sample tile: rollout_split_tile (nlc_rollout.h), GRU latents from the (K, T, 2) tensor
-template <int HT, int NT3, bool LIN = false>
+template <int HT, int NT3, bool LIN = false, bool CV = false>
 __global__ __launch_bounds__(256) void nl_rollout_split_kernel(const RolloutArgs a) {
   constexpr int KS = HT * 4;
   __shared__ double H1[KS * 64], H2[KS * 64], AX[4 * 2 * 64];
   PaDirect src{a.pa, a.T, 0.0, 0.0, 0.0, 0.0};
-  rollout_split_tile<HT, NT3, PaDirect, LIN>(a, (int64_t)blockIdx.x, src, H1, H2, AX);
+  rollout_split_tile<HT, NT3, PaDirect, LIN, kCwStandalone, kSplitPrefetch, CV>(a, (int64_t)blockIdx.x, src, H1, H2, AX);
 }
 
 // ------------------------------------------------------------------ single model forward, per-sample t

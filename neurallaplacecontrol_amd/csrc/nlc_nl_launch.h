@@ -12,10 +12,15 @@ hipError_t launch_nl_rollout_ht(const RolloutArgs& a, hipStream_t s, bool split)
     if (a.net.Cp2 == nullptr || a.net.lin != 1) return hipErrorInvalidValue;
   }
   if (split) {
+    if (a.cost_variant != 0)  // the cost variant's instance of the body
+      return launch_nt3(a.net.nt3, [&](auto nt3) {
+        hipLaunchKernelGGL((nl_rollout_split_kernel<HT, nt3, LIN, true>), dim3((unsigned)((a.K + 15) / 16)), dim3(256), 0, s, a);
+      });
     return launch_nt3(a.net.nt3, [&](auto nt3) {
       hipLaunchKernelGGL((nl_rollout_split_kernel<HT, nt3, LIN>), dim3((unsigned)((a.K + 15) / 16)), dim3(256), 0, s, a);
     });
   }
+  if (a.cost_variant != 0) return hipErrorInvalidValue;  // (the wave-per-tile body has no such instance: the host's post-pass)
   return launch_nt3(a.net.nt3, [&](auto nt3) {
     hipLaunchKernelGGL((nl_rollout_kernel<HT, nt3, LIN>), dim3((unsigned)((a.K + 63) / 64)), dim3(256), 0, s, a);
   });

@@ -570,7 +570,9 @@ struct PaDirect {
 };
 
 // Returns the sample's total cost (meaningful in wave CW when the launch runs the last horizon chunk).
-template <int HT, int NT3, class PA, bool LIN = false, int CW = kCwStandalone, int D = kSplitPrefetch>
+// CV: the instance of a cost variant (nlc_mppi_desc.cost_variant): its running cost is running_cost_variant, whose double exp
+// costs 30 to 40 vector registers -- a compile-time parameter, so that the default instances are the ones they were.
+template <int HT, int NT3, class PA, bool LIN = false, int CW = kCwStandalone, int D = kSplitPrefetch, bool CV = false>
 __device__ __forceinline__ double rollout_split_tile(const RolloutArgs& a, int64_t tile, PA& src, double* __restrict__ H1,
                                                      double* __restrict__ H2, double* __restrict__ AX) {
   constexpr int KS = HT * 4;           // k-steps over the hidden dimension
@@ -632,7 +634,10 @@ __device__ __forceinline__ double rollout_split_tile(const RolloutArgs& a, int64
       }
       pc += src.U(a, uoff, tc, j) * acj;
     }
-    cost += running_cost(a.env, xs, u, a.nu);
+    if constexpr (CV)
+      cost += running_cost_variant(a.env, a.cost_variant, xs, u, a.nu);
+    else
+      cost += running_cost(a.env, xs, u, a.nu);
     pcost += pc;
   };
   SplitClk clk;

@@ -15,6 +15,9 @@ with one HIP launch (``nlc_env_step``), so a control step next to ``BatchedMPPID
 Same per-env semantics as the reference classes (``envs/oderl/envs/ct{cartpole,pendulum,acrobot}.py``): ``reset``
 draws from each env's own ``RandomState`` stream (``seed + e``), ``state`` is the reduced state, ``get_obs`` the trig
 observation, the reward is ``diff_reward(new_state, applied_action)``.
+
+:func:`evaluate_episodes` is the harness's ``loop()`` (``mppi_with_model.py:244-300``) around the two, with its
+``state_constraint`` / ``change_goal`` experiment flags.
 """
 
 import math
@@ -105,3 +108,63 @@ class BatchedEnv:
         )
         self.time_step += 1
         return self._obs, self._reward
+
+
+def _same_cost_branch(a, b):
+    """Two ``EnvCost`` of the same env and the same branch (``change_goal_flipped`` may differ: it moves during an episode)."""
+    flags = ("state_constraint", "change_goal")
+    if not any(getattr(a, n, False) or getattr(b, n) for n in flags):
+        return True  # default branch on both sides (or a cost of the caller's own beside the default)
+    return all(getattr(a, n, None) == getattr(b, n) for n in ("env_name",) + flags)
+
+
+def evaluate_episodes(env_name, dynamics, num_envs=1, *, state_constraint=False, change_goal=False, flip_goal_at=None,
+                      steps=None, timelen=10.0, dt=0.05, action_delay=0, action_buffer_size=4, friction=False, roll_outs=1000,
+                      time_steps=40, lambda_=1.0, sigma=1.0, seed=0, device=None, planner=None, env=None):
+    """The evaluation harness's ``loop()`` (``mppi_with_model.py:231-300``) for ``num_envs`` episodes on the device.  With
+    ``num_envs > 1`` (``BatchedMPPIDelay``) a control step makes no host round trip; with ``num_envs == 1`` the single
+    ``MPPIDelay`` reads the state and the action buffer on the host, one synchronisation per step.  Returns ``(total_reward (E), actions (steps, E, nu))`` device tensors.
+
+    ``state_constraint`` / ``change_goal`` (``:42-43``) select the branch of the planner's cartpole running cost; the reward
+    summed here is the env's own, as ``integrate_system`` computes it.  With ``change_goal`` the episode is twice as long
+    (``:235-239``).  In the reference the goal never flips: ``loop()`` assigns a LOCAL ``change_goal_flipped`` (``:251-253``,
+    no ``global`` statement), so the closure keeps reading ``False``; the default (``flip_goal_at=None``) reproduces that.
+    ``flip_goal_at=n`` performs the flip the code evidently meant: from control step ``n`` on the goal is x = +2
+    (one host word per flip, ``nlc_mppi_set_goal_flipped``).
+
+    ``dynamics``: ``"oracle"`` or a trained model (as ``collect_expert_dataset``).  ``planner`` / ``env``: objects to run
+    instead of building them (the planner's cost must be the ``EnvCost`` of the flags)."""
+    from .collector import _make_planner
+    from .envs import EnvCost
+
+    if flip_goal_at is not None and not change_goal:
+        raise ValueError("flip_goal_at needs change_goal=True")
+    if env is None:
+        env = BatchedEnv(env_name, num_envs, dt=dt, action_delay=action_delay, action_buffer_size=action_buffer_size,
+                         friction=friction, device=device, seed=seed)
+    cost = EnvCost(env_name, state_constraint=state_constraint, change_goal=change_goal)
+    if planner is None:
+        planner = _make_planner(env_name, action_delay, env.E, dynamics, roll_outs, time_steps, lambda_, sigma, dt, friction,
+                                False, seed, env.device, cost=cost)
+    elif not _same_cost_branch(getattr(planner, "running_cost", None), cost):
+        raise ValueError("the planner's running cost is not the EnvCost of state_constraint / change_goal given here")
+    if steps is None:
+        steps = int((timelen * 2.0 if change_goal else timelen) / dt)
+    if change_goal:
+        planner.running_cost.change_goal_flipped = False  # :231-232
+    single = getattr(planner, "E", 1) == 1
+    total = torch.zeros(env.E, dtype=torch.float64, device=env.device)
+    actions = torch.empty(int(steps), env.E, env.nu, dtype=torch.float64, device=env.device)
+    obs = env.reset(harness_start=True)
+    with torch.no_grad():
+        for it in range(int(steps)):
+            if flip_goal_at is not None and it >= flip_goal_at:
+                planner.running_cost.change_goal_flipped = True
+            if single:
+                act = planner.command(obs[0], env.action_buffer[0]).reshape(1, env.nu)
+            else:
+                act = planner.command(obs, env.action_buffer)
+            actions[it] = act
+            obs, reward = env.step(act)
+            total += reward
+    return total, actions

@@ -7,7 +7,8 @@ closure's semantics, which is what the generic (external-callable) planner path 
 
   NLDynamics(model, ts_pred)          state + model(state, window, ts_pred)          mppi_with_model.py:103-122
   OracleDynamics(env, ts, delay)      oracle.*_dynamics_dt_delay                      mppi_with_model.py:129-143
-  EnvCost(env)                        -(diff_obs_reward_ + diff_ac_reward_)           mppi_with_model.py:145-171
+  EnvCost(env, state_constraint=,     -(diff_obs_reward_ + diff_ac_reward_), all three mppi_with_model.py:145-171
+          change_goal=)               branches of the closure
 """
 
 import math
@@ -78,13 +79,47 @@ def _trig2angle(c, s):
 
 class EnvCost:
     """Running cost of the three reference envs on the trig observation, and of cartpole on its raw 4-dim state
-    (``obs_trans=False``); same formulas as the HIP kernels."""
+    (``obs_trans=False``); same formulas as the HIP kernels.
 
-    def __init__(self, env_name):
+    ``state_constraint`` / ``change_goal`` select the closure's non-default branches (``mppi_with_model.py:146-162`` ->
+    ``ctcartpole.py:311-329``), which only the cartpole env class has: the soft wall ``exp(10 e0 + 7)`` on the cart
+    position, or the goal moved to x = -2 (+2 once ``change_goal_flipped`` is set).  As in the closure's ``if / elif``,
+    ``state_constraint`` wins.  ``change_goal_flipped`` is the reference's module global: it may be assigned at any time
+    and the planner's next ``command()`` sees it (no reconfiguration; ``U`` and the noise stream do not move)."""
+
+    def __init__(self, env_name, state_constraint=False, change_goal=False, change_goal_flipped=False):
         self.env_name = _check_env(env_name)
+        self.state_constraint, self.change_goal = bool(state_constraint), bool(change_goal)
+        self.change_goal_flipped = bool(change_goal_flipped)
+        if (self.state_constraint or self.change_goal or self.change_goal_flipped) and "cartpole" not in self.env_name:
+            raise ValueError(f"{env_name}: only the cartpole env has a state_constraint / change_goal cost (ctcartpole.py:311-329)")
+
+    @property
+    def variant(self):
+        """The ``NLC_COST_*`` bits of ``nlc_mppi_desc.cost_variant`` (include/nlc.h)."""
+        if self.state_constraint:
+            return _lib.COST_STATE_CONSTRAINT
+        if self.change_goal:
+            return _lib.COST_CHANGE_GOAL | (_lib.COST_GOAL_FLIPPED if self.change_goal_flipped else 0)
+        return 0
+
+    def _cartpole(self, x, sl, cl, xd, thd, uu):
+        goal_x = (2.0 if self.change_goal_flipped else -2.0) if (self.change_goal and not self.state_constraint) else 0.0
+        e0, e1 = x + sl - goal_x, cl - 1.0
+        if self.state_constraint:
+            sr = -((e0 * e0 + torch.exp(e0 * 10.0 + 7.0)) + e1 * e1)
+        else:
+            sr = -(e0 * e0 + e1 * e1)
+        vr = -(xd * xd) - thd * thd
+        return -((sr + 0.01 * vr) + (-0.01 * uu))
 
     def __call__(self, state, action):
         uu = (action * action).sum(-1)
+        if self.variant and self.env_name == "oderl-cartpole":
+            return self._cartpole(state[..., 0], state[..., 3], state[..., 2], state[..., 1], state[..., 4], uu)
+        if self.variant:  # ctcartpole.py:297-300: explicit angle
+            return self._cartpole(state[..., 0], 1.0 * torch.sin(state[..., 2]), 1.0 * torch.cos(state[..., 2]), state[..., 1],
+                                  state[..., 3], uu)
         if self.env_name == "oderl-cartpole":
             e0, e1 = state[..., 0] + state[..., 3] - 0.0, state[..., 2] - 1.0
             sr = -(e0 * e0 + e1 * e1)

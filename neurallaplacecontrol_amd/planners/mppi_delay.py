@@ -8,9 +8,11 @@ lambda_ u_scale``).  Everything numeric runs in HIP kernels behind ``libnlc_hip.
   :class:`~neurallaplacecontrol_amd.envs.OracleDynamics` and ``running_cost`` an
   :class:`~neurallaplacecontrol_amd.envs.EnvCost`: one ``command()`` = shift/perturb kernel, hoisted GRU
   encode over all K*T windows, one persistent T-step rollout kernel, softmax-weight reduction, U update.
+  An ``EnvCost`` built with ``state_constraint`` / ``change_goal`` (the closure's other two branches,
+  ``mppi_with_model.py:146-162``) stays on this path: the latency-split and one-launch bodies evaluate it themselves,
+  behind the other bodies one more HIP launch evaluates it on the stored rollout before the weights; assigning its ``change_goal_flipped`` between two commands costs one host word.
 * fused dynamics + cost callables -- same rollout kernel, but ``running_cost`` (and ``terminal_state_cost``) are
-  arbitrary callables, e.g. the harness's ``state_constraint`` / ``change_goal`` closures
-  (``mppi_with_model.py:145-171``): the states do not depend on the cost, so the callables run once per horizon step
+  arbitrary callables: the states do not depend on the cost, so the callables run once per horizon step
   on the stored (K, T, nx) device states after the kernel (``nlc_mppi_desc.cost_external``).
 * generic path -- arbitrary dynamics callables (the reference's contract): sampling, bounding, weighting and the
   U update are the same HIP kernels; the T-step loop calls the user's callables on device tensors.
@@ -177,7 +179,7 @@ class MPPIDelay:
                 and self.E == 1 and type(self) is MPPIDelay and not self.torch_path):
             cd = _recognise.candidate_dynamics(dynamics)
             if cd is not None:
-                self._candidate = (cd, _recognise.candidate_cost(running_cost) or running_cost)
+                self._candidate = (cd, _recognise.candidate_cost(running_cost, variants=True) or running_cost)
         planner_options = opts_in
 
         if compute_device is None:
@@ -259,6 +261,7 @@ class MPPIDelay:
         self._B = None
         self._buf = None
         self._pending_U = None
+        self._variant_sent = 0  # the cost_variant bits the library holds
 
         # sampled results from the last command (device tensors; exposed through the properties below)
         self._noise = self._perturbed = self._states = self._actions = None
@@ -272,6 +275,11 @@ class MPPIDelay:
 
     def _decide_mode(self, dynamics, running_cost):
         """Which planner path the (dynamics, running_cost) pair runs on: fused / fused dynamics + cost callables / generic."""
+        # the literal closure behind a recognised change_goal cost: its module global change_goal_flipped is re-read before
+        # every command, as the closure itself reads it at every call (mppi_with_model.py:153-158)
+        self._flip_source = None
+        if isinstance(running_cost, EnvCost) and running_cost is not getattr(self, "running_cost", running_cost):
+            self._flip_source = _recognise.flip_source(self.running_cost, running_cost)
         self.F = dynamics
         self.running_cost = running_cost
         self.store_rollouts = self._store_rollouts_arg
@@ -289,8 +297,8 @@ class MPPIDelay:
         # otherwise, with fused dynamics, the cost callables (the harness's state_constraint / change_goal closures,
         # a terminal cost, ...) run on the stored device states after the rollout: the states do not depend on them
         self.cost_external = self.fused_dynamics and not self.fused
-        if self.cost_external:
-            self.store_rollouts = True  # the cost callables read the stored states
+        if self.cost_external or (self.fused and running_cost.variant):
+            self.store_rollouts = True  # the cost callables / the cost variant's kernel read the stored states
         if self.M > 1:
             # rollout_samples M > 1 (reference :291-292, 310).  The reference never replicates the state M times: its M
             # cost rows are copies and ``c.var(dim=0)`` is the variance of the running cost OVER THE K SAMPLES, one number
@@ -316,6 +324,8 @@ class MPPIDelay:
         command's state and action buffer, a private noise draw) and switch to the fused path iff they agree."""
         cand, self._candidate = self._candidate, None
         literal = (self.F, self.running_cost)
+        if isinstance(cand[1], EnvCost):
+            _recognise.follow_flip(_recognise.flip_source(self.running_cost, cand[1]), cand[1])
 
         def make(dyn, cost, horizon):
             return MPPIDelay(
@@ -376,11 +386,13 @@ class MPPIDelay:
                 d.delay, d.friction = self.F.delay, int(self.F.friction)
         else:
             d.dynamics = _lib.DYN_EXTERNAL
+        d.cost_variant = self.running_cost.variant if self.fused else 0
         old_U = None
         if self._B is not None:
             old_U = self.U
         self.ctx.check(self.ctx.lib.nlc_mppi_configure(self.ctx.h, C.byref(d)))
         self._B = B
+        self._variant_sent = d.cost_variant
         K, T, nu, nx, dev = self.K_local, self.T, self.nu, self.nx, self.cd
         mk = lambda *s: torch.empty(self._lead(*s), dtype=torch.float64, device=dev)  # noqa: E731
         self._noise, self._perturbed = mk(K, T, nu), mk(K, T, nu)
@@ -410,6 +422,16 @@ class MPPIDelay:
     def _ensure_configured(self, B):
         """(Re)configure when the action-buffer length or the model's weights changed since the last command."""
         stale = self._buf is None or B != self._B
+        if self.fused:
+            _recognise.follow_flip(self._flip_source, self.running_cost)
+            moved = self.running_cost.variant ^ self._variant_sent
+            if moved == _lib.COST_GOAL_FLIPPED and not stale:
+                # change_goal_flipped was assigned since the last command: one host word, nothing is reconfigured
+                flipped = int(bool(self.running_cost.variant & _lib.COST_GOAL_FLIPPED))
+                self.ctx.check(self.ctx.lib.nlc_mppi_set_goal_flipped(self.ctx.h, flipped))
+                self._variant_sent = self.running_cost.variant
+            elif moved:
+                stale = True  # another branch of the cost: a new descriptor (U is carried over)
         if self.fused_dynamics and isinstance(self.F, NLDynamics):
             model = self.F.model
             _recognise.refresh_twin(model)  # a twin of a reference model instance follows that instance's weight updates
