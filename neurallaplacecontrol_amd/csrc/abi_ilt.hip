@@ -135,27 +135,15 @@ extern "C" int nlc_ilt_reconstruct(nlc_ctx* c, const nlc_ilt_desc* d, const doub
   if (N == 0) return NLC_OK;
   if (!theta || !phi || !t || !x) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
-  IltArgs a{theta, phi, t, x, N, dd, d->terms, d->alpha, std::log(d->tol), d->scale, nullptr, nullptr, 1.0, 1, 0, 0};
+  IltArgs a = ilt_args(*d, theta, phi, t, x, N, dd);
   if (d->algo == NLC_ILT_FIXED_TALBOT || d->algo == NLC_ILT_STEHFEST) {
     const double* tab = nullptr;
     if (int r = linear_tables(c, d, &tab)) return r;
-    // the Fourier kernel's coalesced stream with the algorithm's per-term phase and weight (round 3); the one-thread-per-row
-    // kernel remains for a term count the stream's tiling does not take
+    // the Fourier kernels with the algorithm's per-term phase and weight (round 3): every term count has a tile there
     a.lin_wr = tab + 2 * d->terms;
     a.lin_wi = tab + 3 * d->terms;
-    hipError_t le;
-    {
-      ProfScope ps(c, "ilt_linear_stream_kernel");
-      le = launch_ilt_fourier(a, c->stream);
-    }
-    if (le == hipErrorInvalidValue) {
-      (void)hipGetLastError();
-      IltLinArgs la{theta, phi, t, x, N, dd, d->terms, a.lin_wr, a.lin_wi};
-      ProfScope ps(c, "ilt_linear_kernel");
-      NLC_HIP(c, launch_ilt_linear(la, c->stream));
-    } else {
-      NLC_HIP(c, le);
-    }
+    ProfScope ps(c, "ilt_linear_stream_kernel");
+    NLC_HIP(c, launch_ilt_fourier(a, c->stream));
   } else if (d->algo == NLC_ILT_FOURIER) {
     ProfScope ps(c, "ilt_fourier_kernel");
     NLC_HIP(c, launch_ilt_fourier(a, c->stream));
@@ -186,7 +174,7 @@ extern "C" int nlc_ilt_reconstruct_backward(nlc_ctx* c, const nlc_ilt_desc* d, c
     const int64_t bytes = ilt_dehoog_bwd_scratch_bytes(N, dd, d->terms, nullptr);
     void* scratch = nullptr;
     NLC_HIP(c, hipMallocAsync(&scratch, (size_t)bytes, c->stream));
-    IltDehoogBwdArgs da{theta, phi, t, grad_x, grad_theta, grad_phi, N, dd, d->terms, d->alpha, std::log(d->tol), d->scale, 1.0, scratch};
+    const IltDehoogBwdArgs da = ilt_dehoog_bwd_args(*d, theta, phi, t, grad_x, grad_theta, grad_phi, N, dd, scratch);
     hipError_t le;
     {
       ProfScope ps(c, "ilt_dehoog_bwd_kernel");
@@ -205,7 +193,7 @@ extern "C" int nlc_ilt_reconstruct_backward(nlc_ctx* c, const nlc_ilt_desc* d, c
     NLC_HIP(c, launch_ilt_linear_bwd(la, c->stream));
     return NLC_OK;
   }
-  IltBwdArgs a{theta, phi, t, grad_x, grad_theta, grad_phi, N, dd, d->terms, d->alpha, std::log(d->tol), d->scale, 0, 0};
+  const IltBwdArgs a = ilt_bwd_args(*d, theta, phi, t, grad_x, grad_theta, grad_phi, N, dd);
   ProfScope ps(c, "ilt_fourier_bwd_kernel");
   NLC_HIP(c, launch_ilt_fourier_bwd(a, c->stream));
   return NLC_OK;

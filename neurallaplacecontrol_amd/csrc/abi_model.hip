@@ -333,19 +333,12 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
       ProfScope ps(c, "nl_repfunc_kernel");
       NLC_HIP(c, launch_nl_repfunc(rf, c->stream));
     }
-    IltArgs ia{th, ph, ts, out, N, dd, S, c->md.ilt.alpha, std::log(c->md.ilt.tol), c->md.ilt.scale, nullptr, nullptr, c->md.time_div, 1, 0, 0};
+    IltArgs ia = ilt_args(c->md.ilt, th, ph, ts, out, N, dd);
+    ia.t_div = c->md.time_div;
     ia.lin_wr = tab + 2 * S;
     ia.lin_wi = tab + 3 * S;
-    hipError_t le;
-    {
-      ProfScope ps(c, "ilt_linear_stream_kernel");
-      le = launch_ilt_fourier(ia, c->stream);
-    }
-    if (le == hipErrorInvalidValue) {
-      (void)hipGetLastError();
-      return fail(c, NLC_ERR_UNSUPPORTED, "nlc_model_forward: this term count does not fit the stream kernel's tiling");
-    }
-    NLC_HIP(c, le);
+    ProfScope ps(c, "ilt_linear_stream_kernel");
+    NLC_HIP(c, launch_ilt_fourier(ia, c->stream));
     return NLC_OK;
   }
   if (c->md.ilt.algo == NLC_ILT_DEHOOG) {
@@ -369,8 +362,10 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
       ProfScope ps(c, "nl_repfunc_kernel");
       NLC_HIP(c, launch_nl_repfunc(rf, c->stream));
     }
-    IltArgs ia{nullptr, nullptr, ts, out, N, c->md.d, c->S, c->md.ilt.alpha, std::log(c->md.ilt.tol), c->md.ilt.scale,
-               fre, fim, c->md.time_div, 1, 0, 0};
+    IltArgs ia = ilt_args(c->md.ilt, nullptr, nullptr, ts, out, N, c->md.d);
+    ia.fre = fre;
+    ia.fim = fim;
+    ia.t_div = c->md.time_div;
     ProfScope ps(c, "ilt_dehoog_kernel");
     NLC_HIP(c, launch_ilt_dehoog(ia, c->stream));
     return NLC_OK;

@@ -195,8 +195,11 @@ int launch_staged_steps(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc,
   // epilogue, one full line per de Hoog load (kernels_ilt.hip, FMODE 2)
   rf.slot_major = 1;
   rf.split = c->md.h == 128 && c->opt.repfunc_split != 0;
-  IltArgs ia{nullptr, nullptr, tconst, ws + w.dx, KE, d.d, c->S, c->md.ilt.alpha, std::log(c->md.ilt.tol),
-             c->md.ilt.scale, rf.fre, rf.fim, 1.0, 0, 0, 0, c->eidx_dev};
+  IltArgs ia = ilt_args(c->md.ilt, nullptr, nullptr, tconst, ws + w.dx, KE, d.d);
+  ia.fre = rf.fre;
+  ia.fim = rf.fim;
+  ia.t_stride = 0;  // one prediction time for every sample
+  ia.eidx = c->eidx_dev;
   StepTailArgs st{sc};
   st.d = d.d;
   st.x = r.xcarry;

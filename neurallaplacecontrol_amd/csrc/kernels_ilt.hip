@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "nlc_device.h"
+#include "nlc_ilt_tile.h"
 #include "nlc_kernels.h"
 
 namespace nlc {
@@ -64,36 +65,12 @@ hipError_t launch_rep_inputs(const RepInArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------ linear closed-form algorithms (fixed Talbot, Stehfest)
-// One thread per (point, dim) row walks its S (theta, phi) pairs; a wavefront's 64 rows are 64 * S contiguous doubles,
-// so the lines it touches are shared by neighbouring threads' later iterations (L1 / L2 hits).  Not a tuned stream like
-// the Fourier kernel: these two algorithms exist for coverage of the reference's nl_ilt_algorithm knob.
-__global__ __launch_bounds__(256) void ilt_linear_kernel(const IltLinArgs a) {
-  const int64_t rows = a.N * a.d;
-  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (int64_t)gridDim.x * blockDim.x) {
-    const double* th = a.theta + row * a.S;
-    const double* ph = a.phi + row * a.S;
-    double acc = 0.0;
-    for (int k = 0; k < a.S; ++k) {
-      const double rad = m::tan_0_halfpi(ph[k] / 2.0 + kPi / 4.0);
-      double sn, cs;
-      m::sincos_bounded(th[k], &sn, &cs);
-      acc += a.wr[k] * (rad * cs) - a.wi[k] * (rad * sn);
-    }
-    a.x[row] = acc / a.t[row / a.d];
-  }
-}
-hipError_t launch_ilt_linear(const IltLinArgs& a, hipStream_t s) {
-  const int64_t rows = a.N * a.d;
-  if (rows <= 0) return hipSuccess;
-  const int64_t want = (rows + 255) / 256;
-  hipLaunchKernelGGL(ilt_linear_kernel, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
+// The stand-alone reconstruction of these two rides the Fourier kernels below (their general-phase instances: ilt_lane_linear);
+// here are the planner's slot-major form and the backward.
 // Planner path (round 3): F_k = (re, im) arrives SLOT-major (8*nt3, N) from the representation kernel's MFMA epilogue,
 // as for the de Hoog planner (kernels_dehoog.hip, FMODE 2): a wavefront owns 64 consecutive samples of ONE dim, term k of
-// its rows is one full 512-B line per array, and the kernel reads exactly d * S * 16 B per sample.  Same summation order
-// as ilt_linear_kernel.  t is one device scalar (the planner's constant prediction time).
+// its rows is one full 512-B line per array, and the kernel reads exactly d * S * 16 B per sample.  Terms are added in
+// the order k = 0 .. S - 1.  t is one device scalar (the planner's constant prediction time).
 __global__ __launch_bounds__(64) void ilt_linear_slot_kernel(const IltLinSlotArgs a) {
   const int lane = threadIdx.x;
   const int64_t nsb = (a.N + 63) / 64;
@@ -248,7 +225,11 @@ __device__ __forceinline__ double ilt_term(const m::IltTrigK& K, double t_u, dou
   ilt_args(t_u, p_u, L.psi, &xt, &xp);
   return ilt_term2(K, xt, xp, L);
 }
-__device__ __forceinline__ double ilt_row_scale(const IltArgs& a, double t) {
+// what the Fourier series' row scale e^{gamma t} / T reads of a launch's arguments (forward or backward)
+struct IltScaleK {
+  double alpha, log_tol, scale;
+};
+__device__ __forceinline__ double ilt_row_scale(const IltScaleK& a, double t) {
   // once per row, but at one row per 17 terms its IEEE divisions and libm exp were ~10 % of the kernel's instructions
   const double Tt = a.scale * t;
   const double gamma = a.alpha - m::div_fast(a.log_tol, a.scale * Tt);
@@ -277,7 +258,7 @@ __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_
   const int64_t nblk = (rows_total + rows - 1) / rows;
   constexpr int UB = 8;  // pipeline depth in passes; the launcher makes iters a multiple of UB
   // (LIN: t_div is the model's time normalisation when the model forward drives this kernel, 1 otherwise)
-  auto row_scale = [&](double t) { return LIN ? m::div_fast(a.t_div, t) : ilt_row_scale(a, t); };
+  auto row_scale = [&](double t) { return LIN ? m::div_fast(a.t_div, t) : ilt_row_scale(IltScaleK{a.alpha, a.log_tol, a.scale}, t); };
   int64_t blk = blockIdx.x;
 
   if constexpr (ITERS > 0) {
@@ -405,13 +386,19 @@ __global__ __launch_bounds__(256, (ITERS == 8 || ITERS == 16) ? 4 : 3) void ilt_
 // wavefront only waits for its own loads), no LDS writes by the ALU, the term index -- so the quarter turn i^k of the phase and
 // the sign of the weight -- a compile-time constant, the tangent as one rational (m::tan_parts_rat): ~38 instructions per pair.
 // Eight wavefronts per CU (2 x 34 KB regions per workgroup of four at S = 17), each with a whole tile in flight while its SIMD
-// partner computes.  Instances: S = 17 and S = 33 (the reference's default and its de Hoog ablation's term count) with scale = 2
-// (torchlaplace's default: e^{i pi k t / T} = i^k); anything else -- other term counts, another scale, the linear algorithms,
-// unaligned inputs -- keeps ilt_fourier_kernel.
-// GEN = false: scale == 2, the phase of term k is i^k (compile-time quarter turn and sign, w_0 = 1/2).
+// partner computes.  Which launches it takes is ilt_tile::rows_fwd_accepts (nlc_ilt_tile.h); ilt_fourier_kernel keeps the rest.
+// GEN = false: scale == 2 (torchlaplace's default), the phase e^{i pi k t / T} of term k is i^k (compile-time quarter turn and
+// sign, w_0 = 1/2).
 // GEN = true: a per-term phase psi_k and weight w_k from a small table in LDS (`tab`: psi_0, w_0, psi_1, w_1, ...; every lane
 // reads the same address: a broadcast) -- the Fourier series at another scale (psi_k = pi k / scale) and the linear algorithms
 // (fixed Talbot / Stehfest: w_re Re F - w_im Im F = |w| R cos(theta + arg w), kernels above).
+
+// tan(phi/2 + pi/4) = num / den: the argument rounded as the reference rounds it (w_nl.py: tan of the SUM), then a = x - pi/4
+__device__ __forceinline__ void ilt_row_tan_parts(const m::IltRowK& K, double ph, double* num, double* den) {
+  const double x = fma(ph, 0.5, kPi / 4.0);
+  const double a = (x - K.pio4_hi) - K.pio4_lo;
+  m::tan_parts_rat(K, a, num, den);
+}
 template <int S, bool GEN, class LD>
 __device__ __forceinline__ double ilt_row_sum(const m::IltRowK& K, const double* tab, LD ld) {
   double acc = 0.0;
@@ -419,11 +406,8 @@ __device__ __forceinline__ double ilt_row_sum(const m::IltRowK& K, const double*
   for (int k = 0; k < S; ++k) {
     double th, ph;
     ld(k, &th, &ph);
-    // tan(phi/2 + pi/4): the argument rounded as the reference rounds it (w_nl.py: tan of the SUM), then a = x - pi/4
-    const double x = fma(ph, 0.5, kPi / 4.0);
-    const double a = (x - K.pio4_hi) - K.pio4_lo;
     double num, den;
-    m::tan_parts_rat(K, a, &num, &den);
+    ilt_row_tan_parts(K, ph, &num, &den);
     const double r = m::rcp_refined(den);
     if (GEN) {
       const double cs = m::cos_or_sin_reduced<0>(K, th + tab[2 * k]);
@@ -477,9 +461,9 @@ __device__ __forceinline__ void ilt_lds_load16(const void* g, unsigned lds_addr)
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(g), "s"(lds_addr) : "memory", "m0");
 }
 #pragma clang diagnostic pop
-template <int TILE>
+template <int S>
 __device__ __forceinline__ void ilt_lds_load_tile(const char* g_lane, unsigned lds_addr, int lane) {
-  constexpr int NLD = TILE / 1024, REM = TILE % 1024;  // whole-wave 16-byte loads + the lanes of the last one
+  constexpr int NLD = ilt_tile::RowTile<S>::NLD, REM = ilt_tile::RowTile<S>::REM;  // whole-wave 16-byte loads + the lanes of the last one
 #pragma unroll
   for (int i = 0; i < NLD; ++i) ilt_lds_load16(g_lane + i * 1024, lds_addr + i * 1024);
   if (REM != 0) {
@@ -495,12 +479,9 @@ __device__ __forceinline__ void ilt_lds_load_tile(const char* g_lane, unsigned l
 // no longer waits for its wavefront to finish the tile before it, at half the FP64 issue rate (one wavefront per SIMD), which
 // this kernel can afford (arithmetic-only 0.043 ms of 0.16).
 template <int S, bool GEN, int DEPTH>
-__global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_fourier_rows_kernel(const IltArgs a) {
-  static_assert(S % 2 == 1, "row stride S doubles must be odd: conflict-free row-wise reads, 16-byte tile sizes");
+__global__ __launch_bounds__(256, ilt_tile::rows_fwd_per_cu(S, DEPTH)) void ilt_fourier_rows_kernel(const IltArgs a) {
   extern __shared__ __attribute__((aligned(16))) char rows_lds[];
-  constexpr int TILE = 64 * S * 8;                          // bytes of one array's tile
-  constexpr int SLOT = (TILE + 1023) / 1024 * 1024;        // its LDS slot: the last (half) load writes a full KB
-  constexpr int LPT = SLOT / 1024;                          // loads per tile and array
+  constexpr int SLOT = ilt_tile::RowTile<S>::SLOT, LPT = ilt_tile::RowTile<S>::LPT;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (wave-uniform: scalar loop, scalar M0)
   char* lt0 = rows_lds + wave * (DEPTH * 2 * SLOT);
   const unsigned lt_addr0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lt0;
@@ -509,22 +490,21 @@ __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_four
   const int64_t nfull = rows_total / 64;
   const int64_t W = (int64_t)gridDim.x * 4, w0 = (int64_t)blockIdx.x * 4 + wave;
   // GEN: the per-term (phase, weight) table behind the four wavefronts' slots -- the launch's only barrier
-  const double* tab = (const double*)(rows_lds + 4 * (DEPTH * 2 * SLOT));
+  const double* tab = (const double*)(rows_lds + ilt_tile::RowTile<S>::lds_bytes(DEPTH, false));
   const bool lin = a.lin_wr != nullptr;
   if (GEN) {
     if ((int)threadIdx.x < S) {
       const int k = threadIdx.x;
       const IltLane L = lin ? ilt_lane_linear(a.lin_wr[k], a.lin_wi[k]) : ilt_lane(k, a.scale);
       // (ilt_lane at scale == 2 describes the quarter turns by dm / a signed weight: spell them out as a phase)
-      double* tw = (double*)(rows_lds + 4 * (DEPTH * 2 * SLOT));
+      double* tw = (double*)(rows_lds + ilt_tile::RowTile<S>::lds_bytes(DEPTH, false));
       tw[2 * k] = L.psi + L.dm * (kPi / 2.0);
       tw[2 * k + 1] = L.wk;
     }
     __syncthreads();
   }
   // the row scale: e^{gamma t} / T of the Fourier series, 1 / t (times the model's time normalisation) of the linear algorithms
-  auto row_scale = [&](double t) { return (GEN && lin) ? m::div_fast(a.t_div, t) : ilt_row_scale(a, t); };
-  // the row's point index n = row / d, kept incrementally: row advances by 64 W per tile
+  auto row_scale = [&](double t) { return (GEN && lin) ? m::div_fast(a.t_div, t) : ilt_row_scale(IltScaleK{a.alpha, a.log_tol, a.scale}, t); };
   const unsigned d = (unsigned)a.d;
   const int64_t step = 64 * W;
   const int64_t step_n = step / d;
@@ -542,11 +522,11 @@ __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_four
     // the data has not reached yet.
     auto req_theta = [&](int64_t tile, bool real, int par) {
       const char* g = real ? (const char*)(a.theta + tile * (64 * S)) + lane * 16 : (const char*)a.theta;  // no successor: the array's head
-      ilt_lds_load_tile<TILE>(g, lt_addr0 + par * (2 * SLOT), real ? lane : 0);
+      ilt_lds_load_tile<S>(g, lt_addr0 + par * (2 * SLOT), real ? lane : 0);
     };
     auto req_phi = [&](int64_t tile, bool real, int par) {
       const char* g = real ? (const char*)(a.phi + tile * (64 * S)) + lane * 16 : (const char*)a.phi;
-      ilt_lds_load_tile<TILE>(g, lt_addr0 + par * (2 * SLOT) + SLOT, real ? lane : 0);
+      ilt_lds_load_tile<S>(g, lt_addr0 + par * (2 * SLOT) + SLOT, real ? lane : 0);
     };
     auto req_t = [&](int64_t nn) {
       double v;
@@ -561,12 +541,11 @@ __global__ __launch_bounds__(256, (S <= 17 && DEPTH == 1) ? 2 : 1) void ilt_four
     }
     int par = 0;  // the region pair of the current tile (DEPTH = 2: alternating)
     for (int64_t tile = w0; tile < nfull; tile += W) {
-      double t_row = req_t(n);                        // queue: theta_n, phi_n, [theta_(n+1), phi_(n+1),] t_n
+      double t_row = req_t(n);                   // queue: theta_n, phi_n, [theta_(n+1), phi_(n+1),] t_n
       const int64_t nxt = tile + DEPTH * W;
       const bool has_next = nxt < nfull;
       const double* lrow_t = (const double*)(lt0 + par * (2 * SLOT)) + lane * S;
       const double* lrow_p = (const double*)(lt0 + par * (2 * SLOT) + SLOT) + lane * S;
-      // the next tile's point index
       int64_t n_next = n + step_n;
       unsigned rem_next = rem + step_r;
       if (rem_next >= d) {
@@ -631,33 +610,23 @@ static bool lds_attr_once(F* fn, size_t shmem, std::atomic<unsigned long long>& 
   done.fetch_or(bit, std::memory_order_release);
   return true;
 }
-// true when the row-per-lane kernel takes the launch: an odd term count 3 .. 33 (row-wise LDS reads are conflict-free for an
-// odd stride; the reference's default 17, its de Hoog ablation's 33, fixed Talbot's 17) and 16-byte aligned inputs
-template <int S, bool GEN, int DEPTH>
-static bool launch_rows_instance(const IltArgs& a, hipStream_t s, hipError_t* err) {
-  constexpr int SLOT = (64 * S * 8 + 1023) / 1024 * 1024;
-  constexpr size_t shmem = (size_t)4 * DEPTH * 2 * SLOT + 2 * S * 8;  // four wavefronts' theta / phi slots + the (phase, weight) table
-  static std::atomic<unsigned long long> attr_done{0};
-  if (!lds_attr_once(ilt_fourier_rows_kernel<S, GEN, DEPTH>, shmem, attr_done)) return false;
-  const int64_t tiles = (a.N * a.d + 63) / 64;
-  const int per_cu = (S <= 17 && DEPTH == 1) ? 2 : 1;  // workgroups of four wavefronts per CU (launch bounds, LDS)
-  int64_t grid = (tiles + 3) / 4;
-  if (grid > 256 * per_cu) grid = 256 * per_cu;
-  hipLaunchKernelGGL((ilt_fourier_rows_kernel<S, GEN, DEPTH>), dim3((unsigned)grid), dim3(256), shmem, s, a);
+// One launch of a row-per-lane kernel instance over `tiles` 64-row tiles; false (nothing launched: the stream kernel takes the
+// call) when the instance's LDS size cannot be set on this device.
+template <class A>
+static bool launch_rows(void (*kernel)(const A), size_t shmem, int per_cu, int64_t tiles, std::atomic<unsigned long long>& attr_done,
+                        const A& a, hipStream_t s, hipError_t* err) {
+  if (!lds_attr_once(kernel, shmem, attr_done)) return false;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)ilt_tile::rows_grid(tiles, per_cu)), dim3(256), shmem, s, a);
   *err = hipGetLastError();
   return true;
 }
-static bool launch_ilt_fourier_rows(const IltArgs& a, hipStream_t s, hipError_t* err) {
-  if (a.S < 3 || a.S > 33 || (a.S & 1) == 0) return false;
-  if (a.lin_wr != nullptr && a.lin_wi == nullptr) return false;
-  if ((((uintptr_t)a.theta) | ((uintptr_t)a.phi)) & 15) return false;  // 16-byte loads
-  const bool gen = a.lin_wr != nullptr || a.scale != 2.0;
-  switch (a.S) {
-  // two tiles in flight per wavefront where two region pairs fit four wavefronts' LDS (S <= 17): 0.160 -> 0.154 ms at S = 17
-#define NLC_ROWS_CASE(SS)                                                                                 \
-  case SS:                                                                                                \
-    return gen ? launch_rows_instance<SS, true, (SS <= 17 ? 2 : 1)>(a, s, err)                            \
-               : launch_rows_instance<SS, false, (SS <= 17 ? 2 : 1)>(a, s, err);
+// f(std::integral_constant<int, S>) for the term counts the row-per-lane kernels have instances of (ilt_tile::rows_term_count)
+template <class F>
+static bool dispatch_rows_terms(int S, F&& f) {
+  switch (S) {
+#define NLC_ROWS_CASE(SS) \
+  case SS:                \
+    return f(std::integral_constant<int, SS>{});
     NLC_ROWS_CASE(3) NLC_ROWS_CASE(5) NLC_ROWS_CASE(7) NLC_ROWS_CASE(9) NLC_ROWS_CASE(11) NLC_ROWS_CASE(13) NLC_ROWS_CASE(15)
     NLC_ROWS_CASE(17) NLC_ROWS_CASE(19) NLC_ROWS_CASE(21) NLC_ROWS_CASE(23) NLC_ROWS_CASE(25) NLC_ROWS_CASE(27) NLC_ROWS_CASE(29)
     NLC_ROWS_CASE(31) NLC_ROWS_CASE(33)
@@ -665,50 +634,52 @@ static bool launch_ilt_fourier_rows(const IltArgs& a, hipStream_t s, hipError_t*
   }
   return false;
 }
+static bool launch_ilt_fourier_rows(const IltArgs& a, hipStream_t s, hipError_t* err) {
+  if (!ilt_tile::rows_fwd_accepts(a.S, a.lin_wr != nullptr, a.lin_wi != nullptr, (uintptr_t)a.theta | (uintptr_t)a.phi)) return false;
+  const bool gen = ilt_tile::rows_fwd_general(a.scale, a.lin_wr != nullptr);
+  const int64_t tiles = (a.N * a.d + 63) / 64;
+  return dispatch_rows_terms(a.S, [&](auto term_count) {
+    // two tiles in flight per wavefront where two region pairs fit four wavefronts' LDS (S <= 17): 0.160 -> 0.154 ms at S = 17
+    constexpr int S = decltype(term_count)::value, DEPTH = ilt_tile::rows_depth(S);
+    static std::atomic<unsigned long long> attr_done[2] = {{0}, {0}};  // per instance: [GEN]
+    return launch_rows(gen ? ilt_fourier_rows_kernel<S, true, DEPTH> : ilt_fourier_rows_kernel<S, false, DEPTH>,
+                       ilt_tile::RowTile<S>::lds_bytes(DEPTH, true), ilt_tile::rows_fwd_per_cu(S, DEPTH), tiles, attr_done[gen], a, s,
+                       err);
+  });
+}
+
+template <bool LIN>
+static hipError_t launch_stream(const IltArgs& a, unsigned grid, size_t shmem, hipStream_t s) {
+  switch (a.iters) {  // whole-tile pipeline unrolled for the passes per tile of the common term counts; 0: runtime loop
+    case 8: hipLaunchKernelGGL((ilt_fourier_kernel<8, LIN>), dim3(grid), dim3(256), shmem, s, a); break;
+    case 16: hipLaunchKernelGGL((ilt_fourier_kernel<16, LIN>), dim3(grid), dim3(256), shmem, s, a); break;
+    case 24: hipLaunchKernelGGL((ilt_fourier_kernel<24, LIN>), dim3(grid), dim3(256), shmem, s, a); break;
+    case 32: hipLaunchKernelGGL((ilt_fourier_kernel<32, LIN>), dim3(grid), dim3(256), shmem, s, a); break;
+    default: hipLaunchKernelGGL((ilt_fourier_kernel<0, LIN>), dim3(grid), dim3(256), shmem, s, a); break;
+  }
+  return hipGetLastError();
+}
 
 hipError_t launch_ilt_fourier(const IltArgs& a_in, hipStream_t s) {
   IltArgs a = a_in;
   const int64_t rows_total = a.N * a.d;
   if (rows_total <= 0) return hipSuccess;
-  if (a.S > 256) return hipErrorInvalidValue;
+  if (a.S < 1 || a.S > ilt_tile::kStreamMaxTerms) return hipErrorInvalidValue;
+  if (a.lin_wr != nullptr && a.lin_wi == nullptr) return hipErrorInvalidValue;
   {
     hipError_t e2 = hipSuccess;
     if (launch_ilt_fourier_rows(a, s, &e2)) return e2;
   }
-  // rows per block tile = rpp * iters: one thread per row for the final sum (<= 256), LDS tile under 60 KiB
-  const int SP = a.S | 1;
-  a.rpp = 256 / a.S;
-  int max_rows = (60 * 1024 / 8) / SP;
-  if (max_rows > 256) max_rows = 256;
-  if (a.rpp > 32) a.rpp = 32;          // rpp * 8 passes must fit the 256 row-sum threads
-  a.iters = max_rows / a.rpp / 8 * 8;  // multiple of the kernel's pipeline depth
-  if (a.iters < 8) return hipErrorInvalidValue;
-  const int rows = a.rpp * a.iters;
-  const int64_t nblk = (rows_total + rows - 1) / rows;
+  // every accepted S has a block tile (nlc_ilt_tile.h asserts it): one thread per row for the final sum, LDS under 60 KiB
+  const ilt_tile::StreamTile st = ilt_tile::stream_fwd(a.S);
+  a.rpp = st.rpp;
+  a.iters = st.iters;
+  const int64_t nblk = (rows_total + st.rows - 1) / st.rows;
   // persistent grid: 1024-4096 blocks measured the same within run-to-run noise (round 1)
   const int64_t cap = 2048;
   const unsigned grid = (unsigned)(nblk < cap ? nblk : cap);
-  const size_t shmem = (size_t)rows * SP * sizeof(double);
-  if (a.lin_wr != nullptr) {
-    // fixed Talbot / Stehfest: the same stream with per-term phase and weight from the algorithm's tables
-    if (a.lin_wi == nullptr) return hipErrorInvalidValue;
-    switch (a.iters) {
-      case 8: hipLaunchKernelGGL((ilt_fourier_kernel<8, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      case 16: hipLaunchKernelGGL((ilt_fourier_kernel<16, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      case 24: hipLaunchKernelGGL((ilt_fourier_kernel<24, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      case 32: hipLaunchKernelGGL((ilt_fourier_kernel<32, true>), dim3(grid), dim3(256), shmem, s, a); break;
-      default: hipLaunchKernelGGL((ilt_fourier_kernel<0, true>), dim3(grid), dim3(256), shmem, s, a); break;
-    }
-    return hipGetLastError();
-  }
-  switch (a.iters) {
-    case 8: hipLaunchKernelGGL((ilt_fourier_kernel<8>), dim3(grid), dim3(256), shmem, s, a); break;
-    case 16: hipLaunchKernelGGL((ilt_fourier_kernel<16>), dim3(grid), dim3(256), shmem, s, a); break;
-    case 24: hipLaunchKernelGGL((ilt_fourier_kernel<24>), dim3(grid), dim3(256), shmem, s, a); break;
-    case 32: hipLaunchKernelGGL((ilt_fourier_kernel<32>), dim3(grid), dim3(256), shmem, s, a); break;
-    default: hipLaunchKernelGGL((ilt_fourier_kernel<0>), dim3(grid), dim3(256), shmem, s, a); break;
-  }
-  return hipGetLastError();
+  // fixed Talbot / Stehfest: the same stream with per-term phase and weight from the algorithm's tables
+  return a.lin_wr != nullptr ? launch_stream<true>(a, grid, st.lds_bytes, s) : launch_stream<false>(a, grid, st.lds_bytes, s);
 }
 
 // ------------------------------------------------------------------ Fourier series, backward
@@ -730,10 +701,7 @@ __global__ __launch_bounds__(256) void ilt_fourier_bwd_kernel(const IltBwdArgs a
   const int64_t rows_total = a.N * a.d;
   const int64_t nblk = (rows_total + rows - 1) / rows;
   constexpr int UB = 8;
-  IltArgs sc{};  // the row scale only reads these
-  sc.alpha = a.alpha;
-  sc.log_tol = a.log_tol;
-  sc.scale = a.scale;
+  const IltScaleK sc{a.alpha, a.log_tol, a.scale};
   for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int64_t row0 = blk * rows;
     const int rows_here = (int)((rows_total - row0 < rows) ? (rows_total - row0) : rows);
@@ -790,14 +758,11 @@ __global__ __launch_bounds__(256) void ilt_fourier_bwd_kernel(const IltBwdArgs a
 // tangent as one rational:  F_k = w_k R c_k(theta),  R = tan(phi/2 + pi/4),  R' = (1 + R^2) / 2,
 //   c_k = cos, -sin, -cos, sin and c_k' = -sin, -cos, sin, cos for k mod 4 = 0 .. 3  (scale = 2: e^{i pi k t / T} = i^k);
 //   d x / d theta_k = G w_k R c_k'(theta_k),   d x / d phi_k = G w_k R' c_k(theta_k),   G = gx e^{gamma t} / T.
-// Odd term counts 3 .. 33 with scale = 2 and 16-byte aligned arrays; everything else keeps ilt_fourier_bwd_kernel.
+// Takes the launches of ilt_tile::rows_bwd_accepts; ilt_fourier_bwd_kernel keeps the rest.
 template <int S>
-__global__ __launch_bounds__(256, S <= 17 ? 2 : 1) void ilt_fourier_bwd_rows_kernel(const IltBwdArgs a) {
-  static_assert(S % 2 == 1, "row stride S doubles must be odd");
+__global__ __launch_bounds__(256, ilt_tile::rows_bwd_per_cu(S)) void ilt_fourier_bwd_rows_kernel(const IltBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char rows_lds[];
-  constexpr int TILE = 64 * S * 8;
-  constexpr int SLOT = (TILE + 1023) / 1024 * 1024;
-  constexpr int NLD = TILE / 1024, REM = TILE % 1024;
+  constexpr int SLOT = ilt_tile::RowTile<S>::SLOT, NLD = ilt_tile::RowTile<S>::NLD, REM = ilt_tile::RowTile<S>::REM;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   char* lt = rows_lds + wave * (2 * SLOT);
   char* lp = lt + SLOT;
@@ -809,10 +774,7 @@ __global__ __launch_bounds__(256, S <= 17 ? 2 : 1) void ilt_fourier_bwd_rows_ker
   const int64_t rows_total = a.N * a.d;
   const int64_t nfull = rows_total / 64;
   const int64_t W = (int64_t)gridDim.x * 4, w0 = (int64_t)blockIdx.x * 4 + wave;
-  IltArgs sc_args{};  // the row scale only reads these
-  sc_args.alpha = a.alpha;
-  sc_args.log_tol = a.log_tol;
-  sc_args.scale = a.scale;
+  const IltScaleK sc_args{a.alpha, a.log_tol, a.scale};
   const unsigned d = (unsigned)a.d;
   const int64_t step = 64 * W;
   const int64_t step_n = step / d;
@@ -827,10 +789,8 @@ __global__ __launch_bounds__(256, S <= 17 ? 2 : 1) void ilt_fourier_bwd_rows_ker
     for (int k = 0; k < S; ++k) {
       double th, ph;
       ld(k, &th, &ph);
-      const double x = fma(ph, 0.5, kPi / 4.0);
-      const double aa = (x - K.pio4_hi) - K.pio4_lo;
       double num, den;
-      m::tan_parts_rat(K, aa, &num, &den);
+      ilt_row_tan_parts(K, ph, &num, &den);
       const double R = num * m::rcp_refined(den);
       const double Rp = 0.5 * fma(R, R, 1.0);
       double sn, cs;
@@ -846,8 +806,8 @@ __global__ __launch_bounds__(256, S <= 17 ? 2 : 1) void ilt_fourier_bwd_rows_ker
     }
   };
   for (int64_t tile = w0; tile < nfull; tile += W) {
-    ilt_lds_load_tile<TILE>((const char*)(a.theta + tile * (64 * S)) + lane * 16, lt_addr, lane);
-    ilt_lds_load_tile<TILE>((const char*)(a.phi + tile * (64 * S)) + lane * 16, lp_addr, lane);
+    ilt_lds_load_tile<S>((const char*)(a.theta + tile * (64 * S)) + lane * 16, lt_addr, lane);
+    ilt_lds_load_tile<S>((const char*)(a.phi + tile * (64 * S)) + lane * 16, lp_addr, lane);
     double t_row, gx_row;
     asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(t_row) : "v"(a.t + n) : "memory");
     asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(gx_row) : "v"(a.gx + row) : "memory");
@@ -914,52 +874,33 @@ __global__ __launch_bounds__(256, S <= 17 ? 2 : 1) void ilt_fourier_bwd_rows_ker
     }
   }
 }
-template <int S>
-static bool launch_bwd_rows_instance(const IltBwdArgs& a, hipStream_t s, hipError_t* err) {
-  constexpr int SLOT = (64 * S * 8 + 1023) / 1024 * 1024;
-  constexpr size_t shmem = (size_t)4 * 2 * SLOT;
-  static std::atomic<unsigned long long> attr_done{0};
-  if (!lds_attr_once(ilt_fourier_bwd_rows_kernel<S>, shmem, attr_done)) return false;
-  const int64_t tiles = (a.N * a.d + 63) / 64;
-  const int per_cu = S <= 17 ? 2 : 1;
-  int64_t grid = (tiles + 3) / 4;
-  if (grid > 256 * per_cu) grid = 256 * per_cu;
-  hipLaunchKernelGGL((ilt_fourier_bwd_rows_kernel<S>), dim3((unsigned)grid), dim3(256), shmem, s, a);
-  *err = hipGetLastError();
-  return true;
-}
 static bool launch_ilt_fourier_bwd_rows(const IltBwdArgs& a, hipStream_t s, hipError_t* err) {
-  if (a.S < 3 || a.S > 33 || (a.S & 1) == 0 || a.scale != 2.0) return false;
-  if ((((uintptr_t)a.theta) | ((uintptr_t)a.phi) | ((uintptr_t)a.gtheta) | ((uintptr_t)a.gphi)) & 15) return false;
-  switch (a.S) {
-#define NLC_ROWS_CASE(SS) \
-  case SS:                \
-    return launch_bwd_rows_instance<SS>(a, s, err);
-    NLC_ROWS_CASE(3) NLC_ROWS_CASE(5) NLC_ROWS_CASE(7) NLC_ROWS_CASE(9) NLC_ROWS_CASE(11) NLC_ROWS_CASE(13) NLC_ROWS_CASE(15)
-    NLC_ROWS_CASE(17) NLC_ROWS_CASE(19) NLC_ROWS_CASE(21) NLC_ROWS_CASE(23) NLC_ROWS_CASE(25) NLC_ROWS_CASE(27) NLC_ROWS_CASE(29)
-    NLC_ROWS_CASE(31) NLC_ROWS_CASE(33)
-#undef NLC_ROWS_CASE
-  }
-  return false;
+  const uintptr_t ptr_bits = (uintptr_t)a.theta | (uintptr_t)a.phi | (uintptr_t)a.gtheta | (uintptr_t)a.gphi;
+  if (!ilt_tile::rows_bwd_accepts(a.S, a.scale, ptr_bits)) return false;
+  const int64_t tiles = (a.N * a.d + 63) / 64;
+  return dispatch_rows_terms(a.S, [&](auto term_count) {
+    constexpr int S = decltype(term_count)::value;
+    static std::atomic<unsigned long long> attr_done{0};  // per instance
+    return launch_rows(ilt_fourier_bwd_rows_kernel<S>, ilt_tile::RowTile<S>::lds_bytes(1, false), ilt_tile::rows_bwd_per_cu(S), tiles,
+                       attr_done, a, s, err);
+  });
 }
 
 hipError_t launch_ilt_fourier_bwd(const IltBwdArgs& a_in, hipStream_t s) {
   IltBwdArgs a = a_in;
   const int64_t rows_total = a.N * a.d;
   if (rows_total <= 0) return hipSuccess;
-  if (a.S > 256) return hipErrorInvalidValue;
+  if (a.S < 1 || a.S > ilt_tile::kStreamMaxTerms) return hipErrorInvalidValue;
   {
     hipError_t e2 = hipSuccess;
     if (launch_ilt_fourier_bwd_rows(a, s, &e2)) return e2;
   }
-  a.rpp = 256 / a.S;
-  if (a.rpp > 32) a.rpp = 32;
-  a.iters = 256 / a.rpp / 8 * 8;  // rows = rpp * iters <= 256: one thread per row stages the row's gradient
-  if (a.iters < 8) return hipErrorInvalidValue;
-  const int rows = a.rpp * a.iters;
-  const int64_t nblk = (rows_total + rows - 1) / rows;
+  const ilt_tile::StreamTile st = ilt_tile::stream_bwd(a.S);  // rows <= 256: one thread per row stages the row's gradient
+  a.rpp = st.rpp;
+  a.iters = st.iters;
+  const int64_t nblk = (rows_total + st.rows - 1) / st.rows;
   const unsigned grid = (unsigned)(nblk < 4096 ? nblk : 4096);
-  hipLaunchKernelGGL(ilt_fourier_bwd_kernel, dim3(grid), dim3(256), (size_t)rows * sizeof(double), s, a);
+  hipLaunchKernelGGL(ilt_fourier_bwd_kernel, dim3(grid), dim3(256), st.lds_bytes, s, a);
   return hipGetLastError();
 }
 

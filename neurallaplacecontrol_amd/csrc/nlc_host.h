@@ -342,6 +342,47 @@ int check_ilt(nlc_ctx* c, const nlc_ilt_desc* d);
 void sphere_inputs(const nlc_ilt_desc& ilt, double tn, std::vector<double>& sph);
 void linear_tables_host(int algo, int S, std::vector<double>& h);
 int linear_tables(nlc_ctx* c, const nlc_ilt_desc* d, const double** tab);
+// The ILT kernels' argument blocks, filled by name: the arrays, the shape and the contour's options, with t_div = 1,
+// t_stride = 1 and everything else zero / NULL.  A call site then sets what its algorithm adds (fre / fim, eidx, lin_wr /
+// lin_wi, t_div, t_stride, scratch); the launchers set rpp / iters.
+template <class A>
+inline A ilt_args_common(const nlc_ilt_desc& ilt, const double* theta, const double* phi, const double* t, int64_t N, int d) {
+  A a{};
+  a.theta = theta;
+  a.phi = phi;
+  a.t = t;
+  a.N = N;
+  a.d = d;
+  a.S = ilt.terms;
+  a.alpha = ilt.alpha;
+  a.log_tol = std::log(ilt.tol);
+  a.scale = ilt.scale;
+  return a;
+}
+inline IltArgs ilt_args(const nlc_ilt_desc& ilt, const double* theta, const double* phi, const double* t, double* x, int64_t N,
+                        int d) {
+  IltArgs a = ilt_args_common<IltArgs>(ilt, theta, phi, t, N, d);
+  a.x = x;
+  a.t_div = 1.0;
+  a.t_stride = 1;
+  return a;
+}
+template <class A = IltBwdArgs>
+inline A ilt_bwd_args(const nlc_ilt_desc& ilt, const double* theta, const double* phi, const double* t, const double* gx,
+                      double* gtheta, double* gphi, int64_t N, int d) {
+  A a = ilt_args_common<A>(ilt, theta, phi, t, N, d);
+  a.gx = gx;
+  a.gtheta = gtheta;
+  a.gphi = gphi;
+  return a;
+}
+inline IltDehoogBwdArgs ilt_dehoog_bwd_args(const nlc_ilt_desc& ilt, const double* theta, const double* phi, const double* t,
+                                            const double* gx, double* gtheta, double* gphi, int64_t N, int d, void* scratch) {
+  IltDehoogBwdArgs a = ilt_bwd_args<IltDehoogBwdArgs>(ilt, theta, phi, t, gx, gtheta, gphi, N, d);
+  a.t_div = 1.0;
+  a.scratch = scratch;
+  return a;
+}
 
 // ---- abi_baselines.hip
 int node_substeps(double t_end, double step, double* h, int max_n);

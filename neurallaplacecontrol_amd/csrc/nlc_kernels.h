@@ -7,10 +7,9 @@
 #include <type_traits>
 
 #include "../../include/nlc.h"
+#include "nlc_ilt_tile.h"  // kMaxTerms
 
 namespace nlc {
-
-constexpr int kMaxTerms = 129;  // ILT terms the coefficient tables hold
 
 // ------------------------------------------------------------------ ILT (standalone, a9)
 struct IltArgs {
@@ -66,19 +65,8 @@ struct RepInArgs {
 };
 hipError_t launch_rep_inputs(const RepInArgs& a, hipStream_t s);
 
-// fixed Talbot / Stehfest: x[n,c] = (1/t_n) sum_k (wr_k Re F_k - wi_k Im F_k), query points s_k = (node_k) / t
-struct IltLinArgs {
-  const double* theta;  // (N, d, S)
-  const double* phi;
-  const double* t;      // (N)
-  double* x;            // (N, d)
-  int64_t N;
-  int d, S;
-  const double* wr;     // (S) device tables
-  const double* wi;
-};
-hipError_t launch_ilt_linear(const IltLinArgs& a, hipStream_t s);
-// the same sum over F_k = (re, im) held SLOT-major (8*nt3, N) (staged planner path; see IltArgs::eidx)
+// fixed Talbot / Stehfest: x[n,c] = (1/t_n) sum_k (wr_k Re F_k - wi_k Im F_k), query points s_k = (node_k) / t,
+// over F_k = (re, im) held SLOT-major (8*nt3, N) (staged planner path; see IltArgs::eidx)
 struct IltLinSlotArgs {
   const double* fre;  // (8*nt3, N)
   const double* fim;

@@ -429,3 +429,43 @@ def test_ilt_fourier_unaligned_and_even_inputs_keep_the_stream_kernel(nlc):
     np.testing.assert_allclose(got_u.numpy() / scale, ref.numpy() / scale, rtol=1e-9, atol=1e-11)
     np.testing.assert_allclose(got_a.numpy() / scale, ref.numpy() / scale, rtol=1e-9, atol=1e-11)
     np.testing.assert_allclose(got_a.numpy(), got_u.numpy(), rtol=1e-12, atol=1e-13 * float(scale))
+
+
+_STREAM_LOOP_OPTS = (None, dict(scale=3.0, alpha=1e-2))
+
+
+@pytest.fixture(scope="module", params=[86, 129])
+def stream_loop_case(request):
+    """Term counts past the row kernels' 33 whose passes per block tile (40 at S = 86: 80 rows; 56 at S = 129, the table
+    limit: 56 rows) have no unrolled instance: ilt_fourier_kernel's runtime pass loop (ITERS == 0) and ilt_fourier_bwd_kernel,
+    on N d = 201 rows -- several whole tiles and a ragged one.  The oracle's values and gradients, computed once."""
+    from oracle import ilt as oilt
+
+    S, d, N = request.param, 3, 67
+    g = torch.Generator().manual_seed(1000 + S)
+    theta = ((torch.rand(N, d, S, dtype=torch.float64, generator=g) * 2 - 1) * np.pi).requires_grad_()
+    phi = ((torch.rand(N, d, S, dtype=torch.float64, generator=g) * 2 - 1) * np.pi / 2 * 0.99).requires_grad_()
+    t = torch.rand(N, dtype=torch.float64, generator=g) * 2 + 0.05
+    gx = torch.randn(N, d, dtype=torch.float64, generator=g)
+    refs = [oilt.ilt_from_sphere(theta, phi, t, "fourier", opts) for opts in _STREAM_LOOP_OPTS]
+    ref_gt, ref_gp = torch.autograd.grad(refs[0], (theta, phi), gx)
+    return dict(theta=theta.detach(), phi=phi.detach(), t=t, gx=gx, refs=[r.detach() for r in refs], ref_gt=ref_gt, ref_gp=ref_gp)
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["default", "scale3_alpha1e-2"])
+def test_ilt_fourier_stream_runtime_loop_vs_oracle(nlc, stream_loop_case, which):
+    c = stream_loop_case
+    ref = c["refs"][which]
+    got = nlc.ilt_reconstruct(c["theta"].cuda(), c["phi"].cuda(), c["t"].cuda(), "fourier", _STREAM_LOOP_OPTS[which]).cpu()
+    scale = ref.abs().max()
+    np.testing.assert_allclose(got.numpy() / scale, ref.numpy() / scale, rtol=1e-9, atol=1e-11)
+
+
+def test_ilt_fourier_stream_runtime_loop_backward_vs_autograd_of_oracle(nlc, stream_loop_case):
+    c = stream_loop_case
+    th, ph = c["theta"].cuda().requires_grad_(), c["phi"].cuda().requires_grad_()
+    got = nlc.ilt_reconstruct(th, ph, c["t"].cuda(), "fourier", None)
+    got_gt, got_gp = torch.autograd.grad(got, (th, ph), c["gx"].cuda())
+    for got_g, ref_g in ((got_gt, c["ref_gt"]), (got_gp, c["ref_gp"])):
+        sc = float(ref_g.abs().max())
+        np.testing.assert_allclose(got_g.cpu().numpy() / sc, ref_g.numpy() / sc, rtol=1e-9, atol=1e-11)

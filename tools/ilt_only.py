@@ -24,7 +24,7 @@ for _ in range(20):
 torch.cuda.synchronize()
 ctx.profile(False)
 prof = ctx.profile_read()
-p = prof["ilt_fourier_kernel"] if algo == "fourier" else (prof.get("ilt_linear_kernel") or prof["ilt_linear_stream_kernel"])
+p = prof["ilt_fourier_kernel"] if algo == "fourier" else prof["ilt_linear_stream_kernel"]
 ms = p["total_ms"] / p["launches"]
 nbytes = N * (2 * d * S + d) * 8
 print(algo, "avg ms", ms)
