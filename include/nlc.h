@@ -104,6 +104,18 @@ int nlc_synchronize(nlc_ctx* ctx);
  *   "gru_coop"           stand-alone GRU encodes (nlc_gru_encode, nlc_model_forward, the two-launch planner bodies) with the
  *                        cooperative kernel -- one 16-window tile per workgroup, one gate chunk per wavefront, a third of
  *                        the latency -- 1 / 0; -1 = auto (default): up to 50 000 windows at hidden_units 128, 8 192 at 64, always at 256
+ *   "gru_prefix"         two-launch planner bodies, wave-per-tile FP64 encoder, one action dimension without a time channel
+ *                        (nu == nin == 1) and action bounds: MPPI stores a clipped action as exactly u_max / u_scale or
+ *                        u_min / u_scale, and the encoder consumes a window newest action first from h = 0, so while the consumed
+ *                        actions are clipped the hidden states are constants of (weights, bounds, u_scale, normalisation,
+ *                        pattern).  nlc_mppi_configure builds a table of the 2 + 4 + 8 + 16 states after one to four such steps
+ *                        (30 KB in the model's arena; rebuilt by every configure, which a new model forces); per command an index
+ *                        pass behind perturb_kernel sorts the windows by the length of their clipped prefix (0 .. min(B, 4)) and
+ *                        the encoder launch runs only the remaining steps of each -- same step code, bit-identical latents
+ *                        (csrc/nlc_gru_prefix.h).  -1 (default): whenever the launch is in scope, silently not otherwise;
+ *                        0: never (the plain launch); 1: required -- NLC_ERR_UNSUPPORTED from nlc_mppi_rollout when the command
+ *                        runs another body (fused, staged), the cooperative or int8-sliced encoder, horizon chunks, nu or nin
+ *                        other than 1, no bounds, B > 32, more than 2^27 windows, or a bound whose normalised image is not finite
  *   "gru_gemm"           EXPERIMENTAL.  0 (default): the GRU encoder's hidden-state GEMMs on FP64 MFMAs.  1: the same GEMMs as
  *                        int8-sliced fixed-point products on the INT8 matrix pipe (csrc/kernels_gru_i8.hip, nlc_i8gemm.h; models with
  *                        hidden_units = 128, the stand-alone encode launches that take the wave-sized form -- more than 50 000
@@ -194,6 +206,10 @@ int nlc_set_option(nlc_ctx* ctx, const char* name, double value);
  *   "comm_world", "comm_rank"  size / rank of the library-owned RCCL communicator (0 / -1 = none: nlc_comm_init not called)
  *   "fused_blocks_per_cu"  resident workgroups per CU the occupancy query returned for the fused kernel (-1 = not queried yet)
  *   "fused_spin_limit"     the option's current value
+ *   "gru_prefix"           1 when the LAST command's encoder launch started from the prefix-state table (option "gru_prefix")
+ *   "gru_prefix_windows_l0" .. "_l4"  that command's windows by the number of leading GRU steps taken from the table (0 when
+ *                          the table was not used); they sum to E K T.  Reading one waits for the command's launches
+ *   "latents_offset"       offset, in doubles, of the (E K, T, 2) GRU latents inside nlc_mppi_buffers.workspace (-1: no NL planner)
  *   "gru_gemm"             1 when encode launches run the int8-sliced kernel (option "gru_gemm" = 1 and a hidden_units = 128 model)
  *   "gru_i8_launches"      launches of the int8-sliced encoder kernel in this PROCESS so far (any ctx): the option alone does not say
  *                          that a launch took it -- cooperative and fused launches keep their FP64 encoder

@@ -123,6 +123,7 @@ extern "C" void nlc_destroy(nlc_ctx* c) {
   prof_flush(c);
   if (c->arena.base) hipFree(c->arena.base);
   if (c->dbg_scratch) hipFree(c->dbg_scratch);
+  if (c->prefix.lists) hipFree(c->prefix.lists);
   if (c->rnn_base) hipFree(c->rnn_base);
   if (c->node_base) hipFree(c->node_base);
   if (c->slot_dev) hipFree(c->slot_dev);
@@ -220,6 +221,9 @@ extern "C" int nlc_set_option(nlc_ctx* c, const char* name, double value) {
   } else if (n == "gru_coop") {
     if (value != 0 && value != 1 && value != -1) return fail(c, NLC_ERR_BAD_ARG, "gru_coop must be -1 (auto), 0 or 1");
     c->opt.gru_coop = (int)value;
+  } else if (n == "gru_prefix") {
+    if (value != 0 && value != 1 && value != -1) return fail(c, NLC_ERR_BAD_ARG, "gru_prefix must be -1 (auto), 0 or 1");
+    c->opt.gru_prefix = (int)value;
   } else if (n == "gru_gemm") {
     // 0: FP64 MFMAs (default); 1: the encoder's hidden-state GEMMs as int8-sliced fixed-point products (kernels_gru_i8.hip;
     // hidden_units = 128: the stand-alone encoder launches that take the wave-sized form; the one-launch planner body keeps its FP64
@@ -258,6 +262,17 @@ extern "C" int nlc_get_stat(nlc_ctx* c, const char* name, double* out) {
   else if (n == "fused_spin_limit") *out = (double)c->opt.fused_spin_limit;
   else if (n == "model_nt3") *out = c->has_model ? (double)c->net.nt3 : 0.0;
   else if (n == "gru_gemm") *out = (c->has_model && c->gru.use_i8) ? 1.0 : 0.0;  // 1: the encoder launches run kernels_gru_i8.hip
+  else if (n == "gru_prefix") *out = c->prefix.last_used ? 1.0 : 0.0;
+  else if (n.rfind("gru_prefix_windows_l", 0) == 0 && n.size() == 21 && n[20] >= '0' && n[20] <= '4') {
+    // the last command's windows by prefix length; waits for the command's launches
+    *out = 0.0;
+    if (c->prefix.last_used && c->prefix.lists) {
+      unsigned cnt[nlc::prefix::kLists] = {0};
+      NLC_HIP(c, hipStreamSynchronize(c->stream));
+      NLC_HIP(c, hipMemcpy(cnt, c->prefix.lists, sizeof(cnt), hipMemcpyDeviceToHost));
+      *out = (double)cnt[n[20] - '0'];
+    }
+  } else if (n == "latents_offset") *out = (c->has_mppi && c->pd.dynamics == NLC_DYN_NL) ? (double)ws_layout(c).pa : -1.0;
   else if (n == "gru_i8_launches") *out = (double)nlc::gru_i8_launch_count();  // process-wide
   else return fail(c, NLC_ERR_BAD_ARG, "unknown stat: " + n);
   return NLC_OK;

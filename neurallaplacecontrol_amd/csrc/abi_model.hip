@@ -103,6 +103,7 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   const size_t o_W3 = ar.push(pack_A(W3, h, h, slots.rowmap3));
   const size_t o_b3 = ar.push(b3p);
   const size_t o_Cp = ar.push(slots.Cp);
+  const size_t o_prefix = ar.push(std::vector<double>(gru_prefix_arena_doubles(g), 0.0));  // filled by nlc_mppi_configure
 
   // ---- upload
   double* base = nullptr;
@@ -183,6 +184,8 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   N.log_tol = std::log(d->ilt.tol);
   N.scale = d->ilt.scale;
   N.time_div = d->time_div;
+  c->prefix.arena_off = o_prefix;
+  c->prefix.why_not = "gru_prefix: planner not configured";
   c->has_model = true;
   c->fwd_tn = -1.0;  // the constant-time forward's folded bias belongs to the previous weights
   c->has_mppi = false;  // a planner configured against the previous weights must be re-configured

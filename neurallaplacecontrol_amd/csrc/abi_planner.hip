@@ -114,6 +114,9 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
       if (int rc = hold_doubles(c, c->cp_lin, cp.size(), cp.data())) return rc;
     }
   }
+  c->prefix.last_used = false;
+  if (d->dynamics == NLC_DYN_NL)
+    if (int rc = gru_prefix_configure(c)) return rc;
   c->has_mppi = true;
   c->dh.reset();
   c->wait.reset();

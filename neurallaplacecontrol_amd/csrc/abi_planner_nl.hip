@@ -398,10 +398,49 @@ int rollout_nl_fused(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r, 
   return NLC_OK;
 }
 
+// "gru_prefix" for the encoder launch of the two-launch body over N windows: *use, or (option 1) the reason it cannot be.  On
+// *use the perturb kernel is told to zero the list counters, as it zeroes the fused body's sync block.
+int gru_prefix_begin(nlc_ctx* c, RolloutCall& call, const GruArgs& g, int64_t N, int chunks, bool* use, GruPrefixArgs* px) {
+  *use = false;
+  if (c->opt.gru_prefix == 0) return NLC_OK;
+  GruPrefixState& ps = c->prefix;
+  const char* why = ps.why_not;
+  if (!why && ps.last_B != g.B) why = "gru_prefix: the table was built for another action-buffer length";
+  if (!why && chunks != 1) why = "gru_prefix: not with the encoder in horizon chunks (horizon_chunks)";
+  if (!why && gru_use_coop(c, N)) why = "gru_prefix: this launch takes the cooperative encoder (gru_coop)";
+  if (!why && g.use_i8) why = "gru_prefix: the FP64 encoder only (gru_gemm is 1)";
+  if (!why) why = prefix::out_of_scope(g.nact, g.nin, 1, g.B, N, true);
+  if (why) return c->opt.gru_prefix == 1 ? fail(c, NLC_ERR_UNSUPPORTED, why) : NLC_OK;
+  const int64_t stride = (N + 63) / 64 * 64;
+  const size_t need = 64 + (size_t)prefix::kLists * (size_t)stride / 2;  // doubles: a row of counters, then 32-bit lists
+  if (need > ps.lists_n) {
+    NLC_HIP(c, hipStreamSynchronize(c->stream));  // (an earlier command may still read the buffer this replaces)
+    if (int rc = hold_doubles(c, ps.lists, need, nullptr, &ps.lists_n)) return rc;
+  }
+  double* base = c->arena.base + ps.arena_off;
+  px->table = base;
+  px->out_tab = base + (size_t)prefix::kEntries * 2 * c->g;
+  px->counts = reinterpret_cast<unsigned*>(ps.lists);
+  px->lists = reinterpret_cast<unsigned*>(ps.lists + 64);
+  px->list_stride = stride;
+  px->img_max = ps.img_max;
+  px->img_min = ps.img_min;
+  call.p.zero_words = px->counts;
+  call.p.n_zero_words = 16;
+  *use = true;
+  return NLC_OK;
+}
+
 // GRU launch + rollout launch (wave-per-tile or latency-split body), optionally in horizon chunks on two streams
 int rollout_nl_two_launch(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r, int variant) {
   const nlc_mppi_desc& d = c->pd;
   const int64_t KE = call.KE;
+  bool use_prefix = false;
+  GruPrefixArgs px{};
+  {
+    const int chunks = plan::horizon_chunks((variant != 2 && KE > 8192 && d.E == 1) ? c->opt.horizon_chunks : 1, d.T).C;
+    if (int rc = gru_prefix_begin(c, call, g, KE * d.T, chunks, &use_prefix, &px)) return rc;
+  }
   if (int rc2 = nlc::host::launch_shift_perturb(c, call)) return rc2;
   // Horizon chunks (round 3, option "horizon_chunks"): the encoder input does not depend on the state, so the GRU
   // encode of horizon steps [c Tc, (c + 1) Tc) can run on a stream of its own while the rollout walks the chunk before
@@ -415,7 +454,15 @@ int rollout_nl_two_launch(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs
     g.t0 = 0;
     g.Tc = d.T;
     g.N = KE * d.T;
-    {
+    if (use_prefix) {
+      {
+        ProfScope ps(c, "gru_prefix_index_kernel");
+        NLC_HIP(c, launch_gru_prefix_index(g, px, c->stream));
+      }
+      ProfScope ps(c, "gru_encode_kernel");
+      NLC_HIP(c, launch_gru_encode_prefix(g, px, c->g, c->stream));
+      c->prefix.last_used = true;
+    } else {
       ProfScope ps(c, "gru_encode_kernel");
       NLC_HIP(c, launch_gru_encode(g, c->g, c->stream, gru_use_coop(c, g.N)));
     }
@@ -440,6 +487,47 @@ int rollout_nl_two_launch(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs
 }
 
 }  // namespace
+
+// The prefix-state table (nlc_gru_prefix.h) of the planner nlc_mppi_configure has just described in c->pd: one wavefront runs
+// the 16 patterns of four clipped actions through the encoder's own step body.  The tile is fed the bound images exactly as a
+// clipped action reaches the encoder: perturbed holds u_max / u_scale, the encoder multiplies by u_scale and normalises.
+int nlc::host::gru_prefix_configure(nlc_ctx* c) {
+  const nlc_mppi_desc& d = c->pd;
+  GruPrefixState& ps = c->prefix;
+  ps.last_B = d.B;
+  ps.last_used = false;
+  const double img[2] = {prefix::bound_image(d.u_max[0], d.u_scale), prefix::bound_image(d.u_min[0], d.u_scale)};
+  bool finite = true;
+  for (double v : img) finite = finite && std::isfinite((d.u_scale * v - c->gru.mean[0]) / c->gru.std[0]);
+  ps.why_not = prefix::out_of_scope(d.nu, c->md.nin, d.has_bounds, d.B, 0, finite);
+  if (ps.why_not) return NLC_OK;
+  ps.img_max = prefix::bits_of(img[0]);
+  ps.img_min = prefix::bits_of(img[1]);
+  std::vector<double> syn((size_t)16 * d.B, 0.0);  // column c, GRU step s (window element B - 1 - s): bit s of c picks u_min
+  for (int col = 0; col < 16; ++col)
+    for (int s = 0; s < prefix::cap(d.B); ++s) syn[(size_t)col * d.B + (d.B - 1 - s)] = img[(col >> s) & 1];
+  double* base = c->arena.base + ps.arena_off;
+  GruPrefixArgs px{};
+  px.table = base;
+  px.out_tab = base + (size_t)prefix::kEntries * 2 * c->g;
+  double* syn_dev = px.out_tab + 64;
+  NLC_HIP(c, hipMemcpy(syn_dev, syn.data(), syn.size() * sizeof(double), hipMemcpyHostToDevice));
+  GruArgs a = c->gru;
+  a.mode = 1;
+  a.perturbed = syn_dev;
+  a.abuf = syn_dev;  // (never read: every element of window (k, B - 1) is a perturbed one)
+  a.u_scale = d.u_scale;
+  a.T = a.Tc = d.B;
+  a.t0 = 0;
+  a.Kep = 16;
+  a.N = 16;
+  a.B = d.B;
+  a.nact = 1;
+  a.out = nullptr;
+  NLC_HIP(c, launch_gru_prefix_table(a, px, c->g, c->stream));
+  NLC_HIP(c, hipStreamSynchronize(c->stream));
+  return NLC_OK;
+}
 
 int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
   const nlc_mppi_desc& d = c->pd;
@@ -478,7 +566,12 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
     r.net.Cp2 = c->cp_lin + ng;
     r.net.lin = 1;
   }
-  if (c->md.ilt.algo != NLC_ILT_FOURIER && !lin_direct) return rollout_nl_staged(c, call, sc, g, r, pa);
+  c->prefix.last_used = false;
+  const char* prefix_two_launch_only = "gru_prefix: the encoder launch of the two-launch body only (rollout_variant 1 / 2)";
+  if (c->md.ilt.algo != NLC_ILT_FOURIER && !lin_direct) {
+    if (c->opt.gru_prefix == 1) return fail(c, NLC_ERR_UNSUPPORTED, prefix_two_launch_only);
+    return rollout_nl_staged(c, call, sc, g, r, pa);
+  }
   // rollout_variant (nlc_set_option): 0 auto, 1 wave-per-tile, 2 latency-split, 3 fused one-launch body
   int variant = c->opt.rollout_variant;
   const int h_ = c->md.h;
@@ -510,6 +603,7 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
   const bool in_body = variant == 3 || variant == 2 || (variant == 0 && KE <= 8192);
   if (in_body) cost_in_body(r, d);
   if (variant == 3) {
+    if (c->opt.gru_prefix == 1) return fail(c, NLC_ERR_UNSUPPORTED, prefix_two_launch_only);
     bool weights_done = false;
     if (int rc2 = rollout_nl_fused(c, call, g, r, &weights_done)) return rc2;
     if (weights_done) return NLC_OK;

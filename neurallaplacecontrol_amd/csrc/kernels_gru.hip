@@ -12,6 +12,7 @@
 // Roofline: FP64 MFMA bound.  Per 16 windows (B = 4): B*MT (input) + (B-1)*KS*MT (l0 hh) + B*KS*MT (l1 ih)
 // + (B-1)*KS*MT (l1 hh) + KS (head) = 1984 MFMAs of 2048 flop; HBM traffic is nu*8 B in + 16 B out per window.
 #include "nlc_device.h"
+#include "nlc_gru_prefix.h"
 #include "nlc_gru_tile.h"
 #include "nlc_kernels.h"
 
@@ -102,6 +103,164 @@ hipError_t launch_gru_encode(const GruArgs& a, int g, hipStream_t s, bool coop, 
     hipLaunchKernelGGL((gru_encode_kernel<32>), dim3(grid), dim3(256), 0, s, a);
   } else if (g == 128) {
     hipLaunchKernelGGL((gru_encode_kernel<128>), dim3(grid), dim3(256), 0, s, a);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ saturated leading steps from a table ("gru_prefix")
+// See nlc_gru_prefix.h.  All three kernels run gru_encode_tile's own step body, so a window's latents are the bits the full
+// loop gives: a column of an MFMA tile does not depend on its neighbours, and only whole steps are skipped.
+
+// Table build, one wavefront: the 16 sign patterns of four clipped actions are one tile.  It runs steps 0 .. min(B, 4) - 1 and
+// stores the state after step s under the first s + 1 pattern bits; with B <= 4 also linear_out of the 2^B whole windows.
+template <int G>
+__global__ __launch_bounds__(64) void gru_prefix_table_kernel(const GruArgs a, const GruPrefixArgs px) {
+  constexpr int KS = G / 4;
+  const int lane = threadIdx.x & 63;
+  const int q = lane >> 4, c = lane & 15;
+  __shared__ double Hs[2][KS * 64];
+  // entry 0: h = 0, the start of a window without a prefix
+  for (int i = lane; i < 2 * G; i += 64) px.table[i] = 0.0;
+  const int steps = prefix::cap(a.B);
+  // window (k = c, t = B - 1) of the synthetic history: every element is a perturbed one
+  const double o = gru_encode_tile<G, true>(a, lane, c, c, a.B - 1, Hs[0], Hs[1], 0, steps, px.table);
+  if (steps == a.B && q < 2 && c < (1 << steps)) px.out_tab[prefix::entry_index(steps, c) * 2 + q] = o;
+}
+
+// Index pass: a workgroup classifies 2048 windows (eight per thread), appends them to the list of their prefix length, or --
+// the whole window is clipped -- stores the table's latents.  List positions come from ONE global atomic per workgroup and
+// list (every wavefront adding to the same five words costs 0.5 ms at 655 360 windows: the atomics queue up at one L2
+// channel): the workgroup counts in LDS first, reserves its range, then hands out positions from LDS counters, both
+// wave-aggregated.  Every thread walks every iteration, so the ballots see whole wavefronts.
+constexpr int kIndexPerThread = 8;
+__global__ __launch_bounds__(256) void gru_prefix_index_kernel(const GruArgs a, const GruPrefixArgs px) {
+  __shared__ unsigned cnt[8], base[8];
+  const int lane = threadIdx.x & 63;
+  const int nl = prefix::n_lists(a.B);
+  if (threadIdx.x < 8) cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  const int64_t w0 = (int64_t)blockIdx.x * (256 * kIndexPerThread) + threadIdx.x;
+  unsigned cls[kIndexPerThread];  // len (7: no window) | pattern << 3
+#pragma unroll
+  for (int it = 0; it < kIndexPerThread; ++it) {
+    const int64_t w = w0 + it * 256;
+    int len = 7, pattern = 0;
+    if (w < a.N) {
+      const int64_t kk = w / a.Tc;
+      const int tt = a.t0 + (int)(w - kk * a.Tc);
+      const prefix::Class c = prefix::classify(a.perturbed + kk * a.T, tt, a.B, px.img_max, px.img_min);
+      len = c.len;
+      pattern = c.pattern;
+      if (len == a.B) {
+        const double* o = px.out_tab + prefix::entry_index(len, pattern) * 2;
+        a.out[(kk * a.T + tt) * 2 + 0] = o[0];
+        a.out[(kk * a.T + tt) * 2 + 1] = o[1];
+      }
+    }
+    cls[it] = (unsigned)len | ((unsigned)pattern << 3);
+    for (int l = 0; l <= prefix::kMaxLen; ++l) {
+      const unsigned long long m = __ballot(len == l);
+      if (m != 0ull && lane == __ffsll((long long)m) - 1) atomicAdd(&cnt[l], (unsigned)__popcll(m));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x <= prefix::kMaxLen) {
+    const unsigned n = cnt[threadIdx.x];
+    base[threadIdx.x] = n ? atomicAdd(px.counts + threadIdx.x, n) : 0u;
+    cnt[threadIdx.x] = 0u;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < kIndexPerThread; ++it) {
+    const int64_t w = w0 + it * 256;
+    const int len = (int)(cls[it] & 7u);
+    for (int l = 0; l < nl; ++l) {
+      const unsigned long long m = __ballot(len == l);
+      if (m == 0ull) continue;
+      const int leader = __ffsll((long long)m) - 1;
+      unsigned b = 0u;
+      if (lane == leader) b = atomicAdd(&cnt[l], (unsigned)__popcll(m));
+      b = (unsigned)__shfl((int)b, leader);
+      if (len == l) {
+        const unsigned pos = base[l] + b + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        if ((int64_t)pos < px.list_stride) px.lists[(int64_t)l * px.list_stride + pos] = (unsigned)w | ((cls[it] >> 3) << prefix::kPatternShift);
+      }
+    }
+  }
+}
+
+// List launch: a wavefront takes 16 entries of ONE list (tiles in list order, length 0 first: the longest tiles start first
+// and the shortest fill the tail), gathers each column's images from the table, runs steps len .. B - 1 and the head.  The
+// grid is sized for the worst case without reading a count back; wavefronts beyond the lists' tiles exit at once.  Padded
+// columns repeat the list's last entry and do not store.
+template <int G>
+__global__ __launch_bounds__(256, G <= 64 ? 2 : 1) void gru_encode_prefix_kernel(const GruArgs a, const GruPrefixArgs px) {
+  constexpr int KS = G / 4;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int q = lane >> 4, c = lane & 15;
+  const int nl = prefix::n_lists(a.B);
+  int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+  int len = 0;
+  unsigned n = 0u;
+  for (; len < nl; ++len) {
+    n = px.counts[len];
+    if ((int64_t)n > px.list_stride) n = (unsigned)px.list_stride;
+    const int64_t nt = ((int64_t)n + 15) / 16;
+    if (tile < nt) break;
+    tile -= nt;
+  }
+  if (len == nl) return;  // (no barrier in this kernel)
+  const int64_t idx = tile * 16 + c;
+  const bool valid = idx < (int64_t)n;
+  const unsigned e = px.lists[(int64_t)len * px.list_stride + (valid ? idx : (int64_t)n - 1)];
+  int64_t w = (int64_t)(e & ((1u << prefix::kPatternShift) - 1u));
+  if (w >= a.N) w = a.N - 1;  // (every entry the index pass wrote is a window of this launch)
+  const int64_t kk = w / a.Tc;
+  const int tt = a.t0 + (int)(w - kk * a.Tc);
+  __shared__ double Hs[4][2][KS * 64];
+  if (len > 0) {  // (length 0: the tile body zeroes its images itself)
+    const int pattern = (int)(e >> prefix::kPatternShift) & ((1 << len) - 1);
+    const double* ent = px.table + (size_t)prefix::entry_index(len, pattern) * 2 * G;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      Hs[wave][0][ks * 64 + lane] = ent[4 * ks + q];
+      Hs[wave][1][ks * 64 + lane] = ent[G + 4 * ks + q];
+    }
+  }
+  const double o = gru_encode_tile<G, true>(a, lane, w, kk, tt, Hs[wave][0], Hs[wave][1], len);
+  if (valid && q < 2) a.out[(kk * a.T + tt) * 2 + q] = o;
+}
+
+hipError_t launch_gru_prefix_table(const GruArgs& a, const GruPrefixArgs& px, int g, hipStream_t s) {
+  if (g == 64) {
+    hipLaunchKernelGGL(gru_prefix_table_kernel<64>, dim3(1), dim3(64), 0, s, a, px);
+  } else if (g == 32) {
+    hipLaunchKernelGGL(gru_prefix_table_kernel<32>, dim3(1), dim3(64), 0, s, a, px);
+  } else if (g == 128) {
+    hipLaunchKernelGGL(gru_prefix_table_kernel<128>, dim3(1), dim3(64), 0, s, a, px);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+hipError_t launch_gru_prefix_index(const GruArgs& a, const GruPrefixArgs& px, hipStream_t s) {
+  if (a.N <= 0) return hipSuccess;
+  const int64_t per_block = 256 * kIndexPerThread;
+  hipLaunchKernelGGL(gru_prefix_index_kernel, dim3((unsigned)((a.N + per_block - 1) / per_block)), dim3(256), 0, s, a, px);
+  return hipGetLastError();
+}
+hipError_t launch_gru_encode_prefix(const GruArgs& a, const GruPrefixArgs& px, int g, hipStream_t s) {
+  if (a.N <= 0) return hipSuccess;
+  const unsigned grid = (unsigned)((prefix::worst_case_tiles(a.N, a.B) + 3) / 4);
+  if (g == 64) {
+    hipLaunchKernelGGL(gru_encode_prefix_kernel<64>, dim3(grid), dim3(256), 0, s, a, px);
+  } else if (g == 32) {
+    hipLaunchKernelGGL(gru_encode_prefix_kernel<32>, dim3(grid), dim3(256), 0, s, a, px);
+  } else if (g == 128) {
+    hipLaunchKernelGGL(gru_encode_prefix_kernel<128>, dim3(grid), dim3(256), 0, s, a, px);
   } else {
     return hipErrorInvalidValue;
   }

@@ -138,9 +138,15 @@ __device__ __forceinline__ v4d gru_gates(const v4d& ar, const v4d& az, const v4d
 // One wavefront encodes the 16 windows its lanes' columns name.  Mode 0: window row `wc` of the explicit (N, B, nin)
 // tensor; mode 1: window (kk, tt) of the MPPI history.  H0 / H1: this wave's hidden-state images in LDS (KS*64 doubles
 // each, every entry written and read by the same lane: no barrier).  Returns linear_out row q (valid for q < 2).
-template <int G>
+// The step loop runs steps [s0, s_end) (s_end < 0: a.B).  With s0 > 0 the caller has filled H0 / H1 with the images after
+// step s0 - 1 (the "gru_prefix" list launch: nlc_gru_prefix.h); a non-finite input of a step that does not run is not seen.
+// `dump` (the table build): after step s, column c < 2^(s+1) stores both images as table entry 2^(s+1) - 1 + c,
+// dump[(entry * 2 + layer) * G + 4 ks + q] = H[ks * 64 + lane].
+// (kPrefix = false: s0, s_end and dump are not looked at -- the instances every other launch runs are the code they were)
+template <int G, bool kPrefix = false>
 __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, int64_t wc, int64_t kk, int tt,
-                                                  double* __restrict__ H0, double* __restrict__ H1) {
+                                                  double* __restrict__ H0, double* __restrict__ H1, int s0 = 0,
+                                                  int s_end = -1, double* __restrict__ dump = nullptr) {
   constexpr int GT = G / 16;   // tiles per gate = chunks
   constexpr int KS = G / 4;    // k-steps over the hidden dimension
   const int q = lane >> 4;
@@ -151,17 +157,19 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
     in_std = a.std[q];
   }
   const int ab_off = (a.mode == 1) ? (int)(kk / a.Kep) * a.B : 0;  // this sample's episode block of action_buffer
+  if (!kPrefix || s0 == 0) {
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    H0[ks * 64 + lane] = 0.0;
-    H1[ks * 64 + lane] = 0.0;
+    for (int ks = 0; ks < KS; ++ks) {
+      H0[ks * 64 + lane] = 0.0;
+      H1[ks * 64 + lane] = 0.0;
+    }
   }
   v4d hn[GT];
   // A non-finite window entry must leave as NaN latents, as nn.GRU's arithmetic gives it (the reference, w_nl.py:14-29): the
   // gate math here clamps with v_min / v_max, which swallow a NaN -- so the window is remembered and its outputs are replaced
   bool bad_input = false;
 
-  for (int s = 0; s < a.B; ++s) {
+  for (int s = kPrefix ? s0 : 0; s < ((kPrefix && s_end >= 0) ? s_end : a.B); ++s) {
     // reversed time: GRU step s consumes window element B-1-s  (torch.flip, w_nl.py:27)
     const int j_win = a.B - 1 - s;
     double xin = 0.0;
@@ -216,6 +224,14 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
     for (int j = 0; j < GT; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) H1[(4 * j + r) * 64 + lane] = hn[j][r];
+    if (kPrefix && dump != nullptr && (lane & 15) < (2 << s)) {
+      double* e = dump + (size_t)((2 << s) - 1 + (lane & 15)) * 2 * G;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        e[4 * ks + q] = H0[ks * 64 + lane];
+        e[G + 4 * ks + q] = H1[ks * 64 + lane];
+      }
+    }
   }
   // ---------------- linear_out (2 x g): rows 0,1 of one output tile
   v4d o[1];

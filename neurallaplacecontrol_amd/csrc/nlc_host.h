@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "nlc_gru_prefix.h"
 #include "nlc_kernels.h"
 #include "nlc_pack.h"
 #include "nlc_plan.h"
@@ -58,6 +59,7 @@ struct PlannerOptions {
   int rollout_variant = 0;          // 0 auto, 1 wave-per-tile, 2 latency-split (two launches), 3 fused one-launch body
   int repfunc_split = 1;            // staged de Hoog planner: latency-split representation kernel (h = 128)
   int gru_coop = -1;                // stand-alone GRU encodes: cooperative (one tile per workgroup) kernel 1 / 0, -1 auto
+  int gru_prefix = -1;              // two-launch body, wave-per-tile encoder: clipped leading GRU steps from a table (nlc_gru_prefix.h): -1 auto, 0 / 1
   int gru_gemm = 0;                 // 1: encoder hidden-state GEMMs on the INT8 matrix pipe (kernels_gru_i8.hip), g == 64 only
   int horizon_chunks = 1;           // Fourier planner, wave-per-tile body (K > 8192): GRU encode of later horizon chunks beside the rollout of earlier ones
   int dehoog_gru_chunks = 0;        // staged de Hoog planner: GRU encode in this many horizon chunks beside the step chain (0 / 1: one launch up front)
@@ -135,6 +137,19 @@ struct DehoogCalib {
       e = nullptr;
     }
   }
+};
+
+// "gru_prefix" (nlc_gru_prefix.h): the table sits in the model's arena (c->arena, reserved by nlc_set_model) and is built by
+// nlc_mppi_configure -- a new model, other bounds / u_scale / normalisation or another B all pass through there; the window
+// lists and their counters are the ctx's own buffer, grown at the first command that needs it
+struct GruPrefixState {
+  size_t arena_off = 0;          // table, out_tab and the table build's 16 synthetic windows, in doubles from the arena's base
+  const char* why_not = "gru_prefix: planner not configured";  // out of scope (nullptr: the table is built)
+  unsigned long long img_max = 0, img_min = 0;
+  double* lists = nullptr;       // counters (one 64-double row) + kLists lists
+  size_t lists_n = 0;
+  bool last_used = false;        // the last command's encoder launch started from the table
+  int last_B = 0;
 };
 
 // host_spin: the wait for the action in nlc_mppi_finish
@@ -240,6 +255,7 @@ struct nlc_ctx {
   nlc::host::DehoogCalib dh;
   nlc::host::HostWait wait;
   nlc::host::SideStreams side;
+  nlc::host::GruPrefixState prefix;
   // tools only (options "dbg_gap_us" / "dbg_l2_mb")
   double* dbg_scratch = nullptr;
   size_t dbg_scratch_n = 0;
@@ -448,6 +464,11 @@ int launch_shift_perturb(nlc_ctx* c, RolloutCall& call);
 SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call);  // once the shifted U is current
 // ---- abi_planner_nl.hip
 int rollout_nl(nlc_ctx* c, RolloutCall& call);
+// "gru_prefix": the table of a freshly configured NL planner (or the reason there is none); doubles nlc_set_model reserves
+int gru_prefix_configure(nlc_ctx* c);
+inline size_t gru_prefix_arena_doubles(int g) {
+  return (size_t)nlc::prefix::kEntries * 2 * g + 64 + (size_t)16 * nlc::prefix::kMaxB;  // table, out_tab (62), windows
+}
 
 }  // namespace host
 }  // namespace nlc

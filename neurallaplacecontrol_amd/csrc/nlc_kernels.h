@@ -149,6 +149,22 @@ struct GruArgs {
 hipError_t launch_gru_encode(const GruArgs& a, int g, hipStream_t s, bool coop = false, unsigned lds_pad_bytes = 0);
 hipError_t launch_gru_encode_i8(const GruArgs& a, hipStream_t s);
 unsigned long long gru_i8_launch_count();  // process-wide
+// "gru_prefix" (nlc_gru_prefix.h; mode 1, nu == nin == 1, bounds): windows whose first consumed actions are clipped start
+// from a table of precomputed states.  Three launches: the table build (nlc_mppi_configure), and per command the index pass
+// behind perturb_kernel and the list launch in gru_encode_kernel's place.
+struct GruPrefixArgs {
+  double* table;       // [kEntries][2 layers][g]: a column's hidden-state images, 4 ks + q of the tile's ks * 64 + lane
+  double* out_tab;     // [kEntries][2]: linear_out of the entries of length B (B <= 4)
+  unsigned* lists;     // [kLists][list_stride]: window index | pattern << 27, in no particular order
+  unsigned* counts;    // [kLists]: windows by prefix length (length B: written straight from out_tab); zeroed by perturb_kernel
+  int64_t list_stride;
+  unsigned long long img_max, img_min;  // bit patterns of u_max / u_scale and u_min / u_scale
+};
+// table build: `a` is a mode-1 block over 16 synthetic samples of B perturbed actions (sample c, GRU step s: bit s of c picks
+// the u_min image, else the u_max image), T = Tc = B, Kep = 16
+hipError_t launch_gru_prefix_table(const GruArgs& a, const GruPrefixArgs& px, int g, hipStream_t s);
+hipError_t launch_gru_prefix_index(const GruArgs& a, const GruPrefixArgs& px, hipStream_t s);
+hipError_t launch_gru_encode_prefix(const GruArgs& a, const GruPrefixArgs& px, int g, hipStream_t s);
 
 // ------------------------------------------------------------------ samples and cost of one planner rollout
 // What every rollout body of phase 1 reads and writes besides its dynamics.  The argument blocks of the step tail and of the

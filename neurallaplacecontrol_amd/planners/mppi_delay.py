@@ -526,6 +526,24 @@ class MPPIDelay:
         """Commands re-run on the two-launch body inside nlc_mppi_finish (a give-up here or on another rank)."""
         return 0 if self.torch_path else int(self.ctx.get_stat("fused_fallbacks"))
 
+    @property
+    def gru_prefix(self):
+        """Whether the LAST command's encoder launch started windows with clipped leading actions from the precomputed
+        table (planner option ``gru_prefix``, include/nlc.h), and that command's windows by prefix length 0 .. 4 (reading
+        them waits for the command)."""
+        if self.torch_path or self.ctx is None or not int(self.ctx.get_stat("gru_prefix")):
+            return False, [0] * 5
+        return True, [int(self.ctx.get_stat(f"gru_prefix_windows_l{i}")) for i in range(5)]
+
+    @property
+    def gru_latents(self):
+        """The (K, T, 2) GRU latents of the last command (Neural-Laplace dynamics): a view of the planner's workspace."""
+        off = -1 if self.torch_path or self._buf is None else int(self.ctx.get_stat("latents_offset"))
+        if off < 0:
+            return None
+        n = self.K_local * self.T * 2 * getattr(self, "E", 1)
+        return self._ws[off:off + n].view(self._lead(self.K_local, self.T, 2))
+
     noise = property(lambda self: self._out(self._noise))
     perturbed_action = property(lambda self: self._out(self._perturbed))
     states = property(lambda self: self._out(self._states))
