@@ -109,9 +109,12 @@ int nlc_synchronize(nlc_ctx* ctx);
  *                        u_min / u_scale, and the encoder consumes a window newest action first from h = 0, so while the consumed
  *                        actions are clipped the hidden states are constants of (weights, bounds, u_scale, normalisation,
  *                        pattern).  nlc_mppi_configure builds a table of the 2 + 4 + 8 + 16 states after one to four such steps
- *                        (30 KB in the model's arena; rebuilt by every configure, which a new model forces); per command an index
+ *                        (30 KB in the model's arena; rebuilt by every configure, which a new model forces) and, for every state a
+ *                        tile can start from, the hidden-side products W_hh H (+ bias) of the step that follows it: 6 g doubles
+ *                        per entry, 90 KB reserved at hidden_units 128, of which B = 4 uses 42 KB.  Per command an index
  *                        pass behind perturb_kernel sorts the windows by the length of their clipped prefix (0 .. min(B, 4)) and
- *                        the encoder launch runs only the remaining steps of each -- same step code, bit-identical latents
+ *                        the encoder launch runs only the remaining steps of each, the first of them without its two
+ *                        hidden-side GEMMs -- same step code, every gate sums its hidden side first, bit-identical latents
  *                        (csrc/nlc_gru_prefix.h).  -1 (default): whenever the launch is in scope, silently not otherwise;
  *                        0: never (the plain launch); 1: required -- NLC_ERR_UNSUPPORTED from nlc_mppi_rollout when the command
  *                        runs another body (fused, staged), the cooperative or int8-sliced encoder, horizon chunks, nu or nin
@@ -209,6 +212,8 @@ int nlc_set_option(nlc_ctx* ctx, const char* name, double value);
  *   "gru_prefix"           1 when the LAST command's encoder launch started from the prefix-state table (option "gru_prefix")
  *   "gru_prefix_windows_l0" .. "_l4"  that command's windows by the number of leading GRU steps taken from the table (0 when
  *                          the table was not used); they sum to E K T.  Reading one waits for the command's launches
+ *   "gru_prefix_table_tiles"  that command's 16-window tiles that started from the table and took their first step's hidden-side
+ *                          products from it: sum over the lengths 1 .. min(B, 5) - 1 of ceil(windows / 16).  Waits likewise
  *   "latents_offset"       offset, in doubles, of the (E K, T, 2) GRU latents inside nlc_mppi_buffers.workspace (-1: no NL planner)
  *   "gru_gemm"             1 when encode launches run the int8-sliced kernel (option "gru_gemm" = 1 and a hidden_units = 128 model)
  *   "gru_i8_launches"      launches of the int8-sliced encoder kernel in this PROCESS so far (any ctx): the option alone does not say

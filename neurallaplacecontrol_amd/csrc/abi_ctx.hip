@@ -272,6 +272,16 @@ extern "C" int nlc_get_stat(nlc_ctx* c, const char* name, double* out) {
       NLC_HIP(c, hipMemcpy(cnt, c->prefix.lists, sizeof(cnt), hipMemcpyDeviceToHost));
       *out = (double)cnt[n[20] - '0'];
     }
+  } else if (n == "gru_prefix_table_tiles") {
+    // the last command's 16-window tiles that started from the table (lists 1 ..) and took their first step's hidden-side
+    // products from it; waits for the command's launches
+    *out = 0.0;
+    if (c->prefix.last_used && c->prefix.lists) {
+      unsigned cnt[nlc::prefix::kLists] = {0};
+      NLC_HIP(c, hipStreamSynchronize(c->stream));
+      NLC_HIP(c, hipMemcpy(cnt, c->prefix.lists, sizeof(cnt), hipMemcpyDeviceToHost));
+      for (int l = 1; l < nlc::prefix::n_lists(c->prefix.last_B); ++l) *out += (double)((cnt[l] + 15u) / 16u);
+    }
   } else if (n == "latents_offset") *out = (c->has_mppi && c->pd.dynamics == NLC_DYN_NL) ? (double)ws_layout(c).pa : -1.0;
   else if (n == "gru_i8_launches") *out = (double)nlc::gru_i8_launch_count();  // process-wide
   else return fail(c, NLC_ERR_BAD_ARG, "unknown stat: " + n);

@@ -420,6 +420,7 @@ int gru_prefix_begin(nlc_ctx* c, RolloutCall& call, const GruArgs& g, int64_t N,
   double* base = c->arena.base + ps.arena_off;
   px->table = base;
   px->out_tab = base + (size_t)prefix::kEntries * 2 * c->g;
+  px->products = base + gru_prefix_products_off(c->g);
   px->counts = reinterpret_cast<unsigned*>(ps.lists);
   px->lists = reinterpret_cast<unsigned*>(ps.lists + 64);
   px->list_stride = stride;
@@ -510,6 +511,7 @@ int nlc::host::gru_prefix_configure(nlc_ctx* c) {
   GruPrefixArgs px{};
   px.table = base;
   px.out_tab = base + (size_t)prefix::kEntries * 2 * c->g;
+  px.products = base + gru_prefix_products_off(c->g);
   double* syn_dev = px.out_tab + 64;
   NLC_HIP(c, hipMemcpy(syn_dev, syn.data(), syn.size() * sizeof(double), hipMemcpyHostToDevice));
   GruArgs a = c->gru;

@@ -11,6 +11,8 @@
 //
 // Roofline: FP64 MFMA bound.  Per 16 windows (B = 4): B*MT (input) + (B-1)*KS*MT (l0 hh) + B*KS*MT (l1 ih)
 // + (B-1)*KS*MT (l1 hh) + KS (head) = 1984 MFMAs of 2048 flop; HBM traffic is nu*8 B in + 16 B out per window.
+// ("gru_prefix", below: a tile that starts from the table after l >= 1 steps runs neither those steps nor the two hh GEMMs
+// of its first step -- 204 + 588 (l - 1) + 2*KS*MT = 384 MFMAs fewer at g = 64.)
 #include "nlc_device.h"
 #include "nlc_gru_prefix.h"
 #include "nlc_gru_tile.h"
@@ -111,10 +113,13 @@ hipError_t launch_gru_encode(const GruArgs& a, int g, hipStream_t s, bool coop, 
 
 // ------------------------------------------------------------------ saturated leading steps from a table ("gru_prefix")
 // See nlc_gru_prefix.h.  All three kernels run gru_encode_tile's own step body, so a window's latents are the bits the full
-// loop gives: a column of an MFMA tile does not depend on its neighbours, and only whole steps are skipped.
+// loop gives: a column of an MFMA tile does not depend on its neighbours, whole steps are skipped, and of a tile's first step
+// the hidden-side sums -- a prefix of every accumulation chain (nlc_gru_tile.h) -- are the table build's own accumulators.
 
 // Table build, one wavefront: the 16 sign patterns of four clipped actions are one tile.  It runs steps 0 .. min(B, 4) - 1 and
-// stores the state after step s under the first s + 1 pattern bits; with B <= 4 also linear_out of the 2^B whole windows.
+// stores the state after step s under the first s + 1 pattern bits; with B <= 4 also linear_out of the 2^B whole windows.  The
+// step that follows an entry (B > 4: a fifth step runs for the entries of length 4) stores the entry's hidden-side products:
+// the step body's own accumulators, taken where the full kernel has them.
 template <int G>
 __global__ __launch_bounds__(64) void gru_prefix_table_kernel(const GruArgs a, const GruPrefixArgs px) {
   constexpr int KS = G / 4;
@@ -123,10 +128,11 @@ __global__ __launch_bounds__(64) void gru_prefix_table_kernel(const GruArgs a, c
   __shared__ double Hs[2][KS * 64];
   // entry 0: h = 0, the start of a window without a prefix
   for (int i = lane; i < 2 * G; i += 64) px.table[i] = 0.0;
-  const int steps = prefix::cap(a.B);
+  const int steps = prefix::build_steps(a.B);
   // window (k = c, t = B - 1) of the synthetic history: every element is a perturbed one
-  const double o = gru_encode_tile<G, true>(a, lane, c, c, a.B - 1, Hs[0], Hs[1], 0, steps, px.table);
-  if (steps == a.B && q < 2 && c < (1 << steps)) px.out_tab[prefix::entry_index(steps, c) * 2 + q] = o;
+  const double o = gru_encode_tile<G, kTileBuildTable>(a, lane, c, c, a.B - 1, Hs[0], Hs[1], 0, steps, px.table,
+                                                       px.products - px.table);
+  if (a.B <= prefix::kMaxLen && q < 2 && c < (1 << a.B)) px.out_tab[prefix::entry_index(a.B, c) * 2 + q] = o;
 }
 
 // Index pass: a workgroup classifies 2048 windows (eight per thread), appends them to the list of their prefix length, or --
@@ -192,7 +198,8 @@ __global__ __launch_bounds__(256) void gru_prefix_index_kernel(const GruArgs a, 
 }
 
 // List launch: a wavefront takes 16 entries of ONE list (tiles in list order, length 0 first: the longest tiles start first
-// and the shortest fill the tail), gathers each column's images from the table, runs steps len .. B - 1 and the head.  The
+// and the shortest fill the tail), gathers each column's images from the table, runs steps len .. B - 1 and the head; step len
+// takes its hidden-side accumulators from the column's products block.  The
 // grid is sized for the worst case without reading a count back; wavefronts beyond the lists' tiles exit at once.  Padded
 // columns repeat the list's last entry and do not store.
 template <int G>
@@ -221,16 +228,19 @@ __global__ __launch_bounds__(256, G <= 64 ? 2 : 1) void gru_encode_prefix_kernel
   const int64_t kk = w / a.Tc;
   const int tt = a.t0 + (int)(w - kk * a.Tc);
   __shared__ double Hs[4][2][KS * 64];
+  double* prod = nullptr;
   if (len > 0) {  // (length 0: the tile body zeroes its images itself)
     const int pattern = (int)(e >> prefix::kPatternShift) & ((1 << len) - 1);
-    const double* ent = px.table + (size_t)prefix::entry_index(len, pattern) * 2 * G;
+    const int entry = prefix::entry_index(len, pattern);
+    const double* ent = px.table + (size_t)entry * 2 * G;
+    prod = px.products + prefix::products_entry_offset(entry, G);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       Hs[wave][0][ks * 64 + lane] = ent[4 * ks + q];
       Hs[wave][1][ks * 64 + lane] = ent[G + 4 * ks + q];
     }
   }
-  const double o = gru_encode_tile<G, true>(a, lane, w, kk, tt, Hs[wave][0], Hs[wave][1], len);
+  const double o = gru_encode_tile<G, kTileFromTable>(a, lane, w, kk, tt, Hs[wave][0], Hs[wave][1], len, -1, prod);
   if (valid && q < 2) a.out[(kk * a.T + tt) * 2 + q] = o;
 }
 

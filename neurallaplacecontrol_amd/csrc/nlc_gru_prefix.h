@@ -7,7 +7,8 @@
 // mppi_bound), so a clipped action is stored as exactly u_max / u_scale or u_min / u_scale -- the bound's IMAGE.  The encoder
 // consumes a window newest action first from h = 0 (nlc_gru_tile.h); while the consumed actions are images, the two layers'
 // hidden states are constants of (weights, bounds, normalisation, pattern of max / min), kept in a table of
-// 1 + 2 + 4 + 8 + 16 entries built when the planner is configured.  nu = 1 only.
+// 1 + 2 + 4 + 8 + 16 entries built when the planner is configured -- and with them the hidden-side products of the step that
+// follows an entry (below).  nu = 1 only.
 #pragma once
 #include <cstdint>
 
@@ -65,6 +66,22 @@ NLC_PREFIX_HD inline Class classify(const double* row, int t, int B, uint64_t im
     c.len = s + 1;
   }
   return c;
+}
+
+// ---- the hidden-side products of a table-started tile's first step.  A tile on list len >= 1 runs step s = len first; there
+// W_hh0 H0 and W_hh1 H1 are functions of the table entry alone.  The step body (nlc_gru_tile.h) sums "bias + hh" FIRST in every
+// accumulation chain, so the table build stores the six accumulator sets (layer 0: r, z from 0 and hn from b_hn; layer 1: r, z,
+// hn from their biases) as the full step has them at that point, and the list launch loads them in place of 2 KS 3 GT MFMAs.
+// Entries 1 .. 30 have products (entry 0 is h = 0: step 0 has no hidden side; an entry of length B starts no tile and its
+// block stays unwritten), 6 g doubles each, in accumulator-register order: a lane (q = lane >> 4) reads register r of gate
+// set `set` in {r, z, hn} of layer `layer`'s chunk j -- one aligned 32-byte v4d per set.
+NLC_PREFIX_HD inline bool starts_tile(int len, int B) { return len >= 1 && len < n_lists(B); }
+// steps the table build runs: one beyond the last image when tiles start from the longest entries (B > 4)
+NLC_PREFIX_HD inline int build_steps(int B) { return B <= kMaxLen ? B : kMaxLen + 1; }
+NLC_PREFIX_HD inline int64_t products_doubles(int g) { return (int64_t)(kEntries - 1) * 6 * g; }
+NLC_PREFIX_HD inline int64_t products_entry_offset(int entry, int g) { return (int64_t)(entry - 1) * 6 * g; }
+NLC_PREFIX_HD inline int products_index(int layer, int j, int set, int q, int r, int g) {
+  return (((layer * (g / 16) + j) * 3 + set) * 4 + q) * 4 + r;
 }
 
 // encoder tiles of the list launch: sum over the lists of ceil(count / 16) <= N / 16 + lists; no count is read back

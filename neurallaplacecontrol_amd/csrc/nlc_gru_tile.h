@@ -3,6 +3,7 @@
 // (kernels_fused.hip).  See kernels_gru.hip for the dataflow and the roofline.
 #pragma once
 #include "nlc_device.h"
+#include "nlc_gru_prefix.h"
 #include "nlc_kernels.h"
 
 namespace nlc {
@@ -135,18 +136,31 @@ __device__ __forceinline__ v4d gru_gates(const v4d& ar, const v4d& az, const v4d
   return hnew;
 }
 
+// Accumulation order of a gate pre-activation (both tile bodies below, every step): "bias + hidden side" FIRST, the
+// input side after it -- layer 0 r / z: 0, the W_hh0 H0 k-steps, then the one input MFMA; layer 1 r / z: bias, the W_hh1 H1
+// k-steps, then the W_ih1 H0 k-steps; hn: bias then hh; in: the input side alone.  So the hidden side's sum is a prefix of
+// every chain, and where it is a constant of the start state it can be loaded instead of summed (kTileFromTable).  Step 0 has
+// no hidden side.
+//
 // One wavefront encodes the 16 windows its lanes' columns name.  Mode 0: window row `wc` of the explicit (N, B, nin)
 // tensor; mode 1: window (kk, tt) of the MPPI history.  H0 / H1: this wave's hidden-state images in LDS (KS*64 doubles
 // each, every entry written and read by the same lane: no barrier).  Returns linear_out row q (valid for q < 2).
-// The step loop runs steps [s0, s_end) (s_end < 0: a.B).  With s0 > 0 the caller has filled H0 / H1 with the images after
-// step s0 - 1 (the "gru_prefix" list launch: nlc_gru_prefix.h); a non-finite input of a step that does not run is not seen.
-// `dump` (the table build): after step s, column c < 2^(s+1) stores both images as table entry 2^(s+1) - 1 + c,
-// dump[(entry * 2 + layer) * G + 4 ks + q] = H[ks * 64 + lane].
-// (kPrefix = false: s0, s_end and dump are not looked at -- the instances every other launch runs are the code they were)
-template <int G, bool kPrefix = false>
+// kMode (the "gru_prefix" launches, nlc_gru_prefix.h):
+//   kTileFull       steps 0 .. B - 1 from h = 0; s0, s_end and tab are not looked at -- the instances every other launch runs
+//   kTileFromTable  the list launch: steps s0 .. B - 1.  With s0 > 0 the caller has filled H0 / H1 with the images after
+//                   step s0 - 1 and `tab` is THIS LANE's column's products block (6 G doubles, prefix::products_index): step
+//                   s0 takes its six hidden-side accumulator sets from there and runs no hidden-side GEMM.  A non-finite
+//                   input of a step that does not run is not seen.
+//   kTileBuildTable the table build: steps 0 .. s_end - 1 from h = 0, `tab` the whole table (images, then at tab_products
+//                   the products).  After step s < kMaxLen, column c < 2^(s+1) stores both images as entry
+//                   e = 2^(s+1) - 1 + c, tab[(e * 2 + layer) * G + 4 ks + q] = H[ks * 64 + lane]; in step s >= 1, column
+//                   c < 2^s holds entry 2^s - 1 + c's state and stores its accumulators as they stand after the hidden side.
+enum { kTileFull = 0, kTileFromTable = 1, kTileBuildTable = 2 };
+template <int G, int kMode = kTileFull>
 __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, int64_t wc, int64_t kk, int tt,
                                                   double* __restrict__ H0, double* __restrict__ H1, int s0 = 0,
-                                                  int s_end = -1, double* __restrict__ dump = nullptr) {
+                                                  int s_end = -1, double* __restrict__ tab = nullptr,
+                                                  int64_t tab_products = 0) {
   constexpr int GT = G / 16;   // tiles per gate = chunks
   constexpr int KS = G / 4;    // k-steps over the hidden dimension
   const int q = lane >> 4;
@@ -157,7 +171,7 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
     in_std = a.std[q];
   }
   const int ab_off = (a.mode == 1) ? (int)(kk / a.Kep) * a.B : 0;  // this sample's episode block of action_buffer
-  if (!kPrefix || s0 == 0) {
+  if (kMode != kTileFromTable || s0 == 0) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       H0[ks * 64 + lane] = 0.0;
@@ -169,7 +183,9 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
   // gate math here clamps with v_min / v_max, which swallow a NaN -- so the window is remembered and its outputs are replaced
   bool bad_input = false;
 
-  for (int s = kPrefix ? s0 : 0; s < ((kPrefix && s_end >= 0) ? s_end : a.B); ++s) {
+  // one GRU step; kTab: the hidden-side accumulators come from the table (the first step of a table-started tile)
+  auto step = [&](int s, auto tab_c) __attribute__((always_inline)) {
+    constexpr bool kTab = decltype(tab_c)::value;
     // reversed time: GRU step s consumes window element B-1-s  (torch.flip, w_nl.py:27)
     const int j_win = a.B - 1 - s;
     double xin = 0.0;
@@ -190,15 +206,42 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
     } else if (q == 3) {
       xin = 1.0;  // bias column of the packed W_ih0
     }
+    // the table's sets of layer l, chunk j: this lane's three v4d (r, z, hn), 32-byte aligned
+    auto tab_set = [&](int l, int j, int set) -> v4d* {
+      return reinterpret_cast<v4d*>(tab + prefix::products_index(l, j, set, q, 0, G));
+    };
+    // table build: the products block of the entry column c's state is (step s >= 1, c < 2^s)
+    double* put = nullptr;
+    if (kMode == kTileBuildTable && s > 0 && (lane & 15) < (1 << s))
+      put = tab + tab_products + prefix::products_entry_offset(prefix::entry_index(s, lane & 15), G);
+    auto put_sets = [&](int l, int j, const v4d& ar, const v4d& az, const v4d& ahn) {
+      if (put == nullptr) return;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        put[prefix::products_index(l, j, 0, q, r, G)] = ar[r];
+        put[prefix::products_index(l, j, 1, q, r, G)] = az[r];
+        put[prefix::products_index(l, j, 2, q, r, G)] = ahn[r];
+      }
+    };
     // ---------------- layer 0: input side is one k-step (K = nin padded to 4, bias folded into column 3)
 #pragma unroll
     for (int j = 0; j < GT; ++j) {
       gptr wp = opaque(a.Wih0p + (size_t)j * 3 * 64);
-      v4d ar = mfma(wp[lane], xin, splat(0.0));
-      v4d az = mfma(wp[64 + lane], xin, splat(0.0));
-      v4d ain = mfma(wp[128 + lane], xin, splat(0.0));
-      v4d ahn = load_bias_tile(a.bhn0, j, q);
-      if (s > 0) chunk_gemm<KS>(ar, az, ahn, a.Whh0p + (size_t)j * KS * 3 * 64, lane, H0);
+      v4d ar, az, ahn;
+      if (kTab) {
+        ar = *tab_set(0, j, 0);
+        az = *tab_set(0, j, 1);
+        ahn = *tab_set(0, j, 2);
+      } else {
+        ar = splat(0.0);
+        az = splat(0.0);
+        ahn = load_bias_tile(a.bhn0, j, q);
+        if (s > 0) chunk_gemm<KS>(ar, az, ahn, a.Whh0p + (size_t)j * KS * 3 * 64, lane, H0);
+        if (kMode == kTileBuildTable) put_sets(0, j, ar, az, ahn);
+      }
+      ar = mfma(wp[lane], xin, ar);
+      az = mfma(wp[64 + lane], xin, az);
+      const v4d ain = mfma(wp[128 + lane], xin, splat(0.0));
       const v4d hold = {H0[(4 * j + 0) * 64 + lane], H0[(4 * j + 1) * 64 + lane], H0[(4 * j + 2) * 64 + lane],
                         H0[(4 * j + 3) * 64 + lane]};
       hn[j] = gru_gates(ar, az, ain, ahn, hold);
@@ -210,12 +253,20 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
     // ---------------- layer 1
 #pragma unroll
     for (int j = 0; j < GT; ++j) {
-      v4d ar = load_bias_tile(a.brz1, j, q);
-      v4d az = load_bias_tile(a.brz1, GT + j, q);
+      v4d ar, az, ahn;
+      if (kTab) {
+        ar = *tab_set(1, j, 0);
+        az = *tab_set(1, j, 1);
+        ahn = *tab_set(1, j, 2);
+      } else {
+        ar = load_bias_tile(a.brz1, j, q);
+        az = load_bias_tile(a.brz1, GT + j, q);
+        ahn = load_bias_tile(a.bhn1, j, q);
+        if (s > 0) chunk_gemm<KS>(ar, az, ahn, a.Whh1p + (size_t)j * KS * 3 * 64, lane, H1);
+        if (kMode == kTileBuildTable) put_sets(1, j, ar, az, ahn);
+      }
       v4d ain = load_bias_tile(a.bin1, j, q);
-      v4d ahn = load_bias_tile(a.bhn1, j, q);
       chunk_gemm<KS>(ar, az, ain, a.Wih1p + (size_t)j * KS * 3 * 64, lane, H0);
-      if (s > 0) chunk_gemm<KS>(ar, az, ahn, a.Whh1p + (size_t)j * KS * 3 * 64, lane, H1);
       const v4d hold = {H1[(4 * j + 0) * 64 + lane], H1[(4 * j + 1) * 64 + lane], H1[(4 * j + 2) * 64 + lane],
                         H1[(4 * j + 3) * 64 + lane]};
       hn[j] = gru_gates(ar, az, ain, ahn, hold);
@@ -224,15 +275,22 @@ __device__ __forceinline__ double gru_encode_tile(const GruArgs& a, int lane, in
     for (int j = 0; j < GT; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) H1[(4 * j + r) * 64 + lane] = hn[j][r];
-    if (kPrefix && dump != nullptr && (lane & 15) < (2 << s)) {
-      double* e = dump + (size_t)((2 << s) - 1 + (lane & 15)) * 2 * G;
+    if (kMode == kTileBuildTable && s < prefix::kMaxLen && (lane & 15) < (2 << s)) {
+      double* e = tab + (size_t)((2 << s) - 1 + (lane & 15)) * 2 * G;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         e[4 * ks + q] = H0[ks * 64 + lane];
         e[G + 4 * ks + q] = H1[ks * 64 + lane];
       }
     }
+  };
+
+  int s = (kMode == kTileFromTable) ? s0 : 0;
+  if (kMode == kTileFromTable && s0 > 0) {
+    step(s, std::true_type{});
+    ++s;
   }
+  for (const int end = (kMode == kTileBuildTable) ? s_end : a.B; s < end; ++s) step(s, std::false_type{});
   // ---------------- linear_out (2 x g): rows 0,1 of one output tile
   v4d o[1];
   o[0] = splat(0.0);
@@ -318,11 +376,12 @@ __device__ __forceinline__ double gru_encode_tile_coop(const GruArgs& a, int lan
       const int j = wv + 4 * i;
       if (kAllWaves || j < GT) {
         gptr wp = opaque(a.Wih0p + (size_t)j * 3 * 64);
-        v4d ar = mfma(wp[lane], xin, splat(0.0));
-        v4d az = mfma(wp[64 + lane], xin, splat(0.0));
-        v4d ain = mfma(wp[128 + lane], xin, splat(0.0));
+        v4d ar = splat(0.0), az = splat(0.0);  // (hidden side first: see the accumulation order above gru_encode_tile)
         v4d ahn = load_bias_tile(a.bhn0, j, q);
         if (s > 0) chunk_gemm<KS>(ar, az, ahn, a.Whh0p + (size_t)j * KS * 3 * 64, lane, H0c);
+        ar = mfma(wp[lane], xin, ar);
+        az = mfma(wp[64 + lane], xin, az);
+        const v4d ain = mfma(wp[128 + lane], xin, splat(0.0));
         const v4d hold = {H0c[(4 * j + 0) * 64 + lane], H0c[(4 * j + 1) * 64 + lane], H0c[(4 * j + 2) * 64 + lane],
                           H0c[(4 * j + 3) * 64 + lane]};
         const v4d hn = gru_gates(ar, az, ain, ahn, hold);
@@ -340,8 +399,8 @@ __device__ __forceinline__ double gru_encode_tile_coop(const GruArgs& a, int lan
         v4d az = load_bias_tile(a.brz1, GT + j, q);
         v4d ain = load_bias_tile(a.bin1, j, q);
         v4d ahn = load_bias_tile(a.bhn1, j, q);
-        chunk_gemm<KS>(ar, az, ain, a.Wih1p + (size_t)j * KS * 3 * 64, lane, H0n);
         if (s > 0) chunk_gemm<KS>(ar, az, ahn, a.Whh1p + (size_t)j * KS * 3 * 64, lane, H1c);
+        chunk_gemm<KS>(ar, az, ain, a.Wih1p + (size_t)j * KS * 3 * 64, lane, H0n);
         const v4d hold = {H1c[(4 * j + 0) * 64 + lane], H1c[(4 * j + 1) * 64 + lane], H1c[(4 * j + 2) * 64 + lane],
                           H1c[(4 * j + 3) * 64 + lane]};
         const v4d hn = gru_gates(ar, az, ain, ahn, hold);

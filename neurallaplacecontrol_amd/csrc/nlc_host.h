@@ -143,7 +143,7 @@ struct DehoogCalib {
 // nlc_mppi_configure -- a new model, other bounds / u_scale / normalisation or another B all pass through there; the window
 // lists and their counters are the ctx's own buffer, grown at the first command that needs it
 struct GruPrefixState {
-  size_t arena_off = 0;          // table, out_tab and the table build's 16 synthetic windows, in doubles from the arena's base
+  size_t arena_off = 0;          // table, out_tab, the table build's 16 synthetic windows and the products, in doubles from the arena's base
   const char* why_not = "gru_prefix: planner not configured";  // out of scope (nullptr: the table is built)
   unsigned long long img_max = 0, img_min = 0;
   double* lists = nullptr;       // counters (one 64-double row) + kLists lists
@@ -466,8 +466,10 @@ SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call);  // 
 int rollout_nl(nlc_ctx* c, RolloutCall& call);
 // "gru_prefix": the table of a freshly configured NL planner (or the reason there is none); doubles nlc_set_model reserves
 int gru_prefix_configure(nlc_ctx* c);
+// table, out_tab (62), the build's windows; then the products (a multiple of 4 doubles from the base: v4d loads)
+inline size_t gru_prefix_products_off(int g) { return (size_t)nlc::prefix::kEntries * 2 * g + 64 + (size_t)16 * nlc::prefix::kMaxB; }
 inline size_t gru_prefix_arena_doubles(int g) {
-  return (size_t)nlc::prefix::kEntries * 2 * g + 64 + (size_t)16 * nlc::prefix::kMaxB;  // table, out_tab (62), windows
+  return gru_prefix_products_off(g) + (size_t)nlc::prefix::products_doubles(g);
 }
 
 }  // namespace host

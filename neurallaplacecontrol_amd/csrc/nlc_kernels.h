@@ -155,6 +155,8 @@ unsigned long long gru_i8_launch_count();  // process-wide
 struct GruPrefixArgs {
   double* table;       // [kEntries][2 layers][g]: a column's hidden-state images, 4 ks + q of the tile's ks * 64 + lane
   double* out_tab;     // [kEntries][2]: linear_out of the entries of length B (B <= 4)
+  double* products;    // [kEntries - 1][6 g]: entries 1 .. 30, the hidden-side accumulators of the step that follows the entry
+                       // (prefix::products_index; written for the entries of a length below B)
   unsigned* lists;     // [kLists][list_stride]: window index | pattern << 27, in no particular order
   unsigned* counts;    // [kLists]: windows by prefix length (length B: written straight from out_tab); zeroed by perturb_kernel
   int64_t list_stride;
