@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 14
+#define NLC_ABI_VERSION 15
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -614,6 +614,43 @@ typedef struct nlc_collect_desc {
 int nlc_collect_step(nlc_ctx* ctx, const nlc_collect_desc* desc, int it, int64_t episode_base, double* state_dev,
                      double* abuf_dev, const double* action_dev_or_null, double* ret_dev, double* s0_dev, double* a0_dev,
                      double* sn_dev, double* ts_dev);
+
+/* ---- synthetic transition dataset (overlay.py:664-737, generate_irregular_data_delay_time_multi with rand=True; states and
+ * actions from compute_state_actions, :603-631; one Euler step per row, batch_integrate_system, base_env.py:231-280).
+ * A dataset is TI time blocks x A actions x S states, row r = (ti * A + i) * S + j.  Per row: the reduced state j of block
+ * ti, (2u - 1) * state_max per component; action i of block ti, (2u - 1) * action_high per action dim; the block's
+ * interval tsn by ts_grid (drawn once per block); s0 = observation of the state, sn = observation after one Euler step of
+ * size tsn, ts = tsn; a0 = a (B, nu + time_channel) buffer of uniform fills (2u - 1) * action_high whose row B - 1 - delay
+ * is the row's action, the time column, where there is one, B - 1 .. 0 (:718-731).
+ * Random draws are Philox4x32-10 keyed by `seed`; the counters depend on (ti, j) (state), (ti, i) (action), ti (interval)
+ * and (global row r, buffer row) (fill) only, never on the launch shape or on which blocks a call covers
+ * (docs/synthetic.md).  With `reuse` the states and actions of every block are block 0's (:695-702). */
+typedef struct nlc_synth_desc {
+  int32_t env;       /* NLC_ENV_CARTPOLE / _PENDULUM / _ACROBOT */
+  int32_t friction;
+  double dt;
+  int32_t delay;     /* the row's action is buffer row B - 1 - delay */
+  int32_t B;         /* action buffer rows */
+  int32_t nu;        /* action dims (must be the env's) */
+  int32_t time_channel; /* 1: encode_obs_time -- the buffer has nu + 1 columns, the last is B - 1 .. 0 */
+  int32_t ts_grid;   /* NLC_TS_GRID_* */
+  int32_t reuse;     /* reuse_state_actions_when_sampling_times */
+  int64_t S;         /* states per time block */
+  int64_t A;         /* actions per time block */
+  double action_high;
+  double state_max[4]; /* the box of the reduced state; the first n (4, pendulum 2) are read */
+  uint64_t seed;
+} nlc_synth_desc;
+/* Writes time blocks [ti_begin, ti_end) to rows [(ti - ti_begin) * A * S, (ti - ti_begin + 1) * A * S) of
+ *   s0_dev, sn_dev ((ti_end - ti_begin) A S, d); a0_dev (.., B, nu + time_channel); ts_dev (..)
+ * so that calls over consecutive block ranges concatenate to the call over their union, bit for bit.
+ * NLC_ERR_UNSUPPORTED: an env other than the three above; ti_end * A * S >= 2^40 (global rows are counter words and int64
+ * element indices), or a call of more than (2^31 - 1) * 256 rows.  NLC_ERR_BAD_SHAPE: B < 1, delay outside
+ * [0, B-1], nu not the env's, S < 1, A < 1, ti_begin < 0, ti_end <= ti_begin or ti_end >= 2^31.  NLC_ERR_BAD_ARG: NULL
+ * pointer, unknown ts_grid, dt, action_high or a state_max that is not > 0.  Every field is checked on the host and nothing
+ * is launched after a refusal. */
+int nlc_synth_generate(nlc_ctx* ctx, const nlc_synth_desc* desc, int64_t ti_begin, int64_t ti_end, double* s0_dev,
+                       double* a0_dev, double* sn_dev, double* ts_dev);
 
 /* ---- in-library kernel timing (hipEvent pairs on the launch stream) ------------------------- */
 int nlc_profile_enable(nlc_ctx* ctx, int on);

@@ -8,6 +8,7 @@ Drop-in mirrors of the reference's Python interfaces for this path (SURVEY.md §
     from neurallaplacecontrol_amd import NLTrainer              # train_utils.py:388-408 (fused training step)
     from neurallaplacecontrol_amd import DeltaTRNN, NODE        # train_utils.py:589, :664 (baseline models)
     from neurallaplacecontrol_amd import collect_expert_dataset # mppi_dataset_collector.py:324-443 (expert dataset)
+    from neurallaplacecontrol_amd import generate_synthetic_dataset  # overlay.py:664-737 (synthetic dataset)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of ``libnlc_hip.so``
 (``include/nlc.h``); importing the package does not touch the GPU.  There is no CPU fallback.
@@ -22,6 +23,7 @@ from .nl_model import LaplaceRepresentationFunc, NeuralLaplaceModel, ReverseGRUE
 from .node_model import NODE, xOdeFuncInXAndU  # noqa: F401
 from .rnn_model import RNN, DeltaTRNN  # noqa: F401
 from .training import NLTrainer, NLTrainerGroup, RNNTrainer, RNNTrainerGroup  # noqa: F401
+from .synthetic import generate_synthetic_dataset, synthetic_dataset_shape  # noqa: F401
 from .planners.mppi_batch import BatchedMPPIDelay  # noqa: F401
 from .planners.mppi_delay import MPPIDelay  # noqa: F401
 
@@ -33,6 +35,8 @@ __all__ = [
     "ExpertCollector",
     "collect_expert_dataset",
     "replay_buffer_file_name",
+    "generate_synthetic_dataset",
+    "synthetic_dataset_shape",
     "NeuralLaplaceModel",
     "NLTrainer",
     "NLTrainerGroup",

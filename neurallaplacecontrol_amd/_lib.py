@@ -93,6 +93,7 @@ SYMBOLS = [
     "nlc_env_step",
     "nlc_env_obs",
     "nlc_collect_step",
+    "nlc_synth_generate",
     "nlc_profile_enable",
     "nlc_profile_reset",
     "nlc_profile_count",
@@ -223,6 +224,25 @@ class CollectDesc(C.Structure):
     ]
 
 
+class SynthDesc(C.Structure):
+    _fields_ = [
+        ("env", C.c_int32),
+        ("friction", C.c_int32),
+        ("dt", C.c_double),
+        ("delay", C.c_int32),
+        ("B", C.c_int32),
+        ("nu", C.c_int32),
+        ("time_channel", C.c_int32),
+        ("ts_grid", C.c_int32),
+        ("reuse", C.c_int32),
+        ("S", C.c_int64),
+        ("A", C.c_int64),
+        ("action_high", C.c_double),
+        ("state_max", C.c_double * 4),
+        ("seed", C.c_uint64),
+    ]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -290,6 +310,7 @@ def load_library():
         lib.nlc_env_step.argtypes = [vp, i32, i32, dbl, i32, i64, i32, i32, vp, vp, vp, vp, vp]
         lib.nlc_env_obs.argtypes = [vp, i32, i64, vp, vp]
         lib.nlc_collect_step.argtypes = [vp, P(CollectDesc), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.nlc_synth_generate.argtypes = [vp, P(SynthDesc), i64, i64, vp, vp, vp, vp]
         lib.nlc_rep_func.argtypes = [vp, vp, i64, vp, vp]
         lib.nlc_set_option.argtypes = [vp, C.c_char_p, dbl]
         lib.nlc_get_stat.argtypes = [vp, C.c_char_p, P(dbl)]

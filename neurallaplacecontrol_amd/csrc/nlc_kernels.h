@@ -465,6 +465,21 @@ struct CollectStepArgs {
 };
 hipError_t launch_collect_step(const CollectStepArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ synthetic transition dataset (kernels_synth.hip)
+// Time blocks [ti_begin, ti_begin + rows / (A S)) of generate_irregular_data_delay_time_multi (overlay.py:664-737, rand=True):
+// see nlc_synth_generate (include/nlc.h).  Element math: nlc_synth.h; device bodies shared with env_step_kernel: nlc_env_dev.h.
+struct SynthArgs {
+  int env, friction, B, nu, delay, time_channel, ts_grid, reuse;
+  int64_t S, A, ti_begin, rows;  // rows = (ti_end - ti_begin) * A * S
+  double dt, action_high, state_max[4];
+  uint64_t seed;
+  double* s0;  // (rows, d)
+  double* a0;  // (rows, B, nu + time_channel)
+  double* sn;  // (rows, d)
+  double* ts;  // (rows)
+};
+hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ MPPI sampling / weighting
 constexpr int kMaxInlineAbuf = 32;  // action_buffer doubles carried in the kernel arguments (B*nu <= 32)
 struct PerturbArgs {
