@@ -512,7 +512,11 @@ int nlc_mppi_set_goal_flipped(nlc_ctx* ctx, int flipped);
  * softmax partials (beta_r, eta_r, S_r) into buf->partials.
  *   state_host: (d) or (K,d) if state_per_sample (:243-246); action_buffer_host: (B,nu).
  *   E > 1: state (E,d) or (E,K,d), action_buffer (E,B,nu); both may then be host OR device pointers.
- *   rng: 0 = buf->noise holds the caller's raw draw; 1 = device Philox4x32-10(seed, counter). */
+ *   rng: 0 = buf->noise holds the caller's raw draw; 1 = device Philox4x32-10(seed, counter): sample k of episode e, horizon
+ *   step t takes the block of counter words (kg lo, kg hi, t, counter lo) under the key (seed lo, seed hi ^ counter hi), with
+ *   kg = e * K_global + k_offset + k the GLOBAL sample index, so a draw does not depend on the sharding.  The block's words
+ *   0, 1 and 2, 3 make two 53-bit uniforms u1, u2 in (0, 1), z = sqrt(-2 ln u1) (cos, sin)(2 pi u2 - pi), and
+ *   eps = noise_mu + noise_chol z (the lower factor; nu = 1 takes z[0]). */
 int nlc_mppi_rollout(nlc_ctx* ctx, const double* state_host, int state_per_sample,
                      const double* action_buffer_host, const nlc_mppi_buffers* buf, int rng, uint64_t seed,
                      uint64_t counter);

@@ -133,7 +133,7 @@ class ExpertCollector:
         buffer (``:231-235``) and a zero episode return; the next ``collect_step`` is step 0.  Env e starts global episode
         ``episode_base + e`` from the first draw of ``RandomState(seed + episode_base + e)``."""
         for e, rng in enumerate(self.env._rngs):  # (re-seeded in place: the stream of RandomState(seed + g), cheaply)
-            rng.seed(self.seed + self.episode_base + e)
+            rng.seed((self.seed + self.episode_base + e) % 2**32)  # (as BatchedEnv.seed: RandomState seeds are 32-bit)
         self.env.reset(harness_start=False)
         self._reset_buffers()
         return self.env.get_obs()

@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "nlc_math.h"
+#include "nlc_philox.h"  // u4, philox4x32_10, u53
 
 namespace nlc {
 
@@ -173,31 +174,6 @@ __device__ __forceinline__ void gemm_acc_head(v4d (&acc)[MT], const double (&a0)
 __device__ __forceinline__ v4d load_bias_tile(const double* __restrict__ b, int j, int q) {
   const double* p = b + 16 * j + q;
   return v4d{p[0], p[4], p[8], p[12]};
-}
-
-// ---- Philox4x32-10 (Salmon et al. 2011), counter-based so a K-shard reproduces the unsharded stream
-struct u4 {
-  uint32_t x, y, z, w;
-};
-__host__ __device__ inline u4 philox4x32_10(u4 ctr, uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)M0 * ctr.x, p1 = (uint64_t)M1 * ctr.z;
-    u4 n;
-    n.x = (uint32_t)(p1 >> 32) ^ ctr.y ^ k0;
-    n.y = (uint32_t)p1;
-    n.z = (uint32_t)(p0 >> 32) ^ ctr.w ^ k1;
-    n.w = (uint32_t)p0;
-    ctr = n;
-    k0 += W0;
-    k1 += W1;
-  }
-  return ctr;
-}
-// two uint32 -> uniform double in (0,1): 53 random bits, never 0
-__host__ __device__ inline double u53(uint32_t hi, uint32_t lo) {
-  const uint64_t v = (((uint64_t)hi << 32) | lo) >> 11;
-  return ((double)v + 0.5) * (1.0 / 9007199254740992.0);
 }
 
 }  // namespace nlc

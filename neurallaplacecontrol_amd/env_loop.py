@@ -58,8 +58,10 @@ class BatchedEnv:
         self.reset()
 
     def seed(self, seed=0):
-        """Env e draws from its own ``np.random.RandomState(seed + e)`` (the reference seeds one env per process)."""
-        self._rngs = [np.random.RandomState(int(seed) + e) for e in range(self.E)]
+        """Env e draws from its own ``np.random.RandomState(seed + e)`` (the reference seeds one env per process).
+        ``RandomState`` takes 32-bit seeds: ``seed + e`` is reduced modulo 2^32, so the 64-bit seeds the kernels' Philox key
+        takes (``ExpertCollector(seed=...)``) are accepted here too."""
+        self._rngs = [np.random.RandomState((int(seed) + e) % 2**32) for e in range(self.E)]
 
     def _draw(self, rng):
         if self.env_name == "oderl-cartpole":  # ctcartpole.py:160-170 (swing_up)
