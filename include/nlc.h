@@ -302,7 +302,10 @@ int nlc_rep_func(nlc_ctx* ctx, const double* rep_in_dev, int64_t N, double* thet
 /* ---- training: one iteration of the reference's loop over a NeuralLaplaceModel (train_utils.py:388-408, float64 as
  *      model.double() at :267): pred = model(bs0, ba0, bts); loss = MSELoss(pred.squeeze(), bsd.squeeze()); backward;
  *      clip_grad_norm_(params, max_grad_norm); Adam.step().  The shape comes from nlc_set_model on the same ctx; the kernels
- *      take what it takes with the Fourier ILT (any other algorithm, or B > 16: NLC_ERR_UNSUPPORTED).
+ *      take what it takes with the Fourier ILT (scale 2) and with the linear algorithms, fixed Talbot and Stehfest (any scale:
+ *      they have none; x = (1/t) Re sum_k W_k F(delta_k / t) with the node / weight tables of the forward).  de Hoog, a
+ *      Stehfest series the tables do not hold (odd, or past 20 terms), or B > 16: NLC_ERR_UNSUPPORTED on the host, before
+ *      any launch.
  *   params_dev, grad_dev, m_dev, v_dev: flat device arrays of nlc_model_blob_size doubles in nlc_set_model's blob order.
  *   obs_dev (M, d), window_dev (M, B, nin) raw actions, ts_dev (M) raw ts_pred, target_dev (M, d) = bsn - bs0 of the dataset;
  *   idx_dev (N) int64 row indices into them (the reference's permutation[iter*bs : iter*bs+bs], no gather copy).

@@ -1,4 +1,5 @@
-// Host side of libnlc_hip.so, training unit: the fused training step of a NeuralLaplaceModel (kernels_train.hip) and of the
+// Host side of libnlc_hip.so, training unit: the fused training step of a NeuralLaplaceModel (kernels_train.hip; the Fourier
+// ILT, or fixed Talbot / Stehfest with the node and weight tables of abi_ilt.hip's linear_tables) and of the
 // DeltaTRNN / RNN baselines (kernels_train_rnn.hip), one iteration of the reference's loop, train_utils.py:388-408 (forward,
 // MSELoss, backward, clip_grad_norm_, Adam.step).  The two models differ in the forward + backward launch and the blob's
 // tensors; the workspace, the reduction and the Adam launch are written once.  Every entry is the group path: M same-shaped
@@ -78,10 +79,22 @@ int check_group(nlc_ctx* c, int M, int64_t data_rows) {
   return NLC_OK;
 }
 
+// fixed Talbot / Stehfest: fixed nodes and weights (linear_tables), the <true> instance of train_fwd_bwd_kernel
+bool linear_ilt(const nlc_ilt_desc& ilt) { return ilt.algo == NLC_ILT_FIXED_TALBOT || ilt.algo == NLC_ILT_STEHFEST; }
+
 int check_train(nlc_ctx* c, int64_t N, int B) {
   if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
-  if (c->md.ilt.algo != NLC_ILT_FOURIER) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: fourier models only");
-  if (c->md.ilt.scale != 2.0) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step needs ILT scale == 2");
+  const nlc_ilt_desc& ilt = c->md.ilt;
+  if (linear_ilt(ilt)) {
+    // what linear_tables cannot build: an odd or too long Stehfest series, terms past the tables
+    if (check_ilt(c, &ilt) != NLC_OK)
+      return fail(c, NLC_ERR_UNSUPPORTED,
+                  "fused training step: no node / weight tables for these terms (stehfest: even, 2 .. 20; fixed_tablot: 2 .. 129)");
+  } else {
+    if (ilt.algo != NLC_ILT_FOURIER)
+      return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: fourier, fixed_tablot and stehfest models only");
+    if (ilt.scale != 2.0) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step needs ILT scale == 2 (fourier)");
+  }
   if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
   if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
   return NLC_OK;
@@ -182,6 +195,9 @@ int nl_fwd_bwd(nlc_ctx* c, const double* params, const double* obs, const double
   a.time_div = md.time_div;
   a.alpha = md.ilt.alpha;
   a.log_tol = std::log(md.ilt.tol);
+  // one table for all members of a group (they share the descriptor); NULL selects the Fourier instance
+  if (linear_ilt(md.ilt))
+    if (int rc = linear_tables(c, &md.ilt, &a.lin_tab)) return rc;
   for (int i = 0; i < md.d; ++i) {
     a.sm[i] = md.state_mean[i];
     a.ss[i] = md.state_std[i];

@@ -1,6 +1,7 @@
-// Fused training step of NeuralLaplaceModel with the Fourier ILT: one iteration of the reference's training loop
-// (train_utils.py:388-408: model(bs0, ba0, bts), MSELoss, backward, clip_grad_norm_, Adam.step), float64 throughout
-// (model.double(), train_utils.py:267).  Three launches, no host synchronisation:
+// Fused training step of NeuralLaplaceModel with the Fourier ILT or one of the linear algorithms (fixed Talbot, Stehfest:
+// the <true> instance of train_fwd_bwd_kernel, which differs in the query points and the line integral only): one iteration
+// of the reference's training loop (train_utils.py:388-408: model(bs0, ba0, bts), MSELoss, backward, clip_grad_norm_,
+// Adam.step), float64 throughout (model.double(), train_utils.py:267).  Three launches, no host synchronisation:
 //
 // blockIdx.y is the member of a group of same-shaped models (nlc_train.h GroupStrides; a single model is M = 1): every kernel
 // moves its base pointers by the member's strides and then does what it does for one model, with no atomics and no read of
@@ -24,9 +25,9 @@
 // gradient to 1e-9 of its tensor's max |grad| against float64 autograd on the CPU.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage; table in docs/training.md): train_fwd_bwd_kernel 256 VGPRs + 250
-// AGPRs and 68 B/lane of scratch, not yet traced to its source; one wave per SIMD.  The kernel is latency-bound at 2.3 ms
-// per batch-16 iteration (docs/training.md): the next step is LDS-resident activations and MFMA forward products, not this
-// scratch.
+// AGPRs and 68 B/lane of scratch, not yet traced to its source (the linear instance: 230 AGPRs and none); one wave per
+// SIMD.  The kernel is latency-bound at 2.3 ms per batch-16 iteration (docs/training.md): the next step is LDS-resident
+// activations and MFMA forward products, not this scratch.
 #include "nlc_train_dev.h"
 
 namespace nlc {
@@ -172,6 +173,9 @@ __device__ __forceinline__ void quarter(double th, int k, double* c, double* cp)
 
 }  // namespace
 
+// kLinear: the fixed Talbot / Stehfest instance (a.lin_tab: nodes and weights).  Only the query points and the line integral
+// differ; the Fourier instance never reads a.lin_tab and keeps its expressions and their order
+template <bool kLinear>
 __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs a) {
   const int d = a.d, nin = a.nin, g = a.g, h = a.h, S = a.S, B = a.B;
   const int K0 = 2 * S + d + 2, O = 2 * d * S;
@@ -238,15 +242,20 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
       dhA[p] = 0.0;
     }
     __syncthreads();
-    // ---- query points s_k = gamma + i pi k / T of the row's t on the Riemann sphere (as rep_inputs_kernel)
+    // ---- query points s_k = gamma + i pi k / T (linear algorithms: node_k / t) of the row's t on the Riemann sphere (as
+    // rep_inputs_kernel)
     for (int p = threadIdx.x; p < kRows * S; p += kThreads) {
       const int r = p & (kRows - 1), k = p >> 4;
-      const double t = tn[r], Tt = scale * t;
-      const double gamma = a.alpha - a.log_tol / (scale * Tt);
-      const double im = kPi * (double)k / Tt;
-      const double a2v = gamma * gamma + im * im;
-      a0[(int64_t)r * K0 + k] = atan2(im, gamma);
-      a0[(int64_t)r * K0 + S + k] = asin((a2v - 1.0) / (a2v + 1.0));
+      if constexpr (kLinear) {
+        linear_query_point(a.lin_tab[k], a.lin_tab[S + k], tn[r], &a0[(int64_t)r * K0 + k], &a0[(int64_t)r * K0 + S + k]);
+      } else {
+        const double t = tn[r], Tt = scale * t;
+        const double gamma = a.alpha - a.log_tol / (scale * Tt);
+        const double im = kPi * (double)k / Tt;
+        const double a2v = gamma * gamma + im * im;
+        a0[(int64_t)r * K0 + k] = atan2(im, gamma);
+        a0[(int64_t)r * K0 + S + k] = asin((a2v - 1.0) / (a2v + 1.0));
+      }
     }
     // ---- reverse GRU encoder (w_nl.py:25-29), two layers
     gru_layer_fwd(a, prm + off[0], X0, nin, H0, G0);
@@ -272,9 +281,24 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
     dense_tanh(prm + off[14], prm + off[15], a2, h, O, u);
     __syncthreads();
     // ---- sphere map + Fourier line integral at the row's own t, squared error, and their backward down to the last layer's
-    // pre-activations: x = e^{gamma t} / T * sum_k w_k R_k c_k
+    // pre-activations: x = e^{gamma t} / T * sum_k w_k R_k c_k.  The linear algorithms: x = (1/t) sum_k R_k Re(W_k e^{i theta_k}),
+    // no e^{gamma t} / T and no half weight on k = 0 (nlc_train.h linear_row_sum / linear_row_bwd)
     for (int p = threadIdx.x; p < kRows * d; p += kThreads) {
       const int r = p & (kRows - 1), c = p >> 4;
+      if constexpr (kLinear) {
+        const double t = tn[r];
+        const double* wr = a.lin_tab + 2 * S;
+        const double* wi = a.lin_tab + 3 * S;
+        const double* yt = u + (int64_t)r * O + c * S;
+        const double* yp = u + (int64_t)r * O + (d + c) * S;
+        const double pred = linear_row_sum(yt, yp, wr, wi, S) / t;
+        const bool valid = row0 + r < a.N;
+        const double diff = pred - tgt[r * d + c];
+        sq[r * d + c] = valid ? diff * diff : 0.0;
+        const double gs = valid ? (loss_norm * diff) / t : 0.0;
+        linear_row_bwd(gs, yt, yp, wr, wi, S, d3 + (int64_t)r * O + c * S, d3 + (int64_t)r * O + (d + c) * S);
+        continue;
+      }
       const double t = tn[r], Tt = scale * t;
       const double gamma = a.alpha - a.log_tol / (scale * Tt);
       const double srow = exp(gamma * t) / Tt;
@@ -445,7 +469,8 @@ __global__ __launch_bounds__(kThreads) void train_adam_kernel(const AdamArgs a) 
 }
 
 hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, int M, hipStream_t s) {
-  hipLaunchKernelGGL(train_fwd_bwd_kernel, dim3(nblk, M), dim3(kThreads), 0, s, a);
+  const auto kernel = a.lin_tab ? train_fwd_bwd_kernel<true> : train_fwd_bwd_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(nblk, M), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_train_reduce(const ReduceArgs& a, int M, hipStream_t s) {

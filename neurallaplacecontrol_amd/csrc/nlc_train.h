@@ -52,6 +52,53 @@ NLC_HD void ilt_term_bwd(double g, double wk, double R, double c, double c_prime
   *d_phi = (g * wk) * c * (0.5 * (1.0 + R * R));
 }
 
+// ---- the linear algorithms (fixed Talbot, Stehfest: fixed nodes delta_k and weights W_k, s_k = delta_k / t):
+// x = (1/t) sum_k Re(W_k F_k) with F_k = R_k e^{i theta_k}, so a term is R_k c_k with
+// c_k = W_re cos(theta) - W_im sin(theta) in place of the Fourier series' quarter turn, and c'_k = d c_k / d theta.
+// ilt_term_bwd with w_k = 1 and g = dL/dx / t gives the term's gradients.
+NLC_HD void linear_phase(double th, double wr, double wi, double* c, double* c_prime) {
+  double sn, cs;
+#if defined(__HIP_DEVICE_COMPILE__)
+  sincos(th, &sn, &cs);
+#else
+  sn = sin(th);
+  cs = cos(th);
+#endif
+  *c = wr * cs - wi * sn;
+  *c_prime = -wr * sn - wi * cs;
+}
+// R = |F| of the sphere point at latitude phi (both ILT families)
+NLC_HD double sphere_radius(double phi) { return tan(phi / 2.0 + kPiT / 4.0); }
+// a row's line integral sum_k R_k c_k over the S terms of one state dim (yt / yp: the tanh outputs behind theta / phi;
+// wr / wi: the weight tables); the prediction is this over t
+NLC_HD double linear_row_sum(const double* yt, const double* yp, const double* wr, const double* wi, int S) {
+  double acc = 0.0;
+  for (int k = 0; k < S; ++k) {
+    double cv, cp;
+    linear_phase(sphere_theta(yt[k]), wr[k], wi[k], &cv, &cp);
+    acc += sphere_radius(sphere_phi(yp[k])) * cv;
+  }
+  return acc;
+}
+// its backward down to the last layer's pre-activations: g = dL/dx / t -> dt[k], dp[k]
+NLC_HD void linear_row_bwd(double g, const double* yt, const double* yp, const double* wr, const double* wi, int S, double* dt,
+                           double* dp) {
+  for (int k = 0; k < S; ++k) {
+    double cv, cp, gth, gph;
+    linear_phase(sphere_theta(yt[k]), wr[k], wi[k], &cv, &cp);
+    ilt_term_bwd(g, 1.0, sphere_radius(sphere_phi(yp[k])), cv, cp, &gth, &gph);
+    dt[k] = sphere_theta_bwd(gth, yt[k]);
+    dp[k] = sphere_phi_bwd(gph, yp[k]);
+  }
+}
+// the query point s = delta / t of a linear algorithm on the Riemann sphere (as rep_inputs_kernel's linear branch)
+NLC_HD void linear_query_point(double node_re, double node_im, double t, double* theta_s, double* phi_s) {
+  const double sr = node_re / t, si = node_im / t;
+  const double a2v = sr * sr + si * si;
+  *theta_s = atan2(si, sr);
+  *phi_s = asin((a2v - 1.0) / (a2v + 1.0));
+}
+
 // ---- clip_grad_norm_: coefficient the gradients are multiplied by (NaN total -> NaN, as torch.clamp propagates it)
 NLC_HD double clip_coef(double max_norm, double total_norm) {
   const double c = max_norm / (total_norm + 1e-6);
@@ -245,6 +292,9 @@ struct TrainArgs {
   double* act;        // [gridDim.x][A]
   int64_t off[kTensors + 1];
   GroupStrides gs;    // params, partial / tile_loss / act, idx and the dataset pointers above are member 0's
+  // fixed Talbot / Stehfest: the device tables [node_re | node_im | W_re | W_im], S doubles each, shared by every member;
+  // NULL: the Fourier series (alpha, log_tol).  Selects the kernel instance
+  const double* lin_tab;
 };
 
 struct ReduceArgs {

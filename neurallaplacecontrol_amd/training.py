@@ -8,7 +8,7 @@
 a fixed-order reduction of the tile gradients, clip + Adam.  No host synchronisation inside, so ``run()`` walks a whole
 permutation with the weights, Adam moments and per-iteration losses on the device.
 
-Models the kernels do not take (de Hoog / fixed Talbot / Stehfest, widths other than 64 / 128 / 256, ...) train through
+Models the kernels do not take (de Hoog, widths other than 64 / 128 / 256, ...) train through
 the reference's op sequence -- the model's grad-mode forward + ``clip_grad_norm_`` + ``torch.optim.Adam`` -- from
 construction on, with one warning.  A fused trainer sends a single call the library refuses (a window longer than 16, a
 model setting changed to one the kernels do not take) through the same op sequence, on the trainer's own Adam state, also
@@ -541,13 +541,16 @@ class _Group:
 
 class NLTrainer(_FusedTrainer):
     """``tr = NLTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)`` for a
-    ``NeuralLaplaceModel``; the fused step takes Fourier models (``nlc_train_group_step``, M = 1)."""
+    ``NeuralLaplaceModel``; the fused step takes Fourier, fixed Talbot and Stehfest models (``nlc_train_group_step``,
+    M = 1).  ``model.ilt_algorithm`` may change on a live trainer: among those three the next call runs the other kernel
+    instance; set to ``"dehoog"`` the calls take the per-call grad-mode path on the trainer's Adam state."""
 
     _entries = ("nlc_train_group_workspace_bytes", "nlc_train_group_loss_grad", "nlc_train_group_step")
 
     def _unsupported(self, model):
-        if model.ilt_algorithm != "fourier":
-            return f"ilt_algorithm {model.ilt_algorithm!r} has no fused training kernels (fourier only)"
+        if model.ilt_algorithm not in ("fourier", "fixed_tablot", "stehfest"):
+            return (f"ilt_algorithm {model.ilt_algorithm!r} has no fused training kernels (fourier, fixed_tablot and "
+                    "stehfest have)")
         return None
 
 

@@ -10,7 +10,9 @@ Every variant runs a warm-up first and every timing ends with torch.cuda.synchro
 ratios (b) / (a), (c) / (a) at each batch size.  `--only run --run-iters 200` is the shape for a rocprofv3 kernel trace.
 Each (batch size, variant) measurement is a child process of its own under --step-timeout seconds; the first one that fails or
 runs out of time ends the tool (nothing more is started on the GPU).  `--kernel-ms` adds the mean time of each kernel of the
-fused step from the library's event profiling (200 step()s).
+fused step from the library's event profiling (200 step()s).  `--ilt-algorithm fixed_tablot|stehfest` (with `--terms S`)
+times the NL model under one of the linear ILT algorithms instead of the Fourier series; the grad-mode reference (a) is then
+that algorithm's grad-mode path, and the result records both settings.
 
 `--group M [M ...]` measures grouped training instead (NLTrainerGroup / RNNTrainerGroup, run_exp_multi.py:105-110): for both
 families and every M, run() of a group of M differently seeded models at the first --batches size (16) over one shared
@@ -22,7 +24,7 @@ own `tools/train_bench.py --only run` --repeats times per family between this co
 records `parent_single`, `m1_over_parent` (M = 1 of this commit against it) and `aggregate_over_parent` per M.  Writes
 profiles/train_bench_group.json unless --out says otherwise.
 
-    python tools/train_bench.py [--model nl|delta_t_rnn] [--batches 16 256] [--ref-iters 200] [--step-iters 1000] [--run-iters 10000] [--out FILE]
+    python tools/train_bench.py [--model nl|delta_t_rnn] [--ilt-algorithm fourier] [--terms 17] [--batches 16 256] [--ref-iters 200] [--step-iters 1000] [--run-iters 10000] [--out FILE]
     python tools/train_bench.py --group 1 8 64 256 [--repeats 3] [--run-iters 10000] [--parent-tree DIR]
 """
 
@@ -45,12 +47,15 @@ from oracle import nl_model as onl  # noqa: E402
 ENV, D, NU, H, S, B = "oderl-cartpole", 5, 1, 128, 17, 4
 RNN_H = 160  # rnn_hidden_units, config.py:43
 MODEL = "nl"
+ILT = "fourier"  # --ilt-algorithm (NL model)
 WORKLOADS = {"nl": "NeuralLaplaceModel training step, cartpole d=5 h=128 S=17 B=4, float64",
              "delta_t_rnn": "DeltaTRNN training step, cartpole d=5 H=160 B=4, float64"}
 
 
 def make_trainer(model):
-    return nlc.RNNTrainer(model) if MODEL == "delta_t_rnn" else nlc.NLTrainer(model)
+    tr = nlc.RNNTrainer(model) if MODEL == "delta_t_rnn" else nlc.NLTrainer(model)
+    assert tr.fused, "the benchmark times the fused step"
+    return tr
 
 
 def make_model(seed=0):
@@ -64,7 +69,7 @@ def make_model(seed=0):
         m.load_state_dict(sd)
         return m.to("cuda")
     sd = onl.make_synthetic_state_dict(seed, D, NU, H, S, st["state_std"], [st["act_high"] / 2], tame=True)
-    m = nlc.NeuralLaplaceModel(D, NU, D, hidden_units=H, s_recon_terms=S, ilt_algorithm="fourier", state_mean=np.zeros(D),
+    m = nlc.NeuralLaplaceModel(D, NU, D, hidden_units=H, s_recon_terms=S, ilt_algorithm=ILT, state_mean=np.zeros(D),
                                state_std=np.ones(D), action_mean=np.array([0]), action_std=np.array([1.0]), normalize=True,
                                normalize_time=True).double()
     m.load_state_dict(sd)
@@ -199,6 +204,7 @@ def flops_per_iter(bs):
 
 
 def main():
+    global MODEL, ILT, S
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 256])
     ap.add_argument("--ref-iters", type=int, default=200)
@@ -208,6 +214,9 @@ def main():
     ap.add_argument("--only", choices=["ref", "step", "run"], default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--model", choices=sorted(WORKLOADS), default="nl")
+    ap.add_argument("--ilt-algorithm", choices=["fourier", "fixed_tablot", "stehfest"], default="fourier",
+                    help="--model nl: the ILT algorithm of the model (the fused step has an instance for each of these)")
+    ap.add_argument("--terms", type=int, default=S, help="--model nl: ilt_reconstruction_terms (stehfest: even, 2 .. 20)")
     ap.add_argument("--kernel-ms", action="store_true")
     ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds each child measurement may take")
     ap.add_argument("--group", type=int, nargs="+", default=None, metavar="M", help="grouped training: members per group")
@@ -215,8 +224,9 @@ def main():
     ap.add_argument("--parent-tree", default=None, help="--group: a built checkout of the parent commit to time beside this one")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    global MODEL
-    MODEL = args.model
+    MODEL, ILT, S = args.model, args.ilt_algorithm, args.terms
+    if MODEL == "nl" and (ILT, S) != ("fourier", 17):
+        WORKLOADS["nl"] = f"NeuralLaplaceModel training step, cartpole d=5 h=128 {ILT} S={S} B=4, float64"
     torch.manual_seed(0)
     if args.child:
         bs, variant = int(args.child[0]), args.child[1]
@@ -229,7 +239,8 @@ def main():
         return
 
     def measure(bs, variant):
-        cmd = [sys.executable, os.path.abspath(__file__), "--model", MODEL, "--ref-iters", str(args.ref_iters), "--step-iters",
+        cmd = [sys.executable, os.path.abspath(__file__), "--model", MODEL, "--ilt-algorithm", ILT, "--terms", str(S),
+               "--ref-iters", str(args.ref_iters), "--step-iters",
                str(args.step_iters), "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--repeats",
                str(args.repeats), "--child", str(bs), variant]
         out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
@@ -280,6 +291,8 @@ def main():
         return
 
     res = {"workload": WORKLOADS[MODEL], "device": torch.cuda.get_device_name(0), "batches": {}}
+    if MODEL == "nl":
+        res["ilt_algorithm"], res["terms"] = ILT, S
     for bs in args.batches:
         r = {"flops_per_iter": flops_per_iter(bs)}
         if args.only in (None, "ref"):
