@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 15
+#define NLC_ABI_VERSION 16
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -353,6 +353,29 @@ int nlc_train_group_step(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_
                          const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
                          double* loss_dev, double* gradnorm_dev, void* ws_dev);
 
+/* ---- held-out loss: the forward and MSE of the reference's validation loss (overlay.py:112-115
+ *      get_val_loss_delay_precomputed; :175-177: model(s0, a0, ts), then the loss) on the data conventions of the training
+ *      entries above, with no backward, no update and no (N, d) prediction.  loss_dev [M] = mean squared error of member m over
+ *      its N rows; idx_dev [M][N] as for a step, or NULL: every member takes rows 0 .. N - 1.  Contract and host-side refusals
+ *      of nlc_train_group_loss_grad (de Hoog and B > 16: NLC_ERR_UNSUPPORTED; N < 1, M < 1, data_row_stride < 0:
+ *      NLC_ERR_BAD_SHAPE; M > 65535: NLC_ERR_UNSUPPORTED; no model: NLC_ERR_STATE), all before any launch.
+ *   ws_dev: nlc_train_group_eval_workspace_bytes(ctx, M, N): the tile losses only, M regions of ceil(N / 16) doubles, each
+ *   rounded up to a multiple of 256 bytes.  Asynchronous on the ctx's stream; no floating-point atomics: a member's loss does
+ *   not depend on the grid, on M or on its neighbours; the single entries are the M = 1, stride 0 case. */
+/* overlay.py:112-115, :175-177, run_exp_multi.py:105-110 */
+int64_t nlc_train_group_eval_workspace_bytes(nlc_ctx* ctx, int M, int64_t N);
+/* overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110 */
+int nlc_train_group_eval(nlc_ctx* ctx, int M, int64_t data_row_stride, const double* params_dev, const double* obs_dev,
+                         const double* window_dev, const double* ts_dev, const double* target_dev,
+                         const int64_t* idx_dev /* NULL: rows 0..N-1 */, int64_t N, int B, double* loss_dev /* [M] */,
+                         void* ws_dev);
+/* overlay.py:112-115, :175-177 */
+int64_t nlc_train_eval_workspace_bytes(nlc_ctx* ctx, int64_t N);
+/* overlay.py:112-115, :175-177 */
+int nlc_train_eval(nlc_ctx* ctx, const double* params_dev, const double* obs_dev, const double* window_dev,
+                   const double* ts_dev, const double* target_dev, const int64_t* idx_dev /* NULL: rows 0..N-1 */, int64_t N,
+                   int B, double* loss_dev, void* ws_dev);
+
 /* ---- baseline models: DeltaTRNN (train_utils.py:589-631; factory :56-74) and RNN (:550-586; factory :77-98);
  *      rnn_hidden_units config.py:43 ------
  * out, _ = GRU(nin -> hidden, 1 layer, batch_first)(window_n); dx = linear_out(cat(out[:, -1], obs_n, ts_n)). */
@@ -407,6 +430,22 @@ int nlc_rnn_train_group_step(nlc_ctx* ctx, const nlc_train_desc* desc, int M, in
                              double* m_dev, double* v_dev, int64_t step, const double* obs_dev, const double* window_dev,
                              const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
                              double* loss_dev, double* gradnorm_dev, void* ws_dev);
+
+/* held-out loss of these two models: layout and contract of nlc_train_group_eval above (P = nlc_rnn_blob_size; ts_dev may be
+ * NULL for a model without time input) */
+/* overlay.py:112-115, :175-177, run_exp_multi.py:105-110 */
+int64_t nlc_rnn_train_group_eval_workspace_bytes(nlc_ctx* ctx, int M, int64_t N);
+/* overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110 */
+int nlc_rnn_train_group_eval(nlc_ctx* ctx, int M, int64_t data_row_stride, const double* params_dev, const double* obs_dev,
+                             const double* window_dev, const double* ts_dev, const double* target_dev,
+                             const int64_t* idx_dev /* NULL: rows 0..N-1 */, int64_t N, int B, double* loss_dev /* [M] */,
+                             void* ws_dev);
+/* overlay.py:112-115, :175-177 */
+int64_t nlc_rnn_train_eval_workspace_bytes(nlc_ctx* ctx, int64_t N);
+/* overlay.py:112-115, :175-177 */
+int nlc_rnn_train_eval(nlc_ctx* ctx, const double* params_dev, const double* obs_dev, const double* window_dev,
+                       const double* ts_dev, const double* target_dev, const int64_t* idx_dev /* NULL: rows 0..N-1 */,
+                       int64_t N, int B, double* loss_dev, void* ws_dev);
 
 /* ---- baseline model: NODE (train_utils.py:664-724; ODE function xOdeFuncInXAndU :637-661; factory :101-125;
  * node_hidden_units 270, node_augment_dim 1, node_method "euler": config.py:40-42).

@@ -66,6 +66,10 @@ SYMBOLS = [
     "nlc_train_group_workspace_bytes",
     "nlc_train_group_loss_grad",
     "nlc_train_group_step",
+    "nlc_train_group_eval_workspace_bytes",
+    "nlc_train_group_eval",
+    "nlc_train_eval_workspace_bytes",
+    "nlc_train_eval",
     "nlc_rnn_blob_size",
     "nlc_set_rnn_model",
     "nlc_rnn_forward",
@@ -75,6 +79,10 @@ SYMBOLS = [
     "nlc_rnn_train_group_workspace_bytes",
     "nlc_rnn_train_group_loss_grad",
     "nlc_rnn_train_group_step",
+    "nlc_rnn_train_group_eval_workspace_bytes",
+    "nlc_rnn_train_group_eval",
+    "nlc_rnn_train_eval_workspace_bytes",
+    "nlc_rnn_train_eval",
     "nlc_node_blob_size",
     "nlc_set_node_model",
     "nlc_node_forward",
@@ -299,6 +307,14 @@ def load_library():
         lib.nlc_rnn_train_group_workspace_bytes.restype = i64
         lib.nlc_rnn_train_group_loss_grad.argtypes = lib.nlc_train_group_loss_grad.argtypes
         lib.nlc_rnn_train_group_step.argtypes = lib.nlc_train_group_step.argtypes
+        # held-out loss: loss_grad's arguments without grad
+        for fam in ("nlc_train", "nlc_rnn_train"):
+            getattr(lib, fam + "_eval_workspace_bytes").argtypes = [vp, i64]
+            getattr(lib, fam + "_eval_workspace_bytes").restype = i64
+            getattr(lib, fam + "_eval").argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]
+            getattr(lib, fam + "_group_eval_workspace_bytes").argtypes = [vp, i32, i64]
+            getattr(lib, fam + "_group_eval_workspace_bytes").restype = i64
+            getattr(lib, fam + "_group_eval").argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]
         lib.nlc_rnn_blob_size.restype = i64
         lib.nlc_set_rnn_model.argtypes = [vp, P(RnnDesc), vp, i64]

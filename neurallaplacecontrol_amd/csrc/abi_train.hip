@@ -8,6 +8,7 @@
 
 #include "nlc_host.h"
 #include "nlc_train.h"
+#include "nlc_train_eval.h"
 
 using namespace nlc;
 using namespace nlc::host;
@@ -289,6 +290,107 @@ int group_step_entry(nlc_ctx* c, bool rnn, const nlc_train_desc* desc, int M, in
   NLC_GUARD_END(c)
 }
 
+// ---- held-out loss (kernels_train_eval.hip): the forward and the squared error of every member, then one reduction.  The
+// checks are group_loss_grad's, in its order; idx may be NULL (rows 0 .. N - 1).  The workspace is the tile losses
+// (nlc_train_eval.h eval_ws_layout), M regions back to back
+int64_t group_eval_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
+  if (!c || !(rnn ? c->has_rnn : c->has_model) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+  return (int64_t)M * eval_ws_layout(N).total * (int64_t)sizeof(double);
+}
+
+template <class Args>
+void fill_eval(Args& a, int B, const double* params, const double* obs, const double* window, const double* ts,
+               const double* target, const int64_t* idx, int64_t N, int64_t P, int64_t data_rows, const EvalWsLayout& w,
+               void* ws) {
+  a.B = B;
+  a.params = params;
+  a.obs = obs;
+  a.window = window;
+  a.ts = ts;
+  a.target = target;
+  a.idx = idx;
+  a.N = N;
+  a.ntiles = w.ntiles;
+  a.tile_loss = (double*)ws + w.tile_loss;
+  a.gs = GroupStrides{P, w.total, 0, N, data_rows};
+}
+
+int group_eval_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
+                     const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
+                     double* loss, void* ws) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  NLC_GUARD_BEGIN
+  if (int rc = rnn ? check_rnn_train(c, N, B) : check_train(c, N, B)) return rc;
+  if (int rc = check_group(c, M, data_rows)) return rc;
+  const bool need_ts = rnn ? c->rd.time_input != 0 : true;
+  if (!params || !obs || !window || (!ts && need_ts) || !target || !loss || !ws)
+    return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
+  NLC_HIP(c, hipSetDevice(c->device));
+  const EvalWsLayout w = eval_ws_layout(N);
+  const int cus = c->prop.multiProcessorCount;
+  int64_t off[kTensors + 1];
+  int d;
+  if (rnn) {
+    const nlc_rnn_desc& rd = c->rd;
+    d = rd.d;
+    RnnEvalArgs a{};
+    rnn_blob_offsets(rd.d, rd.nin, rd.hidden, rd.time_input, off);
+    fill_eval(a, B, params, obs, window, ts, target, idx, N, off[kTensors], data_rows, w, ws);
+    a.d = rd.d;
+    a.nin = rd.nin;
+    a.time_input = rd.time_input;
+    a.time_div = rd.time_div;
+    for (int i = 0; i < rd.d; ++i) {
+      a.sm[i] = rd.state_mean[i];
+      a.ss[i] = rd.state_std[i];
+    }
+    for (int i = 0; i < rd.nin; ++i) {
+      a.am[i] = rd.action_mean[i];
+      a.as[i] = rd.action_std[i];
+    }
+    for (int i = 0; i <= kRnnTensors; ++i) a.off[i] = off[i];
+    const int per_cu = eval_per_cu(rnn_eval_lds_doubles(rd.hidden) * (int64_t)sizeof(double));
+    ProfScope ps(c, "rnn_eval_kernel");
+    NLC_HIP(c, launch_rnn_eval(a, rd.hidden, eval_grid(w.ntiles, cus, per_cu, M), M, c->stream));
+  } else {
+    const nlc_model_desc& md = c->md;
+    d = md.d;
+    const int g = md.h / 2, S = md.ilt.terms;
+    EvalArgs a{};
+    blob_offsets(md.d, md.nin, g, md.h, S, off);
+    fill_eval(a, B, params, obs, window, ts, target, idx, N, off[kTensors], data_rows, w, ws);
+    a.d = md.d;
+    a.nin = md.nin;
+    a.g = g;
+    a.h = md.h;
+    a.S = S;
+    a.time_div = md.time_div;
+    a.alpha = md.ilt.alpha;
+    a.log_tol = std::log(md.ilt.tol);
+    // one table for all members of a group (they share the descriptor); NULL selects the Fourier instance
+    if (linear_ilt(md.ilt))
+      if (int rc = linear_tables(c, &md.ilt, &a.lin_tab)) return rc;
+    for (int i = 0; i < md.d; ++i) {
+      a.sm[i] = md.state_mean[i];
+      a.ss[i] = md.state_std[i];
+    }
+    for (int i = 0; i < md.nin; ++i) {
+      a.am[i] = md.action_mean[i];
+      a.as[i] = md.action_std[i];
+    }
+    a.L = eval_lds_layout(md.d, md.nin, g, md.h, S, B);
+    for (int i = 0; i <= kTensors; ++i) a.off[i] = off[i];
+    // one workgroup per compute unit: the kernel's registers leave room for one wave per SIMD, whatever its LDS
+    ProfScope ps(c, "train_eval_kernel");
+    NLC_HIP(c, launch_train_eval(a, eval_grid(w.ntiles, cus, 1, M), M, c->stream));
+  }
+  EvalReduceArgs r{(const double*)ws + w.tile_loss, w.ntiles, N, w.total, d, loss};
+  ProfScope ps(c, "eval_reduce_kernel");
+  NLC_HIP(c, launch_eval_reduce(r, M, c->stream));
+  return NLC_OK;
+  NLC_GUARD_END(c)
+}
+
 }  // namespace
 
 // ---- NeuralLaplaceModel.  A group (run_exp_multi.py:105-110: one model per (env, delay, model_name), times seeds) is M
@@ -362,4 +464,41 @@ extern "C" int nlc_rnn_train_step(nlc_ctx* c, const nlc_train_desc* desc, double
                                   const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm,
                                   void* ws) {
   return group_step_entry(c, true, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
+}
+
+// ---- held-out loss of both families: the forward and MSE of the reference's validation loss on the training entries' data
+// conventions; no gradient, no update.  loss [M]; idx may be NULL (rows 0 .. N - 1)
+// overlay.py:112-115, :175-177, run_exp_multi.py:105-110
+extern "C" int64_t nlc_train_group_eval_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
+  return group_eval_workspace_bytes(c, false, M, N);
+}
+// overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110
+extern "C" int nlc_train_group_eval(nlc_ctx* c, int M, int64_t data_row_stride, const double* params, const double* obs,
+                                    const double* window, const double* ts, const double* target, const int64_t* idx,
+                                    int64_t N, int B, double* loss, void* ws) {
+  return group_eval_entry(c, false, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws);
+}
+// overlay.py:112-115, :175-177
+extern "C" int64_t nlc_train_eval_workspace_bytes(nlc_ctx* c, int64_t N) { return group_eval_workspace_bytes(c, false, 1, N); }
+// overlay.py:112-115, :175-177
+extern "C" int nlc_train_eval(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
+                              const double* target, const int64_t* idx, int64_t N, int B, double* loss, void* ws) {
+  return group_eval_entry(c, false, 1, 0, params, obs, window, ts, target, idx, N, B, loss, ws);
+}
+// overlay.py:112-115, :175-177, run_exp_multi.py:105-110
+extern "C" int64_t nlc_rnn_train_group_eval_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
+  return group_eval_workspace_bytes(c, true, M, N);
+}
+// overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110
+extern "C" int nlc_rnn_train_group_eval(nlc_ctx* c, int M, int64_t data_row_stride, const double* params, const double* obs,
+                                        const double* window, const double* ts, const double* target, const int64_t* idx,
+                                        int64_t N, int B, double* loss, void* ws) {
+  return group_eval_entry(c, true, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws);
+}
+// overlay.py:112-115, :175-177
+extern "C" int64_t nlc_rnn_train_eval_workspace_bytes(nlc_ctx* c, int64_t N) { return group_eval_workspace_bytes(c, true, 1, N); }
+// overlay.py:112-115, :175-177
+extern "C" int nlc_rnn_train_eval(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
+                                  const double* target, const int64_t* idx, int64_t N, int B, double* loss, void* ws) {
+  return group_eval_entry(c, true, 1, 0, params, obs, window, ts, target, idx, N, B, loss, ws);
 }

@@ -54,6 +54,8 @@ class _FusedTrainer:
     * ``tr.step(bs0, ba0, bts, bsd)`` -- one reference iteration (loss, backward, clip, Adam); the loss BEFORE the update;
     * ``tr.run(s0, a0, sn, ts, permutation, batch_size=16)`` -- every full batch of ``permutation`` (``bsd = sn - s0``) on the
       device, one loss per iteration;
+    * ``tr.evaluate(s0, a0, ts, target, indices=None)`` -- the held-out loss (overlay.py:112-115): forward and MSE only, on
+      the current weights; touches no gradient, moment or parameter;
     * ``tr.state_dict()`` / ``tr.load_state_dict(sd)`` -- ``torch.optim.Adam``'s format.
 
     ``tr.lr`` may change between calls (what a ``StepLR`` would do).  After ``step()`` / ``run()`` the model's parameters
@@ -65,6 +67,7 @@ class _FusedTrainer:
     ``(M, P)`` buffers, losses ``(M,)``, and every library call is the group entry with its M."""
 
     _entries = None  # the library's group (workspace_bytes, loss_grad, step) of the model family
+    _eval_entries = None  # its (eval_workspace_bytes, eval): the forward-only held-out loss
     _reads_ts = True  # False: the model ignores ts_pred, and the kernels get no ts pointer (a property where it varies)
     _grouped = False  # True: calls take / return the leading M (the group classes)
 
@@ -112,6 +115,7 @@ class _FusedTrainer:
         self._v = torch.zeros(M, P, dtype=torch.float64, device=self._dev)
         self._step = 0
         self._ws = {}
+        self._eval_ws = {}
         self._arange = {}
         self._warned = False
 
@@ -302,6 +306,62 @@ class _FusedTrainer:
             for p, g in zip(ps, self._views(grad, i)):
                 p.grad = g
         return self._out(loss)
+
+    def evaluate(self, s0, a0, ts, target, indices=None):
+        """The held-out loss of the reference's validation (overlay.py:112-115, :175-177: ``model(s0, a0, ts)``, then the
+        MSE against ``target = sn - s0``) on the model's current weights: a 0-dim float64 device tensor, ``(M,)`` for a
+        group.  ``indices`` picks rows of the dataset -- ``(N,)``, or ``(M, N)`` in a group -- without a gather copy;
+        None takes every row.  Forward only (``nlc_train_group_eval``): no ``p.grad``, no write-back, no moments, no step
+        count, no host synchronisation.  A call the fused kernels do not take runs the model's ``no_grad`` forward +
+        ``mse_loss`` instead, under the trainer's one warning."""
+        why = None if not self.fused else self._sync_model()
+        if not self.fused or why is not None:
+            if why is not None:
+                self._host_path(why)
+            return self._host_evaluate(s0, a0, ts, target, indices)
+        obs, win, tsd, tgt, rows, stride = self._group_data(s0, a0, ts, target)
+        M = self._M
+        if indices is None:
+            idx, N = None, rows
+        else:
+            idx = torch.as_tensor(indices).to(self._dev, torch.int64)
+            if idx.dim() == 1:
+                idx = idx.unsqueeze(0).expand(M, -1)
+            elif not (self._grouped and idx.dim() == 2 and idx.shape[0] == M):
+                raise ValueError(f"{self._name}.evaluate: indices must be (N,)" + (f" or ({M}, N)" if self._grouped else ""))
+            idx, N = idx.contiguous(), int(idx.shape[1])
+        ws = self._eval_ws.get(N)
+        if ws is None:
+            n = getattr(self._ctx.lib, self._eval_entries[0])(self._ctx.h, M, N)
+            if n < 0:
+                raise _lib.NlcError(n, self._eval_entries[0])
+            ws = self._eval_ws[N] = torch.empty((n + 7) // 8, dtype=torch.float64, device=self._dev)
+        self._gather()
+        loss = torch.empty(M, dtype=torch.float64, device=self._dev)
+        ctx = self._ctx
+        with ctx.stream():
+            rc = getattr(ctx.lib, self._eval_entries[1])(
+                ctx.h, M, stride, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(tsd), _f64_ptr(tgt),
+                C.c_void_p(0) if idx is None else _i64_ptr(idx), N, win.shape[1], _f64_ptr(loss), _f64_ptr(ws))
+        why = self._refused(rc)
+        if why is not None:
+            self._host_path(why)
+            return self._host_evaluate(s0, a0, ts, target, indices)
+        return self._out(loss)
+
+    def _host_evaluate(self, s0, a0, ts, target, indices):
+        self._check_members()
+        stacked = self._stacked(s0)
+        ind = None if indices is None else torch.as_tensor(indices).to(self._dev, torch.int64)
+        out = []
+        with torch.no_grad():
+            for i in range(self._M):
+                data = [torch.as_tensor(t).to(self._dev) for t in self._member_data(i, stacked, s0, a0, ts, target)]
+                if ind is not None:
+                    mine = ind if ind.dim() == 1 else ind[i]
+                    data = [t[mine] for t in data]
+                out.append(self._ref_loss(*data, i=i).detach())
+        return self._out(torch.stack(out))
 
     def step(self, bs0, ba0, bts, bsd):
         """One iteration of the reference's loop (train_utils.py:391-404); returns the loss before the update."""
@@ -546,6 +606,7 @@ class NLTrainer(_FusedTrainer):
     instance; set to ``"dehoog"`` the calls take the per-call grad-mode path on the trainer's Adam state."""
 
     _entries = ("nlc_train_group_workspace_bytes", "nlc_train_group_loss_grad", "nlc_train_group_step")
+    _eval_entries = ("nlc_train_group_eval_workspace_bytes", "nlc_train_group_eval")
 
     def _unsupported(self, model):
         if model.ilt_algorithm not in ("fourier", "fixed_tablot", "stehfest"):
@@ -560,6 +621,7 @@ class RNNTrainer(_FusedTrainer):
     ``RNN`` ignores ``ts`` as its forward does; the reference's loop still passes it, so every method accepts it."""
 
     _entries = ("nlc_rnn_train_group_workspace_bytes", "nlc_rnn_train_group_loss_grad", "nlc_rnn_train_group_step")
+    _eval_entries = ("nlc_rnn_train_group_eval_workspace_bytes", "nlc_rnn_train_group_eval")
 
     @property
     def _reads_ts(self):

@@ -26,6 +26,15 @@ profiles/train_bench_group.json unless --out says otherwise.
 
     python tools/train_bench.py [--model nl|delta_t_rnn] [--ilt-algorithm fourier] [--terms 17] [--batches 16 256] [--ref-iters 200] [--step-iters 1000] [--run-iters 10000] [--out FILE]
     python tools/train_bench.py --group 1 8 64 256 [--repeats 3] [--run-iters 10000] [--parent-tree DIR]
+
+`--evaluate` times the held-out loss instead (``evaluate``, overlay.py:112-115): both families at N = 256 and N = 156 250 (the
+reference's validation set at samples_per_dim = 5: 50 x 5 x 5^4 rows), one warm-up and --repeats timed calls each (median
+and min .. max, ms), beside (a) ``loss_and_grad`` on the same rows, (b) ``model(...)`` under ``no_grad`` + ``mse_loss`` after a
+parameter change (so the inference path's weight re-upload is inside), and (c) for groups of --group members (default 1 8
+64) at N = 256, the group's one ``evaluate`` against the loop of M single calls.  One child process per family under
+--step-timeout; writes profiles/train_eval_bench.json unless --out says otherwise.
+
+    python tools/train_bench.py --evaluate [--group 1 8 64] [--repeats 3]
 """
 
 import argparse
@@ -190,6 +199,50 @@ def kernel_ms(bs, iters=200, warm=20):
     return out
 
 
+def _timed(fn, repeats):
+    """One warm-up, then `repeats` timed calls, each ended by a synchronise: median, min and max in ms."""
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    ms.sort()
+    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+
+
+def time_evaluate(sizes, groups, repeats):
+    """The --evaluate measurements of the family MODEL names."""
+    Single, Group = (nlc.RNNTrainer, nlc.RNNTrainerGroup) if MODEL == "delta_t_rnn" else (nlc.NLTrainer, nlc.NLTrainerGroup)
+    res = {"workload": WORKLOADS[MODEL].replace("training step", "held-out loss"), "sizes": {}, "groups": {}}
+    model = make_model()
+    tr = make_trainer(model)
+    first = next(model.parameters())
+    for N in sizes:
+        s0, a0, sn, ts = dataset(N)
+        tgt = sn - s0
+
+        def forward_after_a_change():
+            with torch.no_grad():
+                first.mul_(1.0)  # the version moves: the inference path packs and uploads the weights again
+                return torch.nn.functional.mse_loss(model(s0, a0, ts).squeeze(), tgt.squeeze())
+
+        res["sizes"][str(N)] = {"evaluate": _timed(lambda: tr.evaluate(s0, a0, ts, tgt), repeats),
+                                "loss_and_grad": _timed(lambda: tr.loss_and_grad(s0, a0, ts, tgt), repeats),
+                                "no_grad_forward_mse": _timed(forward_after_a_change, repeats)}
+    s0, a0, sn, ts = dataset(sizes[0])
+    tgt = sn - s0
+    for M in groups:
+        models = [make_model(seed=i) for i in range(M)]
+        grp = Group(models)
+        singles = [Single(m) for m in models]
+        res["groups"][str(M)] = {"N": sizes[0], "group_evaluate": _timed(lambda: grp.evaluate(s0, a0, ts, tgt), repeats),
+                                 "loop_of_singles": _timed(lambda: [t.evaluate(s0, a0, ts, tgt) for t in singles], repeats)}
+    return res
+
+
 def flops_per_iter(bs):
     """Multiply-adds x 2 of the dense products (forward + the two backward products per weight matrix); transcendentals
     and element-wise work not counted."""
@@ -222,6 +275,8 @@ def main():
     ap.add_argument("--group", type=int, nargs="+", default=None, metavar="M", help="grouped training: members per group")
     ap.add_argument("--repeats", type=int, default=3, help="timed runs per --group measurement")
     ap.add_argument("--parent-tree", default=None, help="--group: a built checkout of the parent commit to time beside this one")
+    ap.add_argument("--evaluate", action="store_true", help="time the held-out loss (evaluate) instead of training")
+    ap.add_argument("--eval-sizes", type=int, nargs="+", default=[256, 156250], help="--evaluate: rows per call")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     MODEL, ILT, S = args.model, args.ilt_algorithm, args.terms
@@ -230,6 +285,9 @@ def main():
     torch.manual_seed(0)
     if args.child:
         bs, variant = int(args.child[0]), args.child[1]
+        if variant == "evaluate":
+            print("RESULT " + json.dumps(time_evaluate(args.eval_sizes, args.group or [1, 8, 64], args.repeats)))
+            return
         if variant.startswith("group"):
             print("RESULT " + json.dumps(time_group(bs, args.run_iters, args.warmup, int(variant[5:]), args.repeats)))
             return
@@ -261,6 +319,18 @@ def main():
             runs.append(json.loads(out.splitlines()[-1])["batches"][str(bs)]["run_it_s"])
         return spread(runs)
 
+    if args.evaluate:
+        res = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats}
+        for fam in ("nl", "delta_t_rnn"):
+            cmd = [sys.executable, os.path.abspath(__file__), "--model", fam, "--repeats", str(args.repeats), "--eval-sizes",
+                   *map(str, args.eval_sizes), "--group", *map(str, args.group or [1, 8, 64]), "--child", "0", "evaluate"]
+            out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
+            res[fam] = json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
+        print(json.dumps(res))
+        with open(args.out or os.path.join(REPO, "profiles", "train_eval_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     if args.group:
         bs = args.batches[0]
         res = {"device": torch.cuda.get_device_name(0), "batch": bs, "run_iters": args.run_iters, "repeats": args.repeats,
