@@ -5,6 +5,7 @@
 // tensors; the workspace, the reduction and the Adam launch are written once.  Every entry is the group path: M same-shaped
 // models (run_exp_multi.py:105-110) in the same three launches, the member on the grid's y axis; a single model is M = 1.
 #include <cmath>
+#include <iterator>
 
 #include "nlc_host.h"
 #include "nlc_train.h"
@@ -73,17 +74,11 @@ WsPtrs ws_ptrs(const Plan& p, void* base) {
   return WsPtrs{b + p.ws.partial, b + p.ws.tile_loss, b + p.ws.act, b + p.ws.grad, b + p.ws.sq};
 }
 
-int check_group(nlc_ctx* c, int M, int64_t data_rows) {
-  if (M < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: a group needs M >= 1 members");
-  if (M > kMaxGroup) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: at most 65535 members in a group");
-  if (data_rows < 0) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: data_row_stride must be >= 0");
-  return NLC_OK;
-}
-
 // fixed Talbot / Stehfest: fixed nodes and weights (linear_tables), the <true> instance of train_fwd_bwd_kernel
 bool linear_ilt(const nlc_ilt_desc& ilt) { return ilt.algo == NLC_ILT_FIXED_TALBOT || ilt.algo == NLC_ILT_STEHFEST; }
 
-int check_train(nlc_ctx* c, int64_t N, int B) {
+// the NL model the kernels take: uploaded, and with one of the three ILT algorithms they are written for
+int check_nl_model(nlc_ctx* c) {
   if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
   const nlc_ilt_desc& ilt = c->md.ilt;
   if (linear_ilt(ilt)) {
@@ -96,15 +91,19 @@ int check_train(nlc_ctx* c, int64_t N, int B) {
       return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: fourier, fixed_tablot and stehfest models only");
     if (ilt.scale != 2.0) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step needs ILT scale == 2 (fourier)");
   }
-  if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
-  if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
   return NLC_OK;
 }
 
-int check_rnn_train(nlc_ctx* c, int64_t N, int B) {
-  if (!c->has_rnn) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
+// what every training and evaluation entry checks first, in this order: the family's model, the call's shape, the group
+int check_call(nlc_ctx* c, bool rnn, int M, int64_t data_rows, int64_t N, int B) {
+  if (rnn && !c->has_rnn) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
+  if (!rnn)
+    if (int rc = check_nl_model(c)) return rc;
   if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
   if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
+  if (M < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: a group needs M >= 1 members");
+  if (M > kMaxGroup) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: at most 65535 members in a group");
+  if (data_rows < 0) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: data_row_stride must be >= 0");
   return NLC_OK;
 }
 
@@ -162,79 +161,102 @@ int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, doub
   return NLC_OK;
 }
 
-// what the two families' forward + backward launches share: the batch, the plan's sizes and the workspace
-template <class Args>
-void fill_common(Args& a, int B, const double* params, const double* obs, const double* window, const double* ts,
-                 const double* target, const int64_t* idx, int64_t N, const Plan& p, const WsPtrs& w) {
+// normalisation constants of a family's descriptor (nlc_model_desc or nlc_rnn_desc); entries past d / nin stay 0
+template <class Desc>
+void fill_norm(Norm& n, const Desc& m) {
+  for (int i = 0; i < m.d; ++i) {
+    n.sm[i] = m.state_mean[i];
+    n.ss[i] = m.state_std[i];
+  }
+  for (int i = 0; i < m.nin; ++i) {
+    n.am[i] = m.action_mean[i];
+    n.as[i] = m.action_std[i];
+  }
+}
+
+// what the four forward launches (training and evaluation, both families) share: the descriptor's shape and constants, the
+// window length, the batch, and the plan's tiles, blob offsets and member strides
+template <class Args, class Desc>
+void fill_call(Args& a, const Desc& m, int B, const Batch& b, const Plan& p) {
+  a.d = m.d;
+  a.nin = m.nin;
   a.B = B;
-  a.params = params;
-  a.obs = obs;
-  a.window = window;
-  a.ts = ts;
-  a.target = target;
-  a.idx = idx;
-  a.N = N;
-  a.ntiles = (int)p.ntiles;
+  a.time_div = m.time_div;
+  fill_norm(a.norm, m);
+  a.batch = b;
+  a.ntiles = (decltype(a.ntiles))p.ntiles;
+  for (size_t i = 0; i < std::size(a.off); ++i) a.off[i] = p.off[i];
+  a.gs = p.gs;
+}
+
+// the NL model's own part of a launch: widths, the Fourier constants, or the tables of a linear algorithm
+template <class Args>
+int fill_nl(nlc_ctx* c, Args& a, const Plan& p) {
+  const nlc_model_desc& md = c->md;
+  a.g = p.g;
+  a.h = md.h;
+  a.S = p.S;
+  a.alpha = md.ilt.alpha;
+  a.log_tol = std::log(md.ilt.tol);
+  // one table for all members of a group (they share the descriptor); NULL selects the Fourier instance
+  return linear_ilt(md.ilt) ? linear_tables(c, &md.ilt, &a.lin_tab) : NLC_OK;
+}
+
+// the workspace of a forward + backward launch
+template <class Args>
+void fill_train_ws(Args& a, const Plan& p, const WsPtrs& w) {
   a.P = p.P;
   a.A = p.A;
   a.partial = w.partial;
   a.tile_loss = w.tile_loss;
   a.act = w.act;
-  a.gs = p.gs;
 }
 
-int nl_fwd_bwd(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
-               const double* target, const int64_t* idx, int64_t N, int B, const Plan& p, const WsPtrs& w) {
-  const nlc_model_desc& md = c->md;
+int nl_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w) {
   TrainArgs a{};
-  fill_common(a, B, params, obs, window, ts, target, idx, N, p, w);
-  a.d = md.d;
-  a.nin = md.nin;
-  a.g = p.g;
-  a.h = md.h;
-  a.S = p.S;
-  a.time_div = md.time_div;
-  a.alpha = md.ilt.alpha;
-  a.log_tol = std::log(md.ilt.tol);
-  // one table for all members of a group (they share the descriptor); NULL selects the Fourier instance
-  if (linear_ilt(md.ilt))
-    if (int rc = linear_tables(c, &md.ilt, &a.lin_tab)) return rc;
-  for (int i = 0; i < md.d; ++i) {
-    a.sm[i] = md.state_mean[i];
-    a.ss[i] = md.state_std[i];
-  }
-  for (int i = 0; i < md.nin; ++i) {
-    a.am[i] = md.action_mean[i];
-    a.as[i] = md.action_std[i];
-  }
-  a.L = act_layout(md.d, md.nin, p.g, md.h, p.S, B);
-  for (int i = 0; i <= kTensors; ++i) a.off[i] = p.off[i];
+  fill_call(a, c->md, B, b, p);
+  if (int rc = fill_nl(c, a, p)) return rc;
+  fill_train_ws(a, p, w);
+  a.L = act_layout(p.d, c->md.nin, p.g, c->md.h, p.S, B);
   ProfScope ps(c, "train_fwd_bwd_kernel");
   NLC_HIP(c, launch_train_fwd_bwd(a, p.nblk, p.M, c->stream));
   return NLC_OK;
 }
 
-int rnn_fwd_bwd(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
-                const double* target, const int64_t* idx, int64_t N, int B, const Plan& p, const WsPtrs& w) {
+int rnn_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w) {
   const nlc_rnn_desc& rd = c->rd;
   RnnTrainArgs a{};
-  fill_common(a, B, params, obs, window, ts, target, idx, N, p, w);
-  a.d = rd.d;
-  a.nin = rd.nin;
+  fill_call(a, rd, B, b, p);
   a.time_input = rd.time_input;
-  a.time_div = rd.time_div;
-  for (int i = 0; i < rd.d; ++i) {
-    a.sm[i] = rd.state_mean[i];
-    a.ss[i] = rd.state_std[i];
-  }
-  for (int i = 0; i < rd.nin; ++i) {
-    a.am[i] = rd.action_mean[i];
-    a.as[i] = rd.action_std[i];
-  }
+  fill_train_ws(a, p, w);
   a.L = rnn_act_layout(rd.nin, rd.hidden, B);
-  for (int i = 0; i <= kRnnTensors; ++i) a.off[i] = p.off[i];
   ProfScope ps(c, "rnn_train_fwd_bwd_kernel");
   NLC_HIP(c, launch_rnn_train_fwd_bwd(a, rd.hidden, p.nblk, p.M, c->stream));
+  return NLC_OK;
+}
+
+// held-out loss (kernels_train_eval.hip): forward and squared error only; p.gs is the evaluation's (group_eval_entry)
+int nl_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss) {
+  EvalArgs a{};
+  fill_call(a, c->md, B, b, p);
+  if (int rc = fill_nl(c, a, p)) return rc;
+  a.tile_loss = tile_loss;
+  a.L = eval_lds_layout(p.d, c->md.nin, p.g, c->md.h, p.S, B);
+  // one workgroup per compute unit: the kernel's registers leave room for one wave per SIMD, whatever its LDS
+  ProfScope ps(c, "train_eval_kernel");
+  NLC_HIP(c, launch_train_eval(a, eval_grid(a.ntiles, c->prop.multiProcessorCount, 1, p.M), p.M, c->stream));
+  return NLC_OK;
+}
+
+int rnn_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss) {
+  const nlc_rnn_desc& rd = c->rd;
+  RnnEvalArgs a{};
+  fill_call(a, rd, B, b, p);
+  a.time_input = rd.time_input;
+  a.tile_loss = tile_loss;
+  const int per_cu = eval_per_cu(rnn_eval_lds_doubles(rd.hidden) * (int64_t)sizeof(double));
+  ProfScope ps(c, "rnn_eval_kernel");
+  NLC_HIP(c, launch_rnn_eval(a, rd.hidden, eval_grid(a.ntiles, c->prop.multiProcessorCount, per_cu, p.M), p.M, c->stream));
   return NLC_OK;
 }
 
@@ -251,8 +273,7 @@ int64_t group_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
 int group_loss_grad(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
                     const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                     double* grad, double* loss, void* ws, Plan* plan, const int64_t* step = nullptr, bool more_null = false) {
-  if (int rc = rnn ? check_rnn_train(c, N, B) : check_train(c, N, B)) return rc;
-  if (int rc = check_group(c, M, data_rows)) return rc;
+  if (int rc = check_call(c, rnn, M, data_rows, N, B)) return rc;
   if (step && *step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
   const bool need_ts = rnn ? c->rd.time_input != 0 : true;
   if (!params || !obs || !window || (!ts && need_ts) || !target || !idx || (!step && !grad) || !loss || !ws || more_null)
@@ -262,7 +283,8 @@ int group_loss_grad(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double
   p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
   plan_group(p, M, N, data_rows);
   const WsPtrs w = ws_ptrs(p, ws);
-  if (int rc = (rnn ? rnn_fwd_bwd : nl_fwd_bwd)(c, params, obs, window, ts, target, idx, N, B, p, w)) return rc;
+  const Batch b{params, obs, window, ts, target, idx, N};
+  if (int rc = (rnn ? rnn_fwd_bwd : nl_fwd_bwd)(c, b, B, p, w)) return rc;
   return reduce(c, N, step ? w.grad : grad, step ? p.gs.ws : p.P, loss, p, w);
 }
 
@@ -298,93 +320,24 @@ int64_t group_eval_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
   return (int64_t)M * eval_ws_layout(N).total * (int64_t)sizeof(double);
 }
 
-template <class Args>
-void fill_eval(Args& a, int B, const double* params, const double* obs, const double* window, const double* ts,
-               const double* target, const int64_t* idx, int64_t N, int64_t P, int64_t data_rows, const EvalWsLayout& w,
-               void* ws) {
-  a.B = B;
-  a.params = params;
-  a.obs = obs;
-  a.window = window;
-  a.ts = ts;
-  a.target = target;
-  a.idx = idx;
-  a.N = N;
-  a.ntiles = w.ntiles;
-  a.tile_loss = (double*)ws + w.tile_loss;
-  a.gs = GroupStrides{P, w.total, 0, N, data_rows};
-}
-
 int group_eval_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
                      const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                      double* loss, void* ws) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (int rc = rnn ? check_rnn_train(c, N, B) : check_train(c, N, B)) return rc;
-  if (int rc = check_group(c, M, data_rows)) return rc;
+  if (int rc = check_call(c, rnn, M, data_rows, N, B)) return rc;
   const bool need_ts = rnn ? c->rd.time_input != 0 : true;
   if (!params || !obs || !window || (!ts && need_ts) || !target || !loss || !ws)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   const EvalWsLayout w = eval_ws_layout(N);
-  const int cus = c->prop.multiProcessorCount;
-  int64_t off[kTensors + 1];
-  int d;
-  if (rnn) {
-    const nlc_rnn_desc& rd = c->rd;
-    d = rd.d;
-    RnnEvalArgs a{};
-    rnn_blob_offsets(rd.d, rd.nin, rd.hidden, rd.time_input, off);
-    fill_eval(a, B, params, obs, window, ts, target, idx, N, off[kTensors], data_rows, w, ws);
-    a.d = rd.d;
-    a.nin = rd.nin;
-    a.time_input = rd.time_input;
-    a.time_div = rd.time_div;
-    for (int i = 0; i < rd.d; ++i) {
-      a.sm[i] = rd.state_mean[i];
-      a.ss[i] = rd.state_std[i];
-    }
-    for (int i = 0; i < rd.nin; ++i) {
-      a.am[i] = rd.action_mean[i];
-      a.as[i] = rd.action_std[i];
-    }
-    for (int i = 0; i <= kRnnTensors; ++i) a.off[i] = off[i];
-    const int per_cu = eval_per_cu(rnn_eval_lds_doubles(rd.hidden) * (int64_t)sizeof(double));
-    ProfScope ps(c, "rnn_eval_kernel");
-    NLC_HIP(c, launch_rnn_eval(a, rd.hidden, eval_grid(w.ntiles, cus, per_cu, M), M, c->stream));
-  } else {
-    const nlc_model_desc& md = c->md;
-    d = md.d;
-    const int g = md.h / 2, S = md.ilt.terms;
-    EvalArgs a{};
-    blob_offsets(md.d, md.nin, g, md.h, S, off);
-    fill_eval(a, B, params, obs, window, ts, target, idx, N, off[kTensors], data_rows, w, ws);
-    a.d = md.d;
-    a.nin = md.nin;
-    a.g = g;
-    a.h = md.h;
-    a.S = S;
-    a.time_div = md.time_div;
-    a.alpha = md.ilt.alpha;
-    a.log_tol = std::log(md.ilt.tol);
-    // one table for all members of a group (they share the descriptor); NULL selects the Fourier instance
-    if (linear_ilt(md.ilt))
-      if (int rc = linear_tables(c, &md.ilt, &a.lin_tab)) return rc;
-    for (int i = 0; i < md.d; ++i) {
-      a.sm[i] = md.state_mean[i];
-      a.ss[i] = md.state_std[i];
-    }
-    for (int i = 0; i < md.nin; ++i) {
-      a.am[i] = md.action_mean[i];
-      a.as[i] = md.action_std[i];
-    }
-    a.L = eval_lds_layout(md.d, md.nin, g, md.h, S, B);
-    for (int i = 0; i <= kTensors; ++i) a.off[i] = off[i];
-    // one workgroup per compute unit: the kernel's registers leave room for one wave per SIMD, whatever its LDS
-    ProfScope ps(c, "train_eval_kernel");
-    NLC_HIP(c, launch_train_eval(a, eval_grid(w.ntiles, cus, 1, M), M, c->stream));
-  }
-  EvalReduceArgs r{(const double*)ws + w.tile_loss, w.ntiles, N, w.total, d, loss};
+  Plan p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
+  p.M = M;
+  p.gs = GroupStrides{p.P, w.total, 0, N, data_rows};
+  double* tile_loss = (double*)ws + w.tile_loss;
+  const Batch b{params, obs, window, ts, target, idx, N};
+  if (int rc = (rnn ? rnn_eval : nl_eval)(c, b, B, p, tile_loss)) return rc;
+  EvalReduceArgs r{tile_loss, w.ntiles, N, w.total, p.d, loss};
   ProfScope ps(c, "eval_reduce_kernel");
   NLC_HIP(c, launch_eval_reduce(r, M, c->stream));
   return NLC_OK;

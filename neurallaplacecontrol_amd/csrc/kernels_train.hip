@@ -159,18 +159,6 @@ __device__ void dense_tanh_bwd(const double* __restrict__ W, const double* dout,
   }
 }
 
-// c_k = cos(theta + k pi/2) and its theta derivative, from one sincos (exact quarter turns: ILT scale 2)
-__device__ __forceinline__ void quarter(double th, int k, double* c, double* cp) {
-  double sn, cs;
-  sincos(th, &sn, &cs);
-  switch (k & 3) {
-    case 0: *c = cs; *cp = -sn; break;
-    case 1: *c = -sn; *cp = -cs; break;
-    case 2: *c = -cs; *cp = sn; break;
-    default: *c = sn; *cp = cs; break;
-  }
-}
-
 }  // namespace
 
 // kLinear: the fixed Talbot / Stehfest instance (a.lin_tab: nodes and weights).  Only the query points and the line integral
@@ -205,12 +193,11 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
   double* DX1 = ws + L.DX1;
   double* dhA = ws + L.dhA;
   double* dD = ws + L.dD;
-  const double* prm = a.params + mi * a.gs.params;
+  const double* prm = a.batch.params + mi * a.gs.params;
   const int64_t* off = a.off;
   double* part = a.partial + mi * a.gs.ws + (int64_t)blockIdx.x * a.P;
   double* tile_loss = a.tile_loss + mi * a.gs.ws;
-  const double loss_norm = 2.0 / ((double)a.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
-  const double scale = 2.0;
+  const double loss_norm = 2.0 / ((double)a.batch.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
 
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const bool first = tile == (int)blockIdx.x;
@@ -219,21 +206,21 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
     // everywhere, and their loss gradient is 0)
     for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
       const int r = p & (kRows - 1), e = p >> 4;
-      const bool valid = row0 + r < a.N;
+      const bool valid = row0 + r < a.batch.N;
       // the member's rows: its slice of the index array, and of a stacked dataset (gs.rows = 0: the shared one).  The offset
       // goes onto the row index here, not onto four base pointers before the loop: those stayed live across the whole
       // kernel and took its scratch from 68 to 132 B/lane
-      const int64_t src = (valid ? a.idx[mi * a.gs.idx + row0 + r] : 0) + mi * a.gs.rows;
+      const int64_t src = (valid ? a.batch.idx[mi * a.gs.idx + row0 + r] : 0) + mi * a.gs.rows;
       if (e < B * nin) {
         const int s = e / nin, c = e - s * nin;  // step s of the reversed window = window row B - 1 - s
         X0[((int64_t)s * kRows + r) * nin + c] =
-            valid ? (a.window[(src * B + (B - 1 - s)) * nin + c] - a.am[c]) / a.as[c] : 0.0;
+            valid ? (a.batch.window[(src * B + (B - 1 - s)) * nin + c] - a.norm.am[c]) / a.norm.as[c] : 0.0;
       } else if (e < B * nin + d) {
         const int c = e - B * nin;
-        a0[(int64_t)r * K0 + 2 * S + c] = valid ? (a.obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
-        tgt[r * d + c] = valid ? a.target[src * d + c] : 0.0;
+        a0[(int64_t)r * K0 + 2 * S + c] = valid ? (a.batch.obs[src * d + c] - a.norm.sm[c]) / a.norm.ss[c] : 0.0;
+        tgt[r * d + c] = valid ? a.batch.target[src * d + c] : 0.0;
       } else {
-        tn[r] = valid ? a.ts[src] / a.time_div : 1.0;
+        tn[r] = valid ? a.batch.ts[src] / a.time_div : 1.0;
       }
     }
     for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
@@ -249,12 +236,7 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
       if constexpr (kLinear) {
         linear_query_point(a.lin_tab[k], a.lin_tab[S + k], tn[r], &a0[(int64_t)r * K0 + k], &a0[(int64_t)r * K0 + S + k]);
       } else {
-        const double t = tn[r], Tt = scale * t;
-        const double gamma = a.alpha - a.log_tol / (scale * Tt);
-        const double im = kPi * (double)k / Tt;
-        const double a2v = gamma * gamma + im * im;
-        a0[(int64_t)r * K0 + k] = atan2(im, gamma);
-        a0[(int64_t)r * K0 + S + k] = asin((a2v - 1.0) / (a2v + 1.0));
+        fourier_query_point(a.alpha, a.log_tol, tn[r], k, &a0[(int64_t)r * K0 + k], &a0[(int64_t)r * K0 + S + k]);
       }
     }
     // ---- reverse GRU encoder (w_nl.py:25-29), two layers
@@ -292,16 +274,14 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
         const double* yt = u + (int64_t)r * O + c * S;
         const double* yp = u + (int64_t)r * O + (d + c) * S;
         const double pred = linear_row_sum(yt, yp, wr, wi, S) / t;
-        const bool valid = row0 + r < a.N;
+        const bool valid = row0 + r < a.batch.N;
         const double diff = pred - tgt[r * d + c];
         sq[r * d + c] = valid ? diff * diff : 0.0;
         const double gs = valid ? (loss_norm * diff) / t : 0.0;
         linear_row_bwd(gs, yt, yp, wr, wi, S, d3 + (int64_t)r * O + c * S, d3 + (int64_t)r * O + (d + c) * S);
         continue;
       }
-      const double t = tn[r], Tt = scale * t;
-      const double gamma = a.alpha - a.log_tol / (scale * Tt);
-      const double srow = exp(gamma * t) / Tt;
+      const double srow = fourier_pred_factor(a.alpha, a.log_tol, tn[r]);
       const double* yt = u + (int64_t)r * O + c * S;
       const double* yp = u + (int64_t)r * O + (d + c) * S;
       double acc = 0.0;
@@ -312,7 +292,7 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
         acc += (k == 0 ? 0.5 : 1.0) * R * cv;
       }
       const double pred = srow * acc;
-      const bool valid = row0 + r < a.N;
+      const bool valid = row0 + r < a.batch.N;
       const double diff = pred - tgt[r * d + c];
       sq[r * d + c] = valid ? diff * diff : 0.0;
       const double gs = valid ? (loss_norm * diff) * srow : 0.0;

@@ -92,18 +92,6 @@ __device__ __forceinline__ void dense_tanh_lds(const double* in, int ldi, const 
   dense_mfma(in, ldi, W, K, Nout, 0, [=](int r, int n, double v) { out[r * ldo + n] = m::tanh_d(v + b[n]); });
 }
 
-// c_k = cos(theta + k pi/2) (exact quarter turns: ILT scale 2)
-__device__ __forceinline__ double quarter_cos(double th, int k) {
-  double sn, cs;
-  sincos(th, &sn, &cs);
-  switch (k & 3) {
-    case 0: return cs;
-    case 1: return -sn;
-    case 2: return -cs;
-    default: return sn;
-  }
-}
-
 }  // namespace
 
 template <bool kLinear>
@@ -126,12 +114,12 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
   double* a2 = lds + L.a2;
   double* u = lds + L.u;
   const int64_t mi = blockIdx.y;  // member of the group: its own blob, tile losses, index array and dataset rows
-  const double* prm = a.params + mi * a.gs.params;
+  const Batch& b = a.batch;
+  const double* prm = b.params + mi * a.gs.params;
   const int64_t* off = a.off;
   double* tile_loss = a.tile_loss + mi * a.gs.ws;
-  const int64_t* idx = a.idx ? a.idx + mi * a.gs.idx : nullptr;
+  const int64_t* idx = b.idx ? b.idx + mi * a.gs.idx : nullptr;
   const int64_t drow = mi * a.gs.rows;
-  const double scale = 2.0;
   // the encoder's tensors (blob order: W_ih, W_hh, b_ih, b_hh of layer 0, then of layer 1)
   const double* Wih0 = prm + off[0];
   const double* Whh0 = prm + off[1];
@@ -148,17 +136,18 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
     // everywhere) and add nothing to the loss
     for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
       const int r = p & (kRows - 1), e = p >> 4;
-      const bool valid = row0 + r < a.N;
+      const bool valid = row0 + r < b.N;
       const int64_t src = (valid ? (idx ? idx[row0 + r] : row0 + r) : 0) + drow;
       if (e < B * nin) {
         const int s = e / nin, c = e - s * nin;  // step s of the reversed window = window row B - 1 - s
-        X0[(s * kRows + r) * nin + c] = valid ? (a.window[(src * B + (B - 1 - s)) * nin + c] - a.am[c]) / a.as[c] : 0.0;
+        X0[(s * kRows + r) * nin + c] =
+            valid ? (b.window[(src * B + (B - 1 - s)) * nin + c] - a.norm.am[c]) / a.norm.as[c] : 0.0;
       } else if (e < B * nin + d) {
         const int c = e - B * nin;
-        a0[r * ldK + 2 * S + c] = valid ? (a.obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
-        tgt[r * d + c] = valid ? a.target[src * d + c] : 0.0;
+        a0[r * ldK + 2 * S + c] = valid ? (b.obs[src * d + c] - a.norm.sm[c]) / a.norm.ss[c] : 0.0;
+        tgt[r * d + c] = valid ? b.target[src * d + c] : 0.0;
       } else {
-        tn[r] = valid ? a.ts[src] / a.time_div : 1.0;
+        tn[r] = valid ? b.ts[src] / a.time_div : 1.0;
       }
     }
     for (int p = threadIdx.x; p < kRows * ldg; p += kThreads) {
@@ -172,12 +161,7 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
       if constexpr (kLinear) {
         linear_query_point(a.lin_tab[k], a.lin_tab[S + k], tn[r], &a0[r * ldK + k], &a0[r * ldK + S + k]);
       } else {
-        const double t = tn[r], Tt = scale * t;
-        const double gamma = a.alpha - a.log_tol / (scale * Tt);
-        const double im = kPi * (double)k / Tt;
-        const double a2v = gamma * gamma + im * im;
-        a0[r * ldK + k] = atan2(im, gamma);
-        a0[r * ldK + S + k] = asin((a2v - 1.0) / (a2v + 1.0));
+        fourier_query_point(a.alpha, a.log_tol, tn[r], k, &a0[r * ldK + k], &a0[r * ldK + S + k]);
       }
     }
     // ---- reverse GRU encoder (w_nl.py:25-29): both layers step by step, h_0 = 0 (the first step has no hidden products)
@@ -188,25 +172,8 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
       }
       for (int p = threadIdx.x; p < kRows * g; p += kThreads) {
         const int r = p >> lg, j = p & (g - 1);
-        const double* x = X0 + (s * kRows + r) * nin;
-        double ir = 0.0, iz = 0.0, in_ = 0.0;
-        for (int c = 0; c < nin; ++c) {
-          const double xc = x[c];
-          ir += Wih0[j * nin + c] * xc;
-          iz += Wih0[(g + j) * nin + c] * xc;
-          in_ += Wih0[(2 * g + j) * nin + c] * xc;
-        }
-        ir += bih0[j];
-        iz += bih0[g + j];
-        in_ += bih0[2 * g + j];
-        const double* gh = G + r * ldG;
-        const double hr = (s > 0 ? gh[j] : 0.0) + bhh0[j];
-        const double hz = (s > 0 ? gh[g + j] : 0.0) + bhh0[g + j];
-        const double hn = (s > 0 ? gh[2 * g + j] : 0.0) + bhh0[2 * g + j];
-        const double rr = m::sigmoid_d(ir + hr);
-        const double zz = m::sigmoid_d(iz + hz);
-        const double nn = m::tanh_d(in_ + rr * hn);
-        h0[r * ldg + j] = (1.0 - zz) * nn + zz * h0[r * ldg + j];
+        const Gate gt = gru_gate0(X0 + (s * kRows + r) * nin, nin, Wih0, bih0, bhh0, s > 0 ? G + r * ldG : nullptr, g, j);
+        h0[r * ldg + j] = (1.0 - gt.z) * gt.n + gt.z * h0[r * ldg + j];
       }
       __syncthreads();
       // layer 1: the r and z gates take both products in one accumulator; the n gate keeps its two halves apart
@@ -269,7 +236,8 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
           linear_phase(sphere_theta(*yt), a.lin_tab[2 * S + k], a.lin_tab[3 * S + k], &cv, &cp);
           *yt = sphere_radius(sphere_phi(yp)) * cv;
         } else {
-          const double cv = quarter_cos(sphere_theta(*yt), k);
+          double cv, cp;
+          quarter(sphere_theta(*yt), k, &cv, &cp);
           const double R = tan(sphere_phi(yp) / 2.0 + kPi / 4.0);
           *yt = (k == 0 ? 0.5 : 1.0) * R * cv;
         }
@@ -281,17 +249,10 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
         double acc = 0.0;
         for (int k = 0; k < S; ++k) acc += term[k];
         const double t = tn[r];
-        double pred;
-        if constexpr (kLinear) {
-          pred = acc / t;
-        } else {
-          const double Tt = scale * t;
-          const double gamma = a.alpha - a.log_tol / (scale * Tt);
-          pred = exp(gamma * t) / Tt * acc;
-        }
+        const double pred = kLinear ? acc / t : fourier_pred_factor(a.alpha, a.log_tol, t) * acc;
         const int c = c0 + cc;
         const double diff = pred - tgt[r * d + c];
-        sq[r * d + c] = row0 + r < a.N ? diff * diff : 0.0;
+        sq[r * d + c] = row0 + r < b.N ? diff * diff : 0.0;
       }
       __syncthreads();
     }
@@ -307,20 +268,19 @@ __global__ __launch_bounds__(kThreads) void train_eval_kernel(const EvalArgs a) 
 template <int H>
 __global__ __launch_bounds__(kThreads) void rnn_eval_kernel(const RnnEvalArgs a) {
   static_assert(H % 16 == 0, "whole 16-feature output tiles and k quads");
-  constexpr int H3 = 3 * H, LH = H + 2, LG = H3 + 2, LF = kEvalMaxD + 1;
-  __shared__ double hS[kRows * LH];                    // the current hidden state
-  __shared__ double gS[kRows * LG];                    // h W_hh^T
-  __shared__ double xS[kMaxB * kRows * kEvalMaxNin];   // normalised window, forward order: [s][r][nin]
-  __shared__ double fS[kRows * LF];                    // [obs_n | ts_n]
-  __shared__ double tS[kRows * kEvalMaxD];             // target
-  __shared__ double sqS[kRows * kEvalMaxD];            // squared errors
-  static_assert(sizeof(double) * (kRows * LH + kRows * LG + kMaxB * kRows * kEvalMaxNin + kRows * LF + 2 * kRows * kEvalMaxD) ==
-                    sizeof(double) * rnn_eval_lds_doubles(H),
+  constexpr int H3 = 3 * H, LH = H + 2, LG = H3 + 2, LF = kMaxD + 1;
+  __shared__ double hS[kRows * LH];               // the current hidden state
+  __shared__ double gS[kRows * LG];               // h W_hh^T
+  __shared__ double xS[kMaxB * kRows * kMaxNin];  // normalised window, forward order: [s][r][nin]
+  __shared__ double fS[kRows * LF];               // [obs_n | ts_n]
+  __shared__ double tS[kRows * kMaxD];            // target
+  __shared__ double sqS[kRows * kMaxD];           // squared errors
+  static_assert(kRows * LH + kRows * LG + kMaxB * kRows * kMaxNin + kRows * LF + 2 * kRows * kMaxD == rnn_eval_lds_doubles(H),
                 "rnn_eval_lds_doubles is what the host sizes the grid with");
   const int d = a.d, nin = a.nin, B = a.B, ti = a.time_input ? 1 : 0;
   const int F = H + d + ti;
   const int64_t mi = blockIdx.y;  // member of the group (nlc_train.h GroupStrides; a single model is M = 1)
-  const double* prm = a.params + mi * a.gs.params;
+  const double* prm = a.batch.params + mi * a.gs.params;
   const double* Wih = prm + a.off[0];
   const double* Whh = prm + a.off[1];
   const double* bih = prm + a.off[2];
@@ -328,12 +288,12 @@ __global__ __launch_bounds__(kThreads) void rnn_eval_kernel(const RnnEvalArgs a)
   const double* Wo = prm + a.off[4];
   const double* bo = prm + a.off[5];
   double* tile_loss = a.tile_loss + mi * a.gs.ws;
-  const int64_t* idx = a.idx ? a.idx + mi * a.gs.idx : nullptr;
+  const int64_t* idx = a.batch.idx ? a.batch.idx + mi * a.gs.idx : nullptr;
   const int64_t drow = mi * a.gs.rows;  // the member's rows of a stacked dataset (gs.rows = 0: the shared one)
-  const double* obs = a.obs + drow * d;
-  const double* window = a.window + drow * B * nin;
-  const double* tsp = ti ? a.ts + drow : nullptr;  // a model without time input has no ts (a.ts may be NULL)
-  const double* target = a.target + drow * d;
+  const double* obs = a.batch.obs + drow * d;
+  const double* window = a.batch.window + drow * B * nin;
+  const double* tsp = ti ? a.batch.ts + drow : nullptr;  // a model without time input has no ts (batch.ts may be NULL)
+  const double* target = a.batch.target + drow * d;
 
   for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const int64_t row0 = tile * kRows;
@@ -341,15 +301,15 @@ __global__ __launch_bounds__(kThreads) void rnn_eval_kernel(const RnnEvalArgs a)
     // past N are zeros and add nothing to the loss
     for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
       const int r = p & (kRows - 1), e = p >> 4;
-      const bool valid = row0 + r < a.N;
+      const bool valid = row0 + r < a.batch.N;
       const int64_t src = valid ? (idx ? idx[row0 + r] : row0 + r) : 0;
       if (e < B * nin) {
         const int s = e / nin, c = e - s * nin;
-        xS[(s * kRows + r) * nin + c] = valid ? (window[(src * B + s) * nin + c] - a.am[c]) / a.as[c] : 0.0;
+        xS[(s * kRows + r) * nin + c] = valid ? (window[(src * B + s) * nin + c] - a.norm.am[c]) / a.norm.as[c] : 0.0;
       } else if (e < B * nin + d) {
         const int c = e - B * nin;
-        fS[r * LF + c] = valid ? (obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
-        tS[r * kEvalMaxD + c] = valid ? target[src * d + c] : 0.0;
+        fS[r * LF + c] = valid ? (obs[src * d + c] - a.norm.sm[c]) / a.norm.ss[c] : 0.0;
+        tS[r * kMaxD + c] = valid ? target[src * d + c] : 0.0;
       } else {
         fS[r * LF + d] = (valid && ti) ? tsp[src] / a.time_div : 0.0;
       }
@@ -364,25 +324,8 @@ __global__ __launch_bounds__(kThreads) void rnn_eval_kernel(const RnnEvalArgs a)
       }
       for (int p = threadIdx.x; p < kRows * H; p += kThreads) {
         const int r = p / H, j = p - r * H;
-        const double* x = xS + (s * kRows + r) * nin;
-        double ir = 0.0, iz = 0.0, in_ = 0.0;
-        for (int c = 0; c < nin; ++c) {
-          const double xc = x[c];
-          ir += Wih[j * nin + c] * xc;
-          iz += Wih[(H + j) * nin + c] * xc;
-          in_ += Wih[(2 * H + j) * nin + c] * xc;
-        }
-        ir += bih[j];
-        iz += bih[H + j];
-        in_ += bih[2 * H + j];
-        const double* gh = gS + r * LG;
-        const double hr = (s > 0 ? gh[j] : 0.0) + bhh[j];
-        const double hz = (s > 0 ? gh[H + j] : 0.0) + bhh[H + j];
-        const double hn = (s > 0 ? gh[2 * H + j] : 0.0) + bhh[2 * H + j];
-        const double rr = m::sigmoid_d(ir + hr);
-        const double zz = m::sigmoid_d(iz + hz);
-        const double nn = m::tanh_d(in_ + rr * hn);
-        hS[r * LH + j] = (1.0 - zz) * nn + zz * hS[r * LH + j];
+        const Gate gt = gru_gate0(xS + (s * kRows + r) * nin, nin, Wih, bih, bhh, s > 0 ? gS + r * LG : nullptr, H, j);
+        hS[r * LH + j] = (1.0 - gt.z) * gt.n + gt.z * hS[r * LH + j];
       }
       __syncthreads();
     }
@@ -395,8 +338,8 @@ __global__ __launch_bounds__(kThreads) void rnn_eval_kernel(const RnnEvalArgs a)
 #pragma unroll 8
       for (int i = 0; i < H; ++i) acc += w[i] * hB[i];
       for (int i = 0; i < d + ti; ++i) acc += w[H + i] * fS[r * LF + i];
-      const double diff = (acc + bo[c]) - tS[r * kEvalMaxD + c];
-      sqS[r * d + c] = row0 + r < a.N ? diff * diff : 0.0;
+      const double diff = (acc + bo[c]) - tS[r * kMaxD + c];
+      sqS[r * d + c] = row0 + r < a.batch.N ? diff * diff : 0.0;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -448,17 +391,11 @@ hipError_t launch_train_eval(const EvalArgs& a, int G, int M, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int... Ws>
-static hipError_t launch_rnn_widths(const RnnEvalArgs& a, int H, int G, int M, hipStream_t s, std::integer_sequence<int, Ws...>) {
-  auto launch = [&](auto w) {
-    hipLaunchKernelGGL((rnn_eval_kernel<decltype(w)::value>), dim3(G, M), dim3(kThreads), 0, s, a);
-    return true;
-  };
-  const bool found = ((H == Ws && launch(std::integral_constant<int, Ws>{})) || ...);
-  return found ? hipGetLastError() : hipErrorInvalidValue;
-}
 hipError_t launch_rnn_eval(const RnnEvalArgs& a, int H, int G, int M, hipStream_t s) {
-  return launch_rnn_widths(a, H, G, M, s, std::integer_sequence<int, 64, 128, 160>{});
+  const bool found = for_rnn_width(H, [&](auto w) {
+    hipLaunchKernelGGL((rnn_eval_kernel<decltype(w)::value>), dim3(G, M), dim3(kThreads), 0, s, a);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_eval_reduce(const EvalReduceArgs& a, int M, hipStream_t s) {

@@ -27,7 +27,6 @@ namespace train {
 
 namespace {
 
-constexpr int kMaxDim = 8;  // largest state_dim (include/nlc.h NLC_MAX_D)
 constexpr int kLdPad = 2;  // doubles of padding per LDS row: rows of an MFMA's A operand start on different banks
 
 // gS[r][n] = sum_k hS[r][k] W_hh[n][k]  (n < 3H, k < H)
@@ -75,14 +74,14 @@ __device__ __forceinline__ void hidden_bwd_mfma(const double* gS, const double* 
 template <int H>
 __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTrainArgs a) {
   static_assert(H % 32 == 0 && (3 * H) % 16 == 0, "k quarters of both products must be whole");
-  constexpr int H3 = 3 * H, LH = H + kLdPad, LG = H3 + kLdPad, LF = kMaxDim + 1;
-  __shared__ double hS[kRows * LH];          // forward: the current hidden state; backward: second addend of dL/dh
-  __shared__ double gS[kRows * LG];          // forward: h W_hh^T; backward: the hidden-side gate gradients
-  __shared__ double dS[kRows * LH];          // backward: dL/dh
-  __shared__ double fS[kRows * LF];          // [obs_n | ts_n]
-  __shared__ double tS[kRows * kMaxDim];   // target
-  __shared__ double eS[kRows * kMaxDim];   // dL/dpred
-  __shared__ double sqS[kRows * kMaxDim];  // squared errors
+  constexpr int H3 = 3 * H, LH = H + kLdPad, LG = H3 + kLdPad, LF = kMaxD + 1;
+  __shared__ double hS[kRows * LH];      // forward: the current hidden state; backward: second addend of dL/dh
+  __shared__ double gS[kRows * LG];      // forward: h W_hh^T; backward: the hidden-side gate gradients
+  __shared__ double dS[kRows * LH];      // backward: dL/dh
+  __shared__ double fS[kRows * LF];      // [obs_n | ts_n]
+  __shared__ double tS[kRows * kMaxD];   // target
+  __shared__ double eS[kRows * kMaxD];   // dL/dpred
+  __shared__ double sqS[kRows * kMaxD];  // squared errors
   const int d = a.d, nin = a.nin, B = a.B, ti = a.time_input ? 1 : 0;
   const int F = H + d + ti;
   const RnnActLayout& L = a.L;
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
   double* G = ws + L.G;
   double* DI = ws + L.DI;
   double* DH = ws + L.DH;
-  const double* prm = a.params + mi * a.gs.params;
+  const double* prm = a.batch.params + mi * a.gs.params;
   const double* Wih = prm + a.off[0];
   const double* Whh = prm + a.off[1];
   const double* bih = prm + a.off[2];
@@ -103,13 +102,13 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
   double* part = a.partial + mi * a.gs.ws + (int64_t)blockIdx.x * a.P;
   double* tile_loss = a.tile_loss + mi * a.gs.ws;
   // the member's slice of the index array and its rows of a stacked dataset (gs.rows = 0: the shared one)
-  const int64_t* idx = a.idx + mi * a.gs.idx;
+  const int64_t* idx = a.batch.idx + mi * a.gs.idx;
   const int64_t drow = mi * a.gs.rows;
-  const double* obs = a.obs + drow * d;
-  const double* window = a.window + drow * B * nin;
-  const double* tsp = ti ? a.ts + drow : nullptr;  // a model without time input has no ts (a.ts may be NULL)
-  const double* target = a.target + drow * d;
-  const double loss_norm = 2.0 / ((double)a.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
+  const double* obs = a.batch.obs + drow * d;
+  const double* window = a.batch.window + drow * B * nin;
+  const double* tsp = ti ? a.batch.ts + drow : nullptr;  // a model without time input has no ts (batch.ts may be NULL)
+  const double* target = a.batch.target + drow * d;
+  const double loss_norm = 2.0 / ((double)a.batch.N * (double)d);  // MSELoss backward: 2 / numel * (input - target)
 
   for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const bool first = tile == (int)blockIdx.x;
@@ -118,15 +117,15 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
     // past N are zeros, and their loss gradient is 0
     for (int p = threadIdx.x; p < kRows * (B * nin + d + 1); p += kThreads) {
       const int r = p & (kRows - 1), e = p >> 4;
-      const bool valid = row0 + r < a.N;
+      const bool valid = row0 + r < a.batch.N;
       const int64_t src = valid ? idx[row0 + r] : 0;
       if (e < B * nin) {
         const int s = e / nin, c = e - s * nin;
-        X[((int64_t)s * kRows + r) * nin + c] = valid ? (window[(src * B + s) * nin + c] - a.am[c]) / a.as[c] : 0.0;
+        X[((int64_t)s * kRows + r) * nin + c] = valid ? (window[(src * B + s) * nin + c] - a.norm.am[c]) / a.norm.as[c] : 0.0;
       } else if (e < B * nin + d) {
         const int c = e - B * nin;
-        fS[r * LF + c] = valid ? (obs[src * d + c] - a.sm[c]) / a.ss[c] : 0.0;
-        tS[r * kMaxDim + c] = valid ? target[src * d + c] : 0.0;
+        fS[r * LF + c] = valid ? (obs[src * d + c] - a.norm.sm[c]) / a.norm.ss[c] : 0.0;
+        tS[r * kMaxD + c] = valid ? target[src * d + c] : 0.0;
       } else {
         fS[r * LF + d] = (valid && ti) ? tsp[src] / a.time_div : 0.0;
       }
@@ -184,10 +183,10 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
 #pragma unroll 8
       for (int i = 0; i < H; ++i) acc += w[i] * hB[i];
       for (int i = 0; i < d + ti; ++i) acc += w[H + i] * fS[r * LF + i];
-      const double diff = (acc + bo[c]) - tS[r * kMaxDim + c];
-      const bool valid = row0 + r < a.N;
+      const double diff = (acc + bo[c]) - tS[r * kMaxD + c];
+      const bool valid = row0 + r < a.batch.N;
       sqS[r * d + c] = valid ? diff * diff : 0.0;
-      eS[r * kMaxDim + c] = valid ? loss_norm * diff : 0.0;
+      eS[r * kMaxD + c] = valid ? loss_norm * diff : 0.0;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -199,19 +198,19 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
     for (int p = threadIdx.x; p < d * F; p += kThreads) {
       const int c = p / F, i = p - c * F;
       double acc = first ? 0.0 : part[a.off[4] + p];
-      for (int r = 0; r < kRows; ++r) acc += eS[r * kMaxDim + c] * (i < H ? hS[r * LH + i] : fS[r * LF + i - H]);
+      for (int r = 0; r < kRows; ++r) acc += eS[r * kMaxD + c] * (i < H ? hS[r * LH + i] : fS[r * LF + i - H]);
       part[a.off[4] + p] = acc;
     }
     if ((int)threadIdx.x < d) {
       const int c = threadIdx.x;
       double acc = first ? 0.0 : part[a.off[5] + c];
-      for (int r = 0; r < kRows; ++r) acc += eS[r * kMaxDim + c];
+      for (int r = 0; r < kRows; ++r) acc += eS[r * kMaxD + c];
       part[a.off[5] + c] = acc;
     }
     for (int p = threadIdx.x; p < kRows * H; p += kThreads) {
       const int r = p / H, j = p - r * H;
       double acc = 0.0;
-      for (int c = 0; c < d; ++c) acc += Wo[(int64_t)c * F + j] * eS[r * kMaxDim + c];
+      for (int c = 0; c < d; ++c) acc += Wo[(int64_t)c * F + j] * eS[r * kMaxD + c];
       dS[r * LH + j] = acc;
     }
     __syncthreads();
@@ -251,19 +250,11 @@ __global__ __launch_bounds__(kThreads) void rnn_train_fwd_bwd_kernel(const RnnTr
   }
 }
 
-// one launcher over the widths nlc_set_rnn_model takes
-template <int... Ws>
-static hipError_t launch_widths(const RnnTrainArgs& a, int H, int nblk, int M, hipStream_t s,
-                                std::integer_sequence<int, Ws...>) {
-  auto launch = [&](auto w) {
-    hipLaunchKernelGGL((rnn_train_fwd_bwd_kernel<decltype(w)::value>), dim3(nblk, M), dim3(kThreads), 0, s, a);
-    return true;
-  };
-  const bool found = ((H == Ws && launch(std::integral_constant<int, Ws>{})) || ...);
-  return found ? hipGetLastError() : hipErrorInvalidValue;
-}
 hipError_t launch_rnn_train_fwd_bwd(const RnnTrainArgs& a, int H, int nblk, int M, hipStream_t s) {
-  return launch_widths(a, H, nblk, M, s, std::integer_sequence<int, 64, 128, 160>{});
+  const bool found = for_rnn_width(H, [&](auto w) {
+    hipLaunchKernelGGL((rnn_train_fwd_bwd_kernel<decltype(w)::value>), dim3(nblk, M), dim3(kThreads), 0, s, a);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace train

@@ -11,6 +11,7 @@
 #pragma once
 #include <math.h>
 
+#include "../../include/nlc.h"  // NLC_MAX_D, NLC_MAX_NIN
 #include "nlc_math.h"
 
 namespace nlc {
@@ -98,6 +99,23 @@ NLC_HD void linear_query_point(double node_re, double node_im, double t, double*
   *theta_s = atan2(si, sr);
   *phi_s = asin((a2v - 1.0) / (a2v + 1.0));
 }
+// the Fourier series at ILT scale 2, T = scale t: gamma = alpha - log_tol / (scale T), the real part of every query point
+constexpr double kFourierScale = 2.0;
+NLC_HD double fourier_gamma(double alpha, double log_tol, double Tt) { return alpha - log_tol / (kFourierScale * Tt); }
+// its query point s_k = gamma + i pi k / T on the Riemann sphere (as rep_inputs_kernel's Fourier branch)
+NLC_HD void fourier_query_point(double alpha, double log_tol, double t, int k, double* theta_s, double* phi_s) {
+  const double Tt = kFourierScale * t;
+  const double gamma = fourier_gamma(alpha, log_tol, Tt);
+  const double im = kPiT * (double)k / Tt;
+  const double a2v = gamma * gamma + im * im;
+  *theta_s = atan2(im, gamma);
+  *phi_s = asin((a2v - 1.0) / (a2v + 1.0));
+}
+// and the factor e^{gamma t} / T of its prediction
+NLC_HD double fourier_pred_factor(double alpha, double log_tol, double t) {
+  const double Tt = kFourierScale * t;
+  return exp(fourier_gamma(alpha, log_tol, Tt) * t) / Tt;
+}
 
 // ---- clip_grad_norm_: coefficient the gradients are multiplied by (NaN total -> NaN, as torch.clamp propagates it)
 NLC_HD double clip_coef(double max_norm, double total_norm) {
@@ -136,6 +154,8 @@ constexpr int kMaxB = 16;      // longest action window (action_buffer_size, con
 constexpr int kMaxBlocks = 128;
 constexpr int kChunk = 1024;   // parameters per reduce / Adam workgroup (never straddles two tensors)
 constexpr int kTensors = 16;   // blob tensors (include/nlc.h, nlc_set_model)
+constexpr int kMaxD = NLC_MAX_D;      // largest state_dim
+constexpr int kMaxNin = NLC_MAX_NIN;  // largest GRU input dim
 
 // per-tile activations, tapes and deltas in one workgroup's slab (doubles, each array 64-byte aligned)
 struct ActLayout {
@@ -258,14 +278,25 @@ inline TrainWsLayout train_ws_layout(int nblk, int64_t P, int64_t A, int chunks)
 }
 constexpr int kMaxGroup = 65535;  // members of a group: the grid's y limit
 
+// ---- what the four forward launches (training and evaluation, both families) are given alike
+// normalisation constants of the model descriptor: state mean / std, action mean / std
+struct Norm {
+  double sm[kMaxD], ss[kMaxD], am[kMaxNin], as[kMaxNin];
+};
+// member 0's blob and dataset, and the N rows of the call: idx [N] into obs (rows, d), window (rows, B, nin), ts (rows),
+// target (rows, d).  ts is not read by an RNN without time input; evaluation takes idx == NULL for rows 0 .. N - 1
+struct Batch {
+  const double* params;
+  const double *obs, *window, *ts, *target;
+  const int64_t* idx;
+  int64_t N;
+};
+
 struct RnnTrainArgs {
   int d, nin, B, time_input;
   double time_div;
-  double sm[8], ss[8], am[3], as[3];
-  const double* params;
-  const double *obs, *window, *ts, *target;  // ts is not read unless time_input
-  const int64_t* idx;
-  int64_t N;
+  Norm norm;
+  Batch batch;
   int ntiles;
   int64_t P, A;
   RnnActLayout L;
@@ -279,11 +310,8 @@ struct RnnTrainArgs {
 struct TrainArgs {
   int d, nin, g, h, S, B;
   double time_div, alpha, log_tol;
-  double sm[8], ss[8], am[3], as[3];
-  const double* params;
-  const double *obs, *window, *ts, *target;
-  const int64_t* idx;
-  int64_t N;
+  Norm norm;
+  Batch batch;
   int ntiles;
   int64_t P, A;
   ActLayout L;        // offsets into a workgroup's slab for this call's B
@@ -291,7 +319,7 @@ struct TrainArgs {
   double* tile_loss;  // [gridDim.x] per-workgroup sums of squared errors
   double* act;        // [gridDim.x][A]
   int64_t off[kTensors + 1];
-  GroupStrides gs;    // params, partial / tile_loss / act, idx and the dataset pointers above are member 0's
+  GroupStrides gs;    // batch, partial / tile_loss / act are member 0's
   // fixed Talbot / Stehfest: the device tables [node_re | node_im | W_re | W_im], S doubles each, shared by every member;
   // NULL: the Fourier series (alpha, log_tol).  Selects the kernel instance
   const double* lin_tab;

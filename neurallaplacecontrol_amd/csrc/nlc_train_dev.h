@@ -1,5 +1,6 @@
-// Device-side pieces the training kernels share (kernels_train.hip, kernels_train_rnn.hip): weight / bias gradients as sums
-// over a tile's samples.
+// Device-side pieces the training and evaluation kernels share (kernels_train.hip, kernels_train_rnn.hip,
+// kernels_train_eval.hip): weight / bias gradients as sums over a tile's samples, the layer-0 GRU gate element of the
+// evaluation kernels, the Fourier series' quarter turn, and the launch dispatch over the RNN widths.
 #pragma once
 #include "nlc_device.h"
 #include "nlc_train.h"
@@ -50,6 +51,58 @@ __device__ void bgrad(double* __restrict__ out, int M, int ns, const double* __r
     for (int s = 0; s < ns; ++s) acc += D[(int64_t)s * ldD + m];
     out[m] = acc;
   }
+}
+
+// element j of a width-H GRU's first layer: r, z, n and hn = W_hn h + b_hn (torch.nn.GRU gate order [r; z; n]) from the
+// row's normalised input x [nin] (nin <= 3: plain FMAs) and its hidden products gh = [r | z | n] of h W_hh^T (NULL at the
+// first step: h_0 = 0).  The caller blends h' = (1 - z) n + z h with its own previous state and keeps what it tapes
+struct Gate {
+  double r, z, n, hn;
+};
+__device__ __forceinline__ Gate gru_gate0(const double* x, int nin, const double* __restrict__ Wih,
+                                          const double* __restrict__ bih, const double* __restrict__ bhh, const double* gh,
+                                          int H, int j) {
+  double ir = 0.0, iz = 0.0, in_ = 0.0;
+  for (int c = 0; c < nin; ++c) {
+    const double xc = x[c];
+    ir += Wih[j * nin + c] * xc;
+    iz += Wih[(H + j) * nin + c] * xc;
+    in_ += Wih[(2 * H + j) * nin + c] * xc;
+  }
+  ir += bih[j];
+  iz += bih[H + j];
+  in_ += bih[2 * H + j];
+  const double hr = (gh ? gh[j] : 0.0) + bhh[j];
+  const double hz = (gh ? gh[H + j] : 0.0) + bhh[H + j];
+  Gate g;
+  g.hn = (gh ? gh[2 * H + j] : 0.0) + bhh[2 * H + j];
+  g.r = m::sigmoid_d(ir + hr);
+  g.z = m::sigmoid_d(iz + hz);
+  g.n = m::tanh_d(in_ + g.r * g.hn);
+  return g;
+}
+
+// c_k = cos(theta + k pi/2) and its theta derivative, from one sincos (exact quarter turns: ILT scale 2)
+__device__ __forceinline__ void quarter(double th, int k, double* c, double* cp) {
+  double sn, cs;
+  sincos(th, &sn, &cs);
+  switch (k & 3) {
+    case 0: *c = cs; *cp = -sn; break;
+    case 1: *c = -sn; *cp = -cs; break;
+    case 2: *c = -cs; *cp = sn; break;
+    default: *c = sn; *cp = cs; break;
+  }
+}
+
+// host: f(std::integral_constant<int, H>{}) at the H among the widths nlc_set_rnn_model takes (a kernel instance each);
+// false when H is none of them
+template <class F, int... Ws>
+bool for_width(int H, F f, std::integer_sequence<int, Ws...>) {
+  return ((H == Ws && (f(std::integral_constant<int, Ws>{}), true)) || ...);
+}
+template <class F>
+bool for_rnn_width(int H, F f) {
+  return for_width(H, f, std::integer_sequence<int, 64, 128, 160>{});
 }
 
 }  // namespace

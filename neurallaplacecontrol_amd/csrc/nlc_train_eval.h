@@ -82,11 +82,9 @@ NLC_HD EvalLdsLayout eval_lds_layout(int d, int nin, int g, int h, int S, int B)
 
 // ---- DeltaTRNN / RNN: the static LDS of rnn_eval_kernel<H>, in doubles (hidden state, gate tile, window, [obs_n | ts_n],
 // target, squared errors)
-constexpr int kEvalMaxD = 8;    // largest state_dim (include/nlc.h NLC_MAX_D)
-constexpr int kEvalMaxNin = 3;  // largest GRU input dim (NLC_MAX_NIN)
 constexpr int64_t rnn_eval_lds_doubles(int H) {
-  return (int64_t)kRows * (H + 2) + (int64_t)kRows * (3 * H + 2) + (int64_t)kMaxB * kRows * kEvalMaxNin +
-         (int64_t)kRows * (kEvalMaxD + 1) + 2 * (int64_t)kRows * kEvalMaxD;
+  return (int64_t)kRows * (H + 2) + (int64_t)kRows * (3 * H + 2) + (int64_t)kMaxB * kRows * kMaxNin +
+         (int64_t)kRows * (kMaxD + 1) + 2 * (int64_t)kRows * kMaxD;
 }
 
 // workgroups of this LDS size a compute unit runs side by side, at most kEvalPerCu
@@ -98,11 +96,9 @@ inline int eval_per_cu(int64_t lds_bytes) {
 struct EvalArgs {
   int d, nin, g, h, S, B;
   double time_div, alpha, log_tol;
-  double sm[8], ss[8], am[3], as[3];
-  const double* params;
-  const double *obs, *window, *ts, *target;
-  const int64_t* idx;  // NULL: rows 0 .. N - 1
-  int64_t N, ntiles;
+  Norm norm;
+  Batch batch;
+  int64_t ntiles;
   EvalLdsLayout L;
   double* tile_loss;  // [ntiles] per member
   int64_t off[kTensors + 1];
@@ -113,11 +109,9 @@ struct EvalArgs {
 struct RnnEvalArgs {
   int d, nin, B, time_input;
   double time_div;
-  double sm[8], ss[8], am[3], as[3];
-  const double* params;
-  const double *obs, *window, *ts, *target;  // ts is not read unless time_input
-  const int64_t* idx;                        // NULL: rows 0 .. N - 1
-  int64_t N, ntiles;
+  Norm norm;
+  Batch batch;
+  int64_t ntiles;
   double* tile_loss;
   int64_t off[kRnnTensors + 1];
   GroupStrides gs;

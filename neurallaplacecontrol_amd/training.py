@@ -115,7 +115,6 @@ class _FusedTrainer:
         self._v = torch.zeros(M, P, dtype=torch.float64, device=self._dev)
         self._step = 0
         self._ws = {}
-        self._eval_ws = {}
         self._arange = {}
         self._warned = False
 
@@ -213,14 +212,23 @@ class _FusedTrainer:
                 for p, v in zip(ps, self._views(self._flat, i)):
                     p.copy_(v)
 
-    def _workspace(self, N):
-        ws = self._ws.get(N)
+    def _workspace(self, N, entry=None):
+        """The device workspace of an N-row call, sized by the library's ``entry`` (the training step's unless given) and
+        kept for the next call of that size."""
+        entry = self._entries[0] if entry is None else entry
+        ws = self._ws.get((entry, N))
         if ws is None:
-            n = getattr(self._ctx.lib, self._entries[0])(self._ctx.h, self._M, N)
+            n = getattr(self._ctx.lib, entry)(self._ctx.h, self._M, N)
             if n < 0:
-                raise _lib.NlcError(n, self._entries[0])
-            ws = self._ws[N] = torch.empty((n + 7) // 8, dtype=torch.float64, device=self._dev)
+                raise _lib.NlcError(n, entry)
+            ws = self._ws[entry, N] = torch.empty((n + 7) // 8, dtype=torch.float64, device=self._dev)
         return ws
+
+    def _why_host(self):
+        """Whether the next call runs the fused kernels: None if so; else why not -- "" for a trainer that has had none
+        since construction (it warned then), or the library's reason for refusing the model's current descriptor, which
+        the caller hands to ``_host_path`` / ``_host_steps``."""
+        return self._sync_model() if self.fused else ""
 
     def _desc(self):
         return _lib.TrainDesc(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.clip_grad_norm)
@@ -284,9 +292,9 @@ class _FusedTrainer:
     # ------------------------------------------------------------------ API
     def loss_and_grad(self, bs0, ba0, bts, bsd):
         """Loss of the batch and ``p.grad`` of every parameter (train_utils.py:391-402); no update."""
-        why = None if not self.fused else self._sync_model()
-        if not self.fused or why is not None:
-            if why is not None:
+        why = self._why_host()
+        if why is not None:
+            if self.fused:
                 self._host_path(why)
             return self._host_loss_and_grad(bs0, ba0, bts, bsd)
         obs, win, ts, tgt, N, rows = self._group_data(bs0, ba0, bts, bsd)
@@ -314,9 +322,9 @@ class _FusedTrainer:
         None takes every row.  Forward only (``nlc_train_group_eval``): no ``p.grad``, no write-back, no moments, no step
         count, no host synchronisation.  A call the fused kernels do not take runs the model's ``no_grad`` forward +
         ``mse_loss`` instead, under the trainer's one warning."""
-        why = None if not self.fused else self._sync_model()
-        if not self.fused or why is not None:
-            if why is not None:
+        why = self._why_host()
+        if why is not None:
+            if self.fused:
                 self._host_path(why)
             return self._host_evaluate(s0, a0, ts, target, indices)
         obs, win, tsd, tgt, rows, stride = self._group_data(s0, a0, ts, target)
@@ -330,12 +338,7 @@ class _FusedTrainer:
             elif not (self._grouped and idx.dim() == 2 and idx.shape[0] == M):
                 raise ValueError(f"{self._name}.evaluate: indices must be (N,)" + (f" or ({M}, N)" if self._grouped else ""))
             idx, N = idx.contiguous(), int(idx.shape[1])
-        ws = self._eval_ws.get(N)
-        if ws is None:
-            n = getattr(self._ctx.lib, self._eval_entries[0])(self._ctx.h, M, N)
-            if n < 0:
-                raise _lib.NlcError(n, self._eval_entries[0])
-            ws = self._eval_ws[N] = torch.empty((n + 7) // 8, dtype=torch.float64, device=self._dev)
+        ws = self._workspace(N, self._eval_entries[0])
         self._gather()
         loss = torch.empty(M, dtype=torch.float64, device=self._dev)
         ctx = self._ctx
@@ -367,12 +370,12 @@ class _FusedTrainer:
         """One iteration of the reference's loop (train_utils.py:391-404); returns the loss before the update."""
         stacked = self._stacked(bs0)
         batches = lambda: [[self._member_data(i, stacked, bs0, ba0, bts, bsd)] for i in range(self._M)]  # noqa: E731
-        if not self.fused:
+        why = self._why_host()
+        if why is not None:
+            if self.fused:
+                return self._out(self._host_steps(why, batches())[:, 0])
             self._check_members()
             return self._out(torch.stack([self._fallback_step(*b[0], i=i) for i, b in enumerate(batches())]))
-        why = self._sync_model()
-        if why is not None:
-            return self._out(self._host_steps(why, batches())[:, 0])
         obs, win, ts, tgt, N, rows = self._group_data(bs0, ba0, bts, bsd)
         self._gather()
         loss = torch.empty(self._M, dtype=torch.float64, device=self._dev)

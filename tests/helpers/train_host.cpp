@@ -41,4 +41,12 @@ void nlc_t_blob_offsets(int d, int nin, int g, int h, int S, long long* out) {
   blob_offsets(d, nin, g, h, S, off);
   for (int i = 0; i <= kTensors; ++i) out[i] = (long long)off[i];
 }
+// the Fourier series' query points and prediction factor: t (n), k (nk) -> theta_s, phi_s (n, nk), factor (n)
+void nlc_t_fourier(double alpha, double log_tol, const double* t, long n, const int* k, int nk, double* th, double* ph,
+                   double* factor) {
+  for (long i = 0; i < n; ++i) {
+    for (int j = 0; j < nk; ++j) fourier_query_point(alpha, log_tol, t[i], k[j], &th[i * nk + j], &ph[i * nk + j]);
+    factor[i] = fourier_pred_factor(alpha, log_tol, t[i]);
+  }
+}
 }

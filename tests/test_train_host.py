@@ -105,6 +105,31 @@ def test_clip_coefficient_vs_clip_grad_norm(lib):
     assert out.max() == 1.0 and out.min() < 1.0
 
 
+def test_fourier_query_points_and_prediction_factor_vs_numpy(lib):
+    """fourier_query_point / fourier_pred_factor (both NL kernels call them) against the same float64 expressions in numpy
+    (torchlaplace's Fourier series at scale 2: T = 2 t, gamma = alpha - log(tol) / (2 T), s_k = gamma + i pi k / T, the
+    prediction's e^{gamma t} / T), at the models' alpha = 1e-3 and tol = 1e-9.  The arithmetic is the same in the same order,
+    so the two differ by their atan2 / asin / exp only: 4 ulp of the result (each library's is within 1; exp's argument
+    gamma t is below 6 here, so its rounding adds at most 1 more)."""
+    alpha, log_tol = 1e-3, float(np.log(1e-9))
+    t = np.array([0.05, 1.0, 7.3])
+    k = np.array([0, 1, 16, 128], dtype=np.int32)
+    th, ph, fac = np.empty((3, 4)), np.empty((3, 4)), np.empty(3)
+    f = lib.nlc_t_fourier
+    vp = ctypes.c_void_p
+    f.argtypes = [ctypes.c_double, ctypes.c_double, vp, ctypes.c_long, vp, ctypes.c_int, vp, vp, vp]
+    f(alpha, log_tol, t.ctypes.data, 3, k.ctypes.data, 4, th.ctypes.data, ph.ctypes.data, fac.ctypes.data)
+    T = 2.0 * t
+    gamma = alpha - log_tol / (2.0 * T)
+    im = np.pi * k.astype(np.float64)[None, :] / T[:, None]
+    a2 = gamma[:, None] * gamma[:, None] + im * im
+    refs = (np.arctan2(im, np.broadcast_to(gamma[:, None], im.shape)), np.arcsin((a2 - 1.0) / (a2 + 1.0)), np.exp(gamma * t) / T)
+    for got, ref in zip((th, ph, fac), refs):
+        assert np.isfinite(got).all()
+        assert (np.abs(got - ref) <= 4 * np.spacing(np.abs(ref))).all(), (got, ref)
+    assert (th[:, 0] == 0.0).all() and (th[:, 1:] > 0.0).all()  # k = 0 is the real axis
+
+
 @pytest.mark.parametrize("wd", [0.0, 1e-2])
 def test_adam_element_vs_torch_adam(lib, wd):
     """Three torch.optim.Adam steps (foreach off and on give the same element formula) against the host element update
