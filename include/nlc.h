@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 16
+#define NLC_ABI_VERSION 17
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -446,6 +446,23 @@ int64_t nlc_rnn_train_eval_workspace_bytes(nlc_ctx* ctx, int64_t N);
 int nlc_rnn_train_eval(nlc_ctx* ctx, const double* params_dev, const double* obs_dev, const double* window_dev,
                        const double* ts_dev, const double* target_dev, const int64_t* idx_dev /* NULL: rows 0..N-1 */,
                        int64_t N, int B, double* loss_dev, void* ws_dev);
+
+/* ---- snapshot selection: keep the parameters of the best loss seen so far, per member, on the device -- the reference saves
+ *      model.state_dict() whenever a window's loss beats best_loss (train_utils.py:439-448) and reports best_val_loss (:491).
+ *      Independent of the model family (the NL and RNN trainers share it) and of any model in the ctx.
+ *   loss_dev, best_loss_dev [M]; params_dev, best_params_dev [M][P]; best_tag_dev [M]; improved_dev [M] int32, or NULL.
+ *   Member m improves iff loss[m] < best_loss[m]: strict; a NaN loss never improves and a NaN best is never replaced; start
+ *   best_loss at +inf (+inf then never improves, -inf does once).  On improvement best_params[m][:] = params[m][:],
+ *   best_loss[m] = loss[m], best_tag[m] = tag, improved[m] = 1; otherwise nothing of member m is written but improved[m] = 0.
+ *   Two launches on the ctx's stream, no atomics, no host synchronisation: the copy (member on the grid's y axis, best_loss
+ *   read-only, a member that did not improve costs two 8-byte reads per workgroup), then one thread per member commits
+ *   best_loss, best_tag and improved.  Rows of odd P are copied with 8-byte accesses where they are not 16-byte aligned.
+ *   Refused on the host before any launch: a NULL pointer other than improved_dev, params_dev == best_params_dev:
+ *   NLC_ERR_BAD_ARG; M < 1 or P < 1: NLC_ERR_BAD_SHAPE; M > 65535 (the grid's y limit): NLC_ERR_UNSUPPORTED. */
+/* train_utils.py:439-448 (save on improvement), :491 (best_val_loss) */
+int nlc_train_keep_best(nlc_ctx* ctx, int M, int64_t P, const double* loss_dev, const double* params_dev,
+                        double* best_loss_dev, double* best_params_dev, int64_t* best_tag_dev, int64_t tag,
+                        int32_t* improved_dev /* (M), may be NULL */);
 
 /* ---- baseline model: NODE (train_utils.py:664-724; ODE function xOdeFuncInXAndU :637-661; factory :101-125;
  * node_hidden_units 270, node_augment_dim 1, node_method "euler": config.py:40-42).

@@ -83,6 +83,7 @@ SYMBOLS = [
     "nlc_rnn_train_group_eval",
     "nlc_rnn_train_eval_workspace_bytes",
     "nlc_rnn_train_eval",
+    "nlc_train_keep_best",
     "nlc_node_blob_size",
     "nlc_set_node_model",
     "nlc_node_forward",
@@ -315,6 +316,8 @@ def load_library():
             getattr(lib, fam + "_group_eval_workspace_bytes").argtypes = [vp, i32, i64]
             getattr(lib, fam + "_group_eval_workspace_bytes").restype = i64
             getattr(lib, fam + "_group_eval").argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]
+        # snapshot selection: M, P, loss, params, best_loss, best_params, best_tag, tag, improved
+        lib.nlc_train_keep_best.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, i64, vp]
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]
         lib.nlc_rnn_blob_size.restype = i64
         lib.nlc_set_rnn_model.argtypes = [vp, P(RnnDesc), vp, i64]

@@ -47,6 +47,13 @@ def _f64_ptr(t, offset=0):
     return C.c_void_p(t.data_ptr() + 8 * offset)
 
 
+def step_lr_after_epoch(lr, epochs_done, step_size, gamma):
+    """The learning rate after ``torch.optim.lr_scheduler.StepLR(opt, step_size, gamma).step()`` has brought the epoch count
+    to ``epochs_done``, from the rate before it: a chained multiply when the count reaches a multiple of ``step_size``
+    (StepLR's recursive form), not ``lr0 * gamma ** k``."""
+    return lr * gamma if epochs_done > 0 and epochs_done % int(step_size) == 0 else lr
+
+
 class _FusedTrainer:
     """``tr = Trainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)``
 
@@ -56,6 +63,11 @@ class _FusedTrainer:
       device, one loss per iteration;
     * ``tr.evaluate(s0, a0, ts, target, indices=None)`` -- the held-out loss (overlay.py:112-115): forward and MSE only, on
       the current weights; touches no gradient, moment or parameter;
+    * ``tr.keep_best(loss, tag=None)`` / ``tr.restore_best()`` -- the reference's save-on-improvement (train_utils.py:439-448)
+      on the device: the current weights become the snapshot of every member whose ``loss`` is below its ``tr.best_loss``
+      (``tr.best_tag``: the step count then), with no host read; ``restore_best`` writes the snapshot back;
+    * ``tr.fit(data, val=None, epochs=1, batch_size=16, eval_every=1000, ...)`` -- the reference's epoch loop
+      (train_utils.py:345-468) from ``run``, ``evaluate``, ``keep_best`` and a ``StepLR`` schedule, nothing read inside;
     * ``tr.state_dict()`` / ``tr.load_state_dict(sd)`` -- ``torch.optim.Adam``'s format.
 
     ``tr.lr`` may change between calls (what a ``StepLR`` would do).  After ``step()`` / ``run()`` the model's parameters
@@ -98,6 +110,7 @@ class _FusedTrainer:
         self._mparams = [[dict(mdl.named_parameters())[k] for k in mdl._BLOB_KEYS] for mdl in self.models]
         self._params = self._mparams[0]
         self._sizes = [p.numel() for p in self._params]
+        self._best = self._best_loss = self._best_tag = None  # keep_best's snapshot (M, P), its losses and tags (M,)
         self._fallback = None
         why = self._unsupported(model)
         if why is None:
@@ -513,6 +526,114 @@ class _FusedTrainer:
                     return host(str(err))
         self._scatter()
         return self._out(losses.t().contiguous())
+
+    # ------------------------------------------------------------------ the best weights
+    @property
+    def best_loss(self):
+        """The lowest loss ``keep_best`` has seen, per member: a float64 device tensor shaped like the trainer's losses
+        (+inf until a loss beat it; None before the first ``keep_best``)."""
+        return None if self._best is None else self._out(self._best_loss)
+
+    @property
+    def best_tag(self):
+        """The ``tag`` of the ``keep_best`` call that took the snapshot (int64, shaped like ``best_loss``; -1: none yet)."""
+        return None if self._best is None else self._out(self._best_tag)
+
+    def _step_count(self):
+        """Adam steps taken so far (one count for all parameters and members)."""
+        if self.fused:
+            return self._step
+        st = self._fallback[0].state.get(self._mparams[0][0])
+        return int(st["step"]) if st else 0
+
+    def keep_best(self, loss, tag=None):
+        """The reference's save-on-improvement (train_utils.py:439-448) without a host read: member m's current parameters
+        become its snapshot iff ``loss[m] < best_loss[m]`` (strict; a NaN never improves), and then ``best_loss[m] = loss[m]``
+        and ``best_tag[m] = tag``.  ``loss`` is a device tensor, 0-dim or (1,) for a single trainer and (M,) for a group --
+        what ``evaluate()`` returned, or a sum of ``run()``'s losses; ``tag`` defaults to the Adam step count.  Returns the
+        ``improved`` flags (int32, shaped like ``loss``).  The first call starts the snapshot from the current parameters
+        with ``best_loss`` +inf and ``best_tag`` -1, so ``restore_best`` is defined from then on.  Fused:
+        ``nlc_train_keep_best``, two launches on the trainer's stream; a non-fused trainer applies the same rule with
+        ``torch.where`` on a flat copy."""
+        M, P = self._M, sum(self._sizes)
+        loss = torch.as_tensor(loss).detach().to(self._dev, torch.float64).reshape(-1).contiguous()
+        if loss.numel() != M:
+            raise ValueError(f"{self._name}.keep_best: loss must hold {M} value" + ("s, one per member" if M > 1 else ""))
+        tag = self._step_count() if tag is None else int(tag)
+        first = self._best is None
+        if self.fused:
+            self._gather()
+            flat = self._flat
+        else:
+            flat = torch.cat([p.detach().reshape(-1) for ps in self._mparams for p in ps]).view(M, P)
+        if first:
+            self._best = flat.clone()
+            self._best_loss = torch.full((M,), float("inf"), dtype=torch.float64, device=self._dev)
+            self._best_tag = torch.full((M,), -1, dtype=torch.int64, device=self._dev)
+        if not self.fused:
+            better = loss < self._best_loss
+            self._best.copy_(torch.where(better[:, None], flat, self._best))
+            self._best_loss.copy_(torch.where(better, loss, self._best_loss))
+            self._best_tag.copy_(torch.where(better, torch.full_like(self._best_tag, tag), self._best_tag))
+            return self._out(better.to(torch.int32))
+        improved = torch.empty(M, dtype=torch.int32, device=self._dev)
+        ctx = self._ctx
+        with ctx.stream():  # the stream the loss was written on
+            ctx.check(ctx.lib.nlc_train_keep_best(
+                ctx.h, M, P, _f64_ptr(loss), _f64_ptr(flat), _f64_ptr(self._best_loss), _f64_ptr(self._best),
+                _i64_ptr(self._best_tag), tag, C.c_void_p(improved.data_ptr())))
+        return self._out(improved)
+
+    def restore_best(self):
+        """Write the snapshot back into the models' parameters, in place (their ``_version`` moves, so ``model.forward`` and
+        planners re-upload).  The Adam moments, the step count, ``best_loss`` and ``best_tag`` stay as they are."""
+        if self._best is None:
+            raise RuntimeError(f"{self._name}.restore_best: keep_best has not been called")
+        with torch.no_grad():
+            for i, ps in enumerate(self._mparams):
+                for p, v in zip(ps, self._views(self._best, i)):
+                    p.copy_(v)
+
+    def fit(self, data, val=None, *, epochs=1, batch_size=16, eval_every=1000, seed=0, step_lr=None, restore_best=True):
+        """The reference's epoch loop (train_utils.py:345-468) with nothing read on the host inside.
+
+        ``data`` is ``(s0, a0, sn, ts)`` or a callable ``epoch -> (s0, a0, sn, ts)`` (the reference regenerates the
+        synthetic dataset every epoch, :353-370).  Each epoch draws ``torch.randperm(R)`` on the device from a generator
+        seeded ``seed + epoch`` (one permutation for all members) and walks it in slices of ``eval_every * batch_size``
+        indices: ``run()`` on the slice, then the criterion -- ``evaluate(*val)`` with ``val = (s0, a0, ts, target)``, else
+        the slice's summed training losses (the reference's ``cum_loss``, :440) -- then ``keep_best(criterion,
+        tag=iterations so far)``.  A last slice without a full batch is skipped.  ``step_lr = (step_size, gamma)`` moves
+        ``tr.lr`` after every epoch as ``torch.optim.lr_scheduler.StepLR.step()`` would.  At the end the best weights are
+        restored unless ``restore_best`` is False.  No patience: the reference's is ``inf``.
+
+        Returns device tensors: ``train_loss`` (iters,) / (M, iters), ``criterion`` (checks,) / (M, checks), ``best_loss``
+        and ``best_iter`` (the iteration count at the best check)."""
+        bs, every = int(batch_size), int(eval_every)
+        if bs < 1 or every < 1:
+            raise ValueError(f"{self._name}.fit: batch_size and eval_every must be >= 1")
+        train_loss, criterion, done = [], [], 0
+        for epoch in range(int(epochs)):
+            s0, a0, sn, ts = data(epoch) if callable(data) else data
+            gen = torch.Generator(device=self._dev)
+            gen.manual_seed(int(seed) + epoch)
+            perm = torch.randperm(int(torch.as_tensor(s0).shape[-2]), device=self._dev, generator=gen)
+            for chunk in perm.split(every * bs):
+                if chunk.numel() < bs:
+                    continue
+                losses = self.run(s0, a0, sn, ts, chunk, bs)
+                done += chunk.numel() // bs
+                crit = self.evaluate(*val) if val is not None else losses.sum(-1)
+                self.keep_best(crit, tag=done)
+                train_loss.append(losses)
+                criterion.append(crit)
+            if step_lr is not None:
+                self.lr = step_lr_after_epoch(self.lr, epoch + 1, *step_lr)
+        if not criterion:
+            raise ValueError(f"{self._name}.fit: no epoch held a full batch")
+        if restore_best:
+            self.restore_best()
+        return {"train_loss": torch.cat(train_loss, dim=-1), "criterion": torch.stack(criterion, dim=-1),
+                "best_loss": self.best_loss.clone(), "best_iter": self.best_tag.clone()}
 
     # ------------------------------------------------------------------ optimiser state
     def _adam(self, i=0):

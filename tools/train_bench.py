@@ -35,6 +35,16 @@ parameter change (so the inference path's weight re-upload is inside), and (c) f
 --step-timeout; writes profiles/train_eval_bench.json unless --out says otherwise.
 
     python tools/train_bench.py --evaluate [--group 1 8 64] [--repeats 3]
+
+`--fit` times the validated loop (``fit``: ``run`` + ``evaluate`` + ``keep_best`` per slice, train_utils.py:345-468): both
+families, the single trainer and groups of --group members (default 1 8 64), batch 16, --eval-every 100, --fit-iters 2000, a
+validation set of 256 rows; (a) ``fit`` and (b) the host loop it replaces (a read of the criteria at every check, ``clone()``
+of a member's parameters on improvement), one warm-up and --repeats timed runs each (median and min .. max, ms).  Also
+nlc_train_keep_best alone at the family's parameter count: 100 enqueued calls ended by one synchronise, with every member
+improving at every call and with none.  One child process per (family, M) under --step-timeout; writes
+profiles/train_select_bench.json unless --out says otherwise.
+
+    python tools/train_bench.py --fit [--group 1 8 64] [--repeats 3] [--fit-iters 2000] [--eval-every 100]
 """
 
 import argparse
@@ -243,6 +253,67 @@ def time_evaluate(sizes, groups, repeats):
     return res
 
 
+def time_fit(M, iters, every, repeats, val_rows=256, bs=16):
+    """The --fit measurements of the family MODEL names at M members (1: the single trainer): ``fit`` against the host loop
+    a user writes without it, and nlc_train_keep_best alone."""
+    import ctypes as C
+
+    Group = nlc.RNNTrainerGroup if MODEL == "delta_t_rnn" else nlc.NLTrainerGroup
+    models = [make_model(seed=i) for i in range(M)]
+    tr = make_trainer(models[0]) if M == 1 else Group(models)
+    assert tr.fused
+    R = iters * bs
+    data = dataset(R)
+    vs0, va0, vsn, vts = dataset(val_rows, seed=1)
+    val = (vs0, va0, vts, vsn - vs0)
+
+    def host_loop():
+        """``.item()`` (one read of the M criteria) at every check, ``clone()`` of a member's parameters on improvement."""
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(0)
+        perm = torch.randperm(R, device="cuda", generator=gen)
+        best, kept = [float("inf")] * M, [None] * M
+        for chunk in perm.split(every * bs):
+            if chunk.numel() < bs:
+                continue
+            tr.run(*data, chunk, bs)
+            crit = tr.evaluate(*val).reshape(-1).tolist()
+            for m, c in enumerate(crit):
+                if c < best[m]:
+                    best[m], kept[m] = c, [p.detach().clone() for p in tr.models[m].parameters()]
+        with torch.no_grad():
+            for m, ps in enumerate(kept):
+                for p, q in zip(tr.models[m].parameters(), ps or ()):
+                    p.copy_(q)
+
+    res = {"M": M, "iters": iters, "eval_every": every, "batch": bs, "val_rows": val_rows, "P": int(tr._flat.shape[1]),
+           "fit": _timed(lambda: tr.fit(data, val, epochs=1, batch_size=bs, eval_every=every, seed=0), repeats),
+           "host_loop": _timed(host_loop, repeats)}
+    # the entry alone: 100 enqueued calls ended by one synchronise (inside _timed), every member improving at every call
+    # (a falling loss), and none (+inf)
+    P, ctx, calls = res["P"], tr._ctx, 100
+    flat = torch.randn(M, P, dtype=torch.float64, device="cuda")
+    best = torch.empty_like(flat)
+    best_loss = torch.empty(M, dtype=torch.float64, device="cuda")
+    best_tag = torch.empty(M, dtype=torch.int64, device="cuda")
+    improved = torch.empty(M, dtype=torch.int32, device="cuda")
+    falling = torch.arange(calls, 0, -1, dtype=torch.float64, device="cuda").repeat_interleave(M).contiguous()  # [calls][M]
+    never = torch.full((calls * M,), float("inf"), dtype=torch.float64, device="cuda")
+
+    def keep(losses):
+        best_loss.fill_(float("inf"))
+        with ctx.stream():
+            for k in range(calls):
+                ctx.check(ctx.lib.nlc_train_keep_best(
+                    ctx.h, M, P, C.c_void_p(losses.data_ptr() + 8 * k * M), C.c_void_p(flat.data_ptr()),
+                    C.c_void_p(best_loss.data_ptr()), C.c_void_p(best.data_ptr()), C.c_void_p(best_tag.data_ptr()), k,
+                    C.c_void_p(improved.data_ptr())))
+
+    res["keep_best_100_calls"] = {"all_improve": _timed(lambda: keep(falling), repeats), "none_improves": _timed(lambda: keep(never), repeats),
+                                  "bytes_copied_per_call_all_improve": 2 * 8 * M * P}
+    return res
+
+
 def flops_per_iter(bs):
     """Multiply-adds x 2 of the dense products (forward + the two backward products per weight matrix); transcendentals
     and element-wise work not counted."""
@@ -277,6 +348,9 @@ def main():
     ap.add_argument("--parent-tree", default=None, help="--group: a built checkout of the parent commit to time beside this one")
     ap.add_argument("--evaluate", action="store_true", help="time the held-out loss (evaluate) instead of training")
     ap.add_argument("--eval-sizes", type=int, nargs="+", default=[256, 156250], help="--evaluate: rows per call")
+    ap.add_argument("--fit", action="store_true", help="time fit() against the host loop it replaces, and nlc_train_keep_best")
+    ap.add_argument("--fit-iters", type=int, default=2000, help="--fit: iterations per timed run (one epoch)")
+    ap.add_argument("--eval-every", type=int, default=100, help="--fit: iterations between checks")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     MODEL, ILT, S = args.model, args.ilt_algorithm, args.terms
@@ -287,6 +361,9 @@ def main():
         bs, variant = int(args.child[0]), args.child[1]
         if variant == "evaluate":
             print("RESULT " + json.dumps(time_evaluate(args.eval_sizes, args.group or [1, 8, 64], args.repeats)))
+            return
+        if variant.startswith("fit"):
+            print("RESULT " + json.dumps(time_fit(int(variant[3:]), args.fit_iters, args.eval_every, args.repeats)))
             return
         if variant.startswith("group"):
             print("RESULT " + json.dumps(time_group(bs, args.run_iters, args.warmup, int(variant[5:]), args.repeats)))
@@ -328,6 +405,23 @@ def main():
             res[fam] = json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
         print(json.dumps(res))
         with open(args.out or os.path.join(REPO, "profiles", "train_eval_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
+    if args.fit:
+        res = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "families": {}}
+        for fam in ("nl", "delta_t_rnn"):
+            res["families"][fam] = {"workload": WORKLOADS[fam].replace("training step", "fit"), "groups": {}}
+            for M in args.group or [1, 8, 64]:
+                cmd = [sys.executable, os.path.abspath(__file__), "--model", fam, "--repeats", str(args.repeats), "--fit-iters",
+                       str(args.fit_iters), "--eval-every", str(args.eval_every), "--child", "16", f"fit{M}"]
+                out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
+                r = json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
+                r["host_loop_over_fit"] =r["host_loop"]["median_ms"] / r["fit"]["median_ms"]
+                res["families"][fam]["groups"][str(M)] = r
+                print(f"# {fam} M={M}: {r}", file=sys.stderr, flush=True)
+        print(json.dumps(res))
+        with open(args.out or os.path.join(REPO, "profiles", "train_select_bench.json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
         return
