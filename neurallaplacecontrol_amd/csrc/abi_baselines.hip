@@ -123,29 +123,16 @@ extern "C" int nlc_set_rnn_model(nlc_ctx* c, const nlc_rnn_desc* d, const double
   const double* Wo = b.take((int64_t)dd * F);
   const double* bo = b.take(dd);
   DeviceArena ar;
-  // input weights with the biases folded into input column 3 (x = [a_0..a_{nin-1}, 0.., 1]), as for the NL encoder
-  std::vector<double> Wihb((size_t)3 * H * 4, 0.0);
-  for (int r = 0; r < 3 * H; ++r) {
-    for (int j = 0; j < nin; ++j) Wihb[(size_t)r * 4 + j] = Wih[(size_t)r * nin + j];
-    Wihb[(size_t)r * 4 + 3] = bih[r] + (r < 2 * H ? bhh[r] : 0.0);
-  }
-  const size_t o_Wih = ar.push(pack_gru_chunked(Wihb.data(), 4, 4, H));
+  const size_t o_Wih = ar.push(pack_gru_chunked(fold_input_bias(Wih, bih, bhh, 3 * H, nin, 2 * H).data(), 4, 4, H));
   const size_t o_Whh = ar.push(pack_gru_chunked(Whh, H, H, H));
   const size_t o_bhn = ar.push(std::vector<double>(bhh + 2 * H, bhh + 3 * H));
   const size_t o_Wo = ar.push(pack_A(Wo, F, H, identity_rows(dd)));
-  double* base = nullptr;
-  NLC_HIP(c, hipMalloc((void**)&base, ar.host.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(base, ar.host.data(), ar.host.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(base);
-    return fail(c, NLC_ERR_HIP, std::string("weight upload: ") + hipGetErrorString(e));
-  }
-  NLC_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->rnn_base) hipFree(c->rnn_base);
-  c->rnn_base = base;
-  c->rd = *d;
-  RnnArgs& R = c->rnn;
-  R = RnnArgs{};
+  RnnModel m;
+  if (int rc = upload_arena(c, ar, m.arena)) return rc;
+  double* base = m.arena.get();
+  m.has = true;
+  m.rd = *d;
+  RnnArgs& R = m.rnn;
   R.nin = nin;
   R.d = dd;
   for (int j = 0; j < nin; ++j) {
@@ -156,8 +143,7 @@ extern "C" int nlc_set_rnn_model(nlc_ctx* c, const nlc_rnn_desc* d, const double
   R.Whhp = base + o_Whh;
   R.bhn = base + o_bhn;
   R.Wop = base + o_Wo;
-  RnnHead& Hd = c->rnn_head;
-  Hd = RnnHead{};
+  RnnHead& Hd = m.rnn_head;
   Hd.d = dd;
   for (int i = 0; i < dd; ++i) {
     for (int j = 0; j < dd; ++j) Hd.Wx[i * dd + j] = Wo[(size_t)i * F + H + j];
@@ -167,7 +153,8 @@ extern "C" int nlc_set_rnn_model(nlc_ctx* c, const nlc_rnn_desc* d, const double
     Hd.std[i] = d->state_std[i];
   }
   Hd.time_div = d->time_div;
-  c->has_rnn = true;
+  NLC_HIP(c, hipStreamSynchronize(c->stream));
+  c->rnnm = std::move(m);  // the previous model's arena goes with it
   if (c->has_mppi && c->pd.dynamics == NLC_DYN_DTRNN) c->has_mppi = false;  // re-configure against the new weights
   return NLC_OK;
   NLC_GUARD_END(c)
@@ -177,12 +164,12 @@ extern "C" int nlc_rnn_forward(nlc_ctx* c, const double* obs, const double* wind
                                double* out, void* ws) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (!c->has_rnn) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
+  if (!c->rnnm.has) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
   if (N < 0 || B < 1) return fail(c, NLC_ERR_BAD_SHAPE, "bad N or B");
   if (N == 0) return NLC_OK;
   if (!obs || !window || !ts || !out || !ws) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
-  RnnArgs a = c->rnn;
+  RnnArgs a = c->rnnm.rnn;
   a.mode = 0;
   a.window = window;
   a.N = N;
@@ -190,10 +177,10 @@ extern "C" int nlc_rnn_forward(nlc_ctx* c, const double* obs, const double* wind
   a.out = (double*)ws;
   {
     ProfScope ps(c, "rnn_encode_kernel");
-    NLC_HIP(c, launch_rnn_encode(a, c->rd.hidden, c->stream));
+    NLC_HIP(c, launch_rnn_encode(a, c->rnnm.rd.hidden, c->stream));
   }
   RnnForwardArgs f{};
-  f.head = c->rnn_head;
+  f.head = c->rnnm.rnn_head;
   f.N = N;
   f.obs = obs;
   f.q = (const double*)ws;
@@ -270,20 +257,13 @@ extern "C" int nlc_set_node_model(nlc_ctx* c, const nlc_node_desc* d, const doub
   const size_t o_b2 = ar.push(b2z);
   const size_t o_W3 = ar.push(pack_A(W3z.data(), Hp, Hp, identity_rows(16)));
   const size_t o_b3 = ar.push(b3z);
-  double* base = nullptr;
-  NLC_HIP(c, hipMalloc((void**)&base, ar.host.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(base, ar.host.data(), ar.host.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(base);
-    return fail(c, NLC_ERR_HIP, std::string("weight upload: ") + hipGetErrorString(e));
-  }
-  NLC_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->node_base) hipFree(c->node_base);
-  c->node_base = base;
-  c->nd = *d;
-  c->node_ht = ht;
-  NodeNetArgs& N = c->node;
-  N = NodeNetArgs{};
+  NodeModel m;
+  if (int rc = upload_arena(c, ar, m.arena)) return rc;
+  double* base = m.arena.get();
+  m.has = true;
+  m.nd = *d;
+  m.node_ht = ht;
+  NodeNetArgs& N = m.node;
   N.d = d->d;
   N.aug = d->augment_dim;
   N.nu = d->nu;
@@ -297,7 +277,8 @@ extern "C" int nlc_set_node_model(nlc_ctx* c, const nlc_node_desc* d, const doub
     N.state_mean[i] = i < d->d ? d->state_mean[i] : 0.0;
     N.state_std[i] = i < d->d ? d->state_std[i] : 1.0;
   }
-  c->has_node = true;
+  NLC_HIP(c, hipStreamSynchronize(c->stream));
+  c->nodem = std::move(m);  // the previous model's arena goes with it
   if (c->has_mppi && c->pd.dynamics == NLC_DYN_NODE) c->has_mppi = false;
   return NLC_OK;
   NLC_GUARD_END(c)
@@ -307,21 +288,21 @@ extern "C" int nlc_node_forward(nlc_ctx* c, const double* obs, const double* act
                                 double* out) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (!c->has_node) return fail(c, NLC_ERR_STATE, "nlc_set_node_model has not been called");
+  if (!c->nodem.has) return fail(c, NLC_ERR_STATE, "nlc_set_node_model has not been called");
   if (N < 0) return fail(c, NLC_ERR_BAD_SHAPE, "bad N");
   if (N == 0) return NLC_OK;
   if (!obs || !action || !out) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   NodeForwardArgs f{};
-  f.net = c->node;
-  f.net.nsub = node_substeps(ts_pred / c->nd.time_div, c->nd.step_size, f.net.hsub, 8);
+  f.net = c->nodem.node;
+  f.net.nsub = node_substeps(ts_pred / c->nodem.nd.time_div, c->nodem.nd.step_size, f.net.hsub, 8);
   if (f.net.nsub < 0) return fail(c, NLC_ERR_UNSUPPORTED, "prediction time needs more than 8 Euler sub-steps (or is <= 0)");
   f.N = N;
   f.obs = obs;
   f.action = action;
   f.out = out;
   ProfScope ps(c, "node_forward_kernel");
-  NLC_HIP(c, launch_node_forward(f, c->node_ht, c->stream));
+  NLC_HIP(c, launch_node_forward(f, c->nodem.node_ht, c->stream));
   return NLC_OK;
   NLC_GUARD_END(c)
 }

@@ -67,9 +67,7 @@ extern "C" int nlc_comm_destroy(nlc_ctx* c) {
     rccl()->CommDestroy(c->comm);
     c->comm = nullptr;
   }
-  if (c->comm_gather) hipFree(c->comm_gather);
-  c->comm_gather = nullptr;
-  c->comm_gather_n = 0;
+  c->comm_gather.reset();
   c->comm_world = 0;
   return NLC_OK;
 }
@@ -100,8 +98,9 @@ extern "C" int nlc_comm_self_test(nlc_ctx* c) {
   if (!c->comm) return fail(c, NLC_ERR_STATE, "nlc_comm_self_test: no communicator (nlc_comm_init)");
   NLC_HIP(c, hipSetDevice(c->device));
   const int G = c->comm_world;
-  double* dev = nullptr;
-  NLC_HIP(c, hipMalloc((void**)&dev, (size_t)(G + 1) * sizeof(double)));
+  DevDoubles buf;
+  NLC_HIP(c, (hipError_t)buf.hold((size_t)G + 1));
+  double* dev = buf.get();
   const double mine = (double)(c->comm_rank + 1);
   hipError_t e = hipMemcpyAsync(dev + G, &mine, sizeof(double), hipMemcpyHostToDevice, c->stream);
   int rc = 0;
@@ -109,7 +108,6 @@ extern "C" int nlc_comm_self_test(nlc_ctx* c) {
   std::vector<double> got((size_t)G, 0.0);
   if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(got.data(), dev, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(c->stream);
-  hipFree(dev);
   if (rc != 0) return fail(c, NLC_ERR_COMM, std::string("ncclAllGather: ") + rccl()->GetErrorString(rc));
   if (e != hipSuccess) return fail(c, NLC_ERR_HIP, std::string("nlc_comm_self_test: ") + hipGetErrorString(e));
   for (int g = 0; g < G; ++g)

@@ -20,8 +20,8 @@ thread_local std::string g_create_error;
 //           0.289 ms at 16 windows, 10.9 vs 11.7 ms at 655360).
 bool gru_use_coop(const nlc_ctx* c, int64_t n_windows) {
   if (c->opt.gru_coop >= 0) return c->opt.gru_coop != 0;
-  if (c->g == 128) return true;
-  return n_windows <= (c->g == 32 ? 8192 : 50000);
+  if (c->nl.g == 128) return true;
+  return n_windows <= (c->nl.g == 32 ? 8192 : 50000);
 }
 
 void prof_flush(nlc_ctx* c) {
@@ -45,28 +45,6 @@ bool is_device_ptr(const void* p) {
     return false;
   }
   return at.type == hipMemoryTypeDevice;
-}
-
-int hold_doubles(nlc_ctx* c, double*& p, size_t n, const double* upload, size_t* have) {
-  if (!have || n > *have) {
-    if (p) hipFree(p);
-    p = nullptr;
-    if (have) *have = 0;
-    NLC_HIP(c, hipMalloc((void**)&p, n * sizeof(double)));
-    if (have) *have = n;
-  }
-  if (upload) NLC_HIP(c, hipMemcpy(p, upload, n * sizeof(double), hipMemcpyHostToDevice));
-  return NLC_OK;
-}
-
-int hold_pinned_doubles(nlc_ctx* c, double*& p, size_t n, size_t* have) {
-  if (n <= *have) return NLC_OK;
-  if (p) hipHostFree(p);
-  p = nullptr;
-  *have = 0;
-  NLC_HIP(c, hipHostMalloc((void**)&p, n * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-  *have = n;
-  return NLC_OK;
 }
 
 }  // namespace host
@@ -121,26 +99,14 @@ extern "C" void nlc_destroy(nlc_ctx* c) {
   hipStreamSynchronize(c->stream);
   nlc_comm_destroy(c);
   prof_flush(c);
-  if (c->arena.base) hipFree(c->arena.base);
-  if (c->dbg_scratch) hipFree(c->dbg_scratch);
-  if (c->prefix.lists) hipFree(c->prefix.lists);
-  if (c->rnn_base) hipFree(c->rnn_base);
-  if (c->node_base) hipFree(c->node_base);
-  if (c->slot_dev) hipFree(c->slot_dev);
-  if (c->eidx_dev) hipFree(c->eidx_dev);
-  if (c->lin_tab) hipFree(c->lin_tab);
-  for (int i = 0; i < 2; ++i)
-    if (c->U[i]) hipFree(c->U[i]);
-  if (c->b1fold) hipFree(c->b1fold);
-  if (c->cp_lin) hipFree(c->cp_lin);
-  if (c->b1fold_fwd) hipFree(c->b1fold_fwd);
-  if (c->small) hipFree(c->small);
-  if (c->pinned) hipHostFree(c->pinned);
   c->dh.destroy();
   c->side.destroy();
-  for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
-  hipStreamDestroy(c->own_stream);
+  // the ctx's buffers are freed by their owners, here: with the device set, before the event pool and the stream go
+  const std::vector<hipEvent_t> event_pool = std::move(c->event_pool);
+  const hipStream_t own_stream = c->own_stream;
   delete c;
+  for (hipEvent_t e : event_pool) hipEventDestroy(e);
+  hipStreamDestroy(own_stream);
 }
 
 extern "C" const char* nlc_last_error(const nlc_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -230,7 +196,7 @@ extern "C" int nlc_set_option(nlc_ctx* c, const char* name, double value) {
     // encoder role)
     if (value != 0 && value != 1) return fail(c, NLC_ERR_BAD_ARG, "gru_gemm must be 0 (FP64 MFMA) or 1 (int8-sliced)");
     c->opt.gru_gemm = (int)value;
-    if (c->has_model) c->gru.use_i8 = (c->gru.i8_stream != nullptr && value == 1) ? 1 : 0;
+    if (c->nl.has) c->nl.gru.use_i8 = (c->nl.gru.i8_stream != nullptr && value == 1) ? 1 : 0;
   } else if (n == "dbg_gap_us") {
     if (value < 0 || value > 1.0e5) return fail(c, NLC_ERR_BAD_ARG, "dbg_gap_us must be in 0 .. 1e5");
     c->opt.dbg_gap_us = value;
@@ -260,27 +226,20 @@ extern "C" int nlc_get_stat(nlc_ctx* c, const char* name, double* out) {
   else if (n == "comm_rank") *out = c->comm ? (double)c->comm_rank : -1.0;
   else if (n == "fused_blocks_per_cu") *out = (double)c->fused.blocks_per_cu;
   else if (n == "fused_spin_limit") *out = (double)c->opt.fused_spin_limit;
-  else if (n == "model_nt3") *out = c->has_model ? (double)c->net.nt3 : 0.0;
-  else if (n == "gru_gemm") *out = (c->has_model && c->gru.use_i8) ? 1.0 : 0.0;  // 1: the encoder launches run kernels_gru_i8.hip
+  else if (n == "model_nt3") *out = c->nl.has ? (double)c->nl.net.nt3 : 0.0;
+  else if (n == "gru_gemm") *out = (c->nl.has && c->nl.gru.use_i8) ? 1.0 : 0.0;  // 1: the encoder launches run kernels_gru_i8.hip
   else if (n == "gru_prefix") *out = c->prefix.last_used ? 1.0 : 0.0;
-  else if (n.rfind("gru_prefix_windows_l", 0) == 0 && n.size() == 21 && n[20] >= '0' && n[20] <= '4') {
-    // the last command's windows by prefix length; waits for the command's launches
+  else if (n == "gru_prefix_table_tiles" || (n.rfind("gru_prefix_windows_l", 0) == 0 && n.size() == 21 && n[20] >= '0' && n[20] <= '4')) {
+    // the last command's windows by prefix length, or its 16-window tiles that started from the table (lists 1 ..) and took
+    // their first step's hidden-side products from it; waits for the command's launches
     *out = 0.0;
-    if (c->prefix.last_used && c->prefix.lists) {
+    if (c->prefix.last_used && c->prefix.lists.get()) {
       unsigned cnt[nlc::prefix::kLists] = {0};
       NLC_HIP(c, hipStreamSynchronize(c->stream));
-      NLC_HIP(c, hipMemcpy(cnt, c->prefix.lists, sizeof(cnt), hipMemcpyDeviceToHost));
-      *out = (double)cnt[n[20] - '0'];
-    }
-  } else if (n == "gru_prefix_table_tiles") {
-    // the last command's 16-window tiles that started from the table (lists 1 ..) and took their first step's hidden-side
-    // products from it; waits for the command's launches
-    *out = 0.0;
-    if (c->prefix.last_used && c->prefix.lists) {
-      unsigned cnt[nlc::prefix::kLists] = {0};
-      NLC_HIP(c, hipStreamSynchronize(c->stream));
-      NLC_HIP(c, hipMemcpy(cnt, c->prefix.lists, sizeof(cnt), hipMemcpyDeviceToHost));
-      for (int l = 1; l < nlc::prefix::n_lists(c->prefix.last_B); ++l) *out += (double)((cnt[l] + 15u) / 16u);
+      NLC_HIP(c, hipMemcpy(cnt, c->prefix.lists.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+      if (n.size() == 21) *out = (double)cnt[n[20] - '0'];
+      else
+        for (int l = 1; l < nlc::prefix::n_lists(c->prefix.last_B); ++l) *out += (double)((cnt[l] + 15u) / 16u);
     }
   } else if (n == "latents_offset") *out = (c->has_mppi && c->pd.dynamics == NLC_DYN_NL) ? (double)ws_layout(c).pa : -1.0;
   else if (n == "gru_i8_launches") *out = (double)nlc::gru_i8_launch_count();  // process-wide

@@ -12,25 +12,20 @@ void sphere_inputs(const nlc_ilt_desc& ilt, double tn, std::vector<double>& sph)
   // [theta_s(0..S-1) | phi_s(0..S-1)] of s_k = gamma + i pi k / T (Fourier, de Hoog) or s_k = node_k / t (linear algorithms)
   const int S = ilt.terms;
   sph.assign(2 * S, 0.0);
-  if (ilt.algo == NLC_ILT_FIXED_TALBOT || ilt.algo == NLC_ILT_STEHFEST) {
+  auto project = [&](int k, double re, double im) {
+    sph[k] = std::atan2(im, re);
+    const double a2 = re * re + im * im;
+    sph[S + k] = std::asin((a2 - 1.0) / (a2 + 1.0));
+  };
+  if (is_linear_ilt(ilt)) {
     std::vector<double> tab;
     linear_tables_host(ilt.algo, S, tab);
-    for (int k = 0; k < S; ++k) {
-      const double re = tab[k] / tn, im = tab[S + k] / tn;
-      sph[k] = std::atan2(im, re);
-      const double a2 = re * re + im * im;
-      sph[S + k] = std::asin((a2 - 1.0) / (a2 + 1.0));
-    }
+    for (int k = 0; k < S; ++k) project(k, tab[k] / tn, tab[S + k] / tn);
     return;
   }
   const double Tt = ilt.scale * tn;
   const double gamma = ilt.alpha - std::log(ilt.tol) / (ilt.scale * Tt);
-  for (int k = 0; k < S; ++k) {
-    const double im = M_PI * (double)k / Tt;
-    sph[k] = std::atan2(im, gamma);
-    const double a2 = gamma * gamma + im * im;
-    sph[S + k] = std::asin((a2 - 1.0) / (a2 + 1.0));
-  }
+  for (int k = 0; k < S; ++k) project(k, gamma, M_PI * (double)k / Tt);
 }
 
 int check_ilt(nlc_ctx* c, const nlc_ilt_desc* d) {
@@ -84,20 +79,20 @@ void linear_tables_host(int algo, int S, std::vector<double>& h) {
 }
 int linear_tables(nlc_ctx* c, const nlc_ilt_desc* d, const double** tab) {
   const int S = d->terms;
-  if (c->lin_tab && c->lin_algo == d->algo && c->lin_S == S) {
-    *tab = c->lin_tab;
+  if (c->nl.lin_tab.get() && c->nl.lin_algo == d->algo && c->nl.lin_S == S) {
+    *tab = c->nl.lin_tab.get();
     return NLC_OK;
   }
   std::vector<double> h;
   linear_tables_host(d->algo, S, h);
-  if (!c->lin_tab) NLC_HIP(c, hipMalloc((void**)&c->lin_tab, (size_t)4 * kMaxTerms * sizeof(double)));
+  NLC_HIP(c, (hipError_t)c->nl.lin_tab.grow((size_t)4 * kMaxTerms));
   // a kernel of an earlier call may still read the old tables -- on ANY stream the ctx was bound to since (the Python
   // mirror rebinds it to torch's current stream every call): this rare path waits for the whole device
   NLC_HIP(c, hipDeviceSynchronize());
-  NLC_HIP(c, hipMemcpy(c->lin_tab, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->lin_algo = d->algo;
-  c->lin_S = S;
-  *tab = c->lin_tab;
+  NLC_HIP(c, hipMemcpy(c->nl.lin_tab.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->nl.lin_algo = d->algo;
+  c->nl.lin_S = S;
+  *tab = c->nl.lin_tab.get();
   return NLC_OK;
 }
 
@@ -114,7 +109,7 @@ extern "C" int nlc_ilt_rep_inputs(nlc_ctx* c, const nlc_ilt_desc* d, const doubl
   if (!p || !t || !out) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   RepInArgs a{p, t, out, B, Tt, P, d->terms, t_batched, d->alpha, std::log(d->tol), d->scale, nullptr, nullptr, 1.0};
-  if (d->algo == NLC_ILT_FIXED_TALBOT || d->algo == NLC_ILT_STEHFEST) {
+  if (is_linear_ilt(*d)) {
     const double* tab = nullptr;
     if (int r = linear_tables(c, d, &tab)) return r;
     a.node_re = tab;
@@ -136,7 +131,7 @@ extern "C" int nlc_ilt_reconstruct(nlc_ctx* c, const nlc_ilt_desc* d, const doub
   if (!theta || !phi || !t || !x) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   IltArgs a = ilt_args(*d, theta, phi, t, x, N, dd);
-  if (d->algo == NLC_ILT_FIXED_TALBOT || d->algo == NLC_ILT_STEHFEST) {
+  if (is_linear_ilt(*d)) {
     const double* tab = nullptr;
     if (int r = linear_tables(c, d, &tab)) return r;
     // the Fourier kernels with the algorithm's per-term phase and weight (round 3): every term count has a tile there
@@ -148,8 +143,7 @@ extern "C" int nlc_ilt_reconstruct(nlc_ctx* c, const nlc_ilt_desc* d, const doub
     ProfScope ps(c, "ilt_fourier_kernel");
     NLC_HIP(c, launch_ilt_fourier(a, c->stream));
   } else {
-    if (d->terms < 3 || d->terms > 33 || d->terms % 2 == 0)
-      return fail(c, NLC_ERR_UNSUPPORTED, "dehoog: ilt_reconstruction_terms must be odd, 3 .. 33 (2M+1 terms)");
+    if (int r = check_dehoog_terms(c, *d)) return r;
     ProfScope ps(c, "ilt_dehoog_kernel");
     NLC_HIP(c, launch_ilt_dehoog(a, c->stream));
   }
@@ -163,8 +157,7 @@ extern "C" int nlc_ilt_reconstruct_backward(nlc_ctx* c, const nlc_ilt_desc* d, c
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
   if (int r = check_ilt(c, d)) return r;
-  if (d->algo == NLC_ILT_DEHOOG && (d->terms < 3 || d->terms > 33 || d->terms % 2 == 0))
-    return fail(c, NLC_ERR_UNSUPPORTED, "dehoog: ilt_reconstruction_terms must be odd, 3 .. 33 (2M+1 terms)");
+  if (int r = check_dehoog_terms(c, *d)) return r;
   if (N < 0 || dd < 1) return fail(c, NLC_ERR_BAD_SHAPE, "bad N or d");
   if (N == 0) return NLC_OK;
   if (!theta || !phi || !t || !grad_x || !grad_theta || !grad_phi) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
@@ -185,7 +178,7 @@ extern "C" int nlc_ilt_reconstruct_backward(nlc_ctx* c, const nlc_ilt_desc* d, c
     NLC_HIP(c, fe);
     return NLC_OK;
   }
-  if (d->algo == NLC_ILT_FIXED_TALBOT || d->algo == NLC_ILT_STEHFEST) {
+  if (is_linear_ilt(*d)) {
     const double* tab = nullptr;
     if (int r = linear_tables(c, d, &tab)) return r;
     IltLinBwdArgs la{theta, phi, t, grad_x, grad_theta, grad_phi, N, dd, d->terms, tab + 2 * d->terms, tab + 3 * d->terms};

@@ -26,7 +26,7 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
     return fail(c, NLC_ERR_UNSUPPORTED, "hidden_units must be 64, 128 or 256 (the kernels are instantiated for these widths)");
   if (d->d < 1 || d->d > 6) return fail(c, NLC_ERR_UNSUPPORTED, "state_dim must be in 1..6");
   if (d->nin < 1 || d->nin > NLC_MAX_NIN) return fail(c, NLC_ERR_UNSUPPORTED, "GRU input dim must be in 1..3");
-  const bool linear_algo = d->ilt.algo == NLC_ILT_FIXED_TALBOT || d->ilt.algo == NLC_ILT_STEHFEST;
+  const bool linear_algo = is_linear_ilt(d->ilt);
   if (!linear_algo && d->ilt.scale != 2.0) return fail(c, NLC_ERR_UNSUPPORTED, "fused model path needs ILT scale == 2");
   if (n != blob_size(d)) return fail(c, NLC_ERR_BAD_SHAPE, "weight blob size mismatch");
   NLC_HIP(c, hipSetDevice(c->device));
@@ -51,12 +51,7 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
 
   DeviceArena ar;
   // ---- GRU: layer-0 input weights with the bias folded into input column 3 (x = [a_0..a_{nin-1}, 0.., 1])
-  std::vector<double> Wih0b((size_t)3 * g * 4, 0.0);
-  for (int r = 0; r < 3 * g; ++r) {
-    for (int j = 0; j < nin; ++j) Wih0b[(size_t)r * 4 + j] = Wih0[(size_t)r * nin + j];
-    Wih0b[(size_t)r * 4 + 3] = bih0[r] + (r < 2 * g ? bhh0[r] : 0.0);
-  }
-  const size_t o_Wih0 = ar.push(pack_gru_chunked(Wih0b.data(), 4, 4, g));
+  const size_t o_Wih0 = ar.push(pack_gru_chunked(fold_input_bias(Wih0, bih0, bhh0, 3 * g, nin, 2 * g).data(), 4, 4, g));
   const size_t o_Whh0 = ar.push(pack_gru_chunked(Whh0, g, g, g));
   const size_t o_Wih1 = ar.push(pack_gru_chunked(Wih1, g, g, g));
   const size_t o_Whh1 = ar.push(pack_gru_chunked(Whh1, g, g, g));
@@ -95,8 +90,6 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   const int nt3 = nl_pick_nt3(ilt_tiles_needed(dd, S));
   if (nt3 < 0) return fail(c, NLC_ERR_UNSUPPORTED, "2*d*S too large for the fused kernel (max 25 output tiles)");
   const IltSlots slots = make_ilt_slots(dd, S, nt3);
-  c->slot_elems = slots.elems;
-  const int n_even_groups = slots.n_even_groups;
   std::vector<double> b3p((size_t)nt3 * 16, 0.0);
   for (size_t i = 0; i < slots.rowmap3.size(); ++i)
     if (slots.rowmap3[i] >= 0) b3p[i] = b3[slots.rowmap3[i]];
@@ -105,43 +98,30 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   const size_t o_Cp = ar.push(slots.Cp);
   const size_t o_prefix = ar.push(std::vector<double>(gru_prefix_arena_doubles(g), 0.0));  // filled by nlc_mppi_configure
 
-  // ---- upload
-  double* base = nullptr;
-  NLC_HIP(c, hipMalloc((void**)&base, ar.host.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(base, ar.host.data(), ar.host.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(base);
-    return fail(c, NLC_ERR_HIP, std::string("weight upload: ") + hipGetErrorString(e));
-  }
+  // ---- upload into a model of its own: the ctx's is replaced once nothing can fail any more
+  NlModel m;
+  if (int rc = upload_arena(c, ar, m.arena)) return rc;
   {
     std::vector<int> slot((size_t)nt3 * 8, -1);
     for (size_t i = 0; i < slot.size(); ++i)
       if (slots.elems[i].first >= 0) slot[i] = slots.elems[i].first * S + slots.elems[i].second;
-    if (c->slot_dev) hipFree(c->slot_dev);
-    c->slot_dev = nullptr;
-    NLC_HIP(c, hipMalloc((void**)&c->slot_dev, slot.size() * sizeof(int)));
-    NLC_HIP(c, hipMemcpy(c->slot_dev, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = upload(c, m.slot_dev, slot.data(), slot.size())) return rc;
     std::vector<int> eidx((size_t)dd * S, 0);
     for (size_t i = 0; i < slot.size(); ++i)
       if (slot[i] >= 0) eidx[slot[i]] = (int)i;
-    if (c->eidx_dev) hipFree(c->eidx_dev);
-    c->eidx_dev = nullptr;
-    NLC_HIP(c, hipMalloc((void**)&c->eidx_dev, eidx.size() * sizeof(int)));
-    NLC_HIP(c, hipMemcpy(c->eidx_dev, eidx.data(), eidx.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = upload(c, m.eidx_dev, eidx.data(), eidx.size())) return rc;
   }
-  NLC_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->arena.base) hipFree(c->arena.base);
-  c->arena = std::move(ar);
-  c->arena.base = base;
-  c->md = *d;
-  c->g = g;
-  c->S = S;
-  c->P = P;
-  c->W1s_host = std::move(W1s);
-  c->b1_host.assign(b1, b1 + h);
+  double* base = m.arena.get();
+  m.has = true;
+  m.md = *d;
+  m.g = g;
+  m.S = S;
+  m.P = P;
+  m.W1s_host = std::move(W1s);
+  m.b1_host.assign(b1, b1 + h);
+  m.slot_elems = slots.elems;
 
-  GruArgs& G = c->gru;
-  G = GruArgs{};
+  GruArgs& G = m.gru;
   G.nin = nin;
   for (int j = 0; j < nin; ++j) {
     G.mean[j] = d->action_mean[j];
@@ -161,13 +141,12 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   if (i8_ok) G.i8_stream = (const signed char*)(base + o_i8);
   G.use_i8 = (i8_ok && c->opt.gru_gemm == 1) ? 1 : 0;  // (nlc_get_stat "gru_gemm" tells whether the option took)
 
-  NlNetArgs& N = c->net;
-  N = NlNetArgs{};
+  NlNetArgs& N = m.net;
   N.d = dd;
   N.S = S;
   N.h = h;
   N.nt3 = nt3;
-  N.n_even_groups = n_even_groups;
+  N.n_even_groups = slots.n_even_groups;
   N.W1p = base + o_W1p;
   N.W1s = base + o_W1s;
   N.b1 = base + o_b1;
@@ -184,41 +163,47 @@ extern "C" int nlc_set_model(nlc_ctx* c, const nlc_model_desc* d, const double* 
   N.log_tol = std::log(d->ilt.tol);
   N.scale = d->ilt.scale;
   N.time_div = d->time_div;
+  // ---- commit.  The previous model's buffers go with it, and so does what was derived from its weights inside the group:
+  // the constant-time forward's folded bias (fwd_tn), the planner's folds and the linear tables' cache
+  NLC_HIP(c, hipStreamSynchronize(c->stream));
+  c->nl = std::move(m);
   c->prefix.arena_off = o_prefix;
   c->prefix.why_not = "gru_prefix: planner not configured";
-  c->has_model = true;
-  c->fwd_tn = -1.0;  // the constant-time forward's folded bias belongs to the previous weights
   c->has_mppi = false;  // a planner configured against the previous weights must be re-configured
   return NLC_OK;
   NLC_GUARD_END(c)
 }
 
-extern "C" int nlc_gru_encode(nlc_ctx* c, const double* window, int64_t N, int B, double* out) {
-  if (!c) return NLC_ERR_BAD_ARG;
-  NLC_GUARD_BEGIN
-  if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
-  if (N < 0 || B < 1) return fail(c, NLC_ERR_BAD_SHAPE, "bad N or B");
-  if (N == 0) return NLC_OK;
-  if (!window || !out) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
-  NLC_HIP(c, hipSetDevice(c->device));
-  GruArgs a = c->gru;
+int nlc::host::encode_windows(nlc_ctx* c, const double* window, int64_t N, int B, double* out) {
+  GruArgs a = c->nl.gru;
   a.mode = 0;
   a.window = window;
   a.N = N;
   a.B = B;
   a.out = out;
   ProfScope ps(c, "gru_encode_kernel");
-  NLC_HIP(c, launch_gru_encode(a, c->g, c->stream, gru_use_coop(c, a.N)));
+  NLC_HIP(c, launch_gru_encode(a, c->nl.g, c->stream, gru_use_coop(c, a.N)));
   return NLC_OK;
+}
+
+extern "C" int nlc_gru_encode(nlc_ctx* c, const double* window, int64_t N, int B, double* out) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  NLC_GUARD_BEGIN
+  if (!c->nl.has) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
+  if (N < 0 || B < 1) return fail(c, NLC_ERR_BAD_SHAPE, "bad N or B");
+  if (N == 0) return NLC_OK;
+  if (!window || !out) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
+  NLC_HIP(c, hipSetDevice(c->device));
+  return encode_windows(c, window, N, B, out);
   NLC_GUARD_END(c)
 }
 
 extern "C" int64_t nlc_model_workspace_bytes(nlc_ctx* c, int64_t N) {
   if (N < 0) return -1;
   int64_t n = N * 2 + 64;  // GRU latents
-  if (c && c->has_model && c->md.ilt.algo == NLC_ILT_DEHOOG) n += 2 * N * c->md.d * c->S + 64;  // F_k re/im
-  if (c && c->has_model && (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST))
-    n += 2 * N * c->md.d * c->S + 2 * N * c->S + 128;  // theta / phi rows + per-row sphere inputs
+  if (c && c->nl.has && c->nl.md.ilt.algo == NLC_ILT_DEHOOG) n += 2 * N * c->nl.md.d * c->nl.S + 64;  // F_k re/im
+  if (c && c->nl.has && is_linear_ilt(c->nl.md.ilt))
+    n += 2 * N * c->nl.md.d * c->nl.S + 2 * N * c->nl.S + 128;  // theta / phi rows + per-row sphere inputs
   return n * (int64_t)sizeof(double);
 }
 
@@ -226,46 +211,30 @@ extern "C" int nlc_model_forward_const_t(nlc_ctx* c, const double* obs, const do
                                          int B, double* out, void* ws) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
-  if (c->md.ilt.algo != NLC_ILT_FOURIER) return fail(c, NLC_ERR_UNSUPPORTED, "constant-time forward: fourier models only");
+  if (!c->nl.has) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
+  if (c->nl.md.ilt.algo != NLC_ILT_FOURIER) return fail(c, NLC_ERR_UNSUPPORTED, "constant-time forward: fourier models only");
   if (N < 0 || B < 1) return fail(c, NLC_ERR_BAD_SHAPE, "bad N or B");
   if (!(ts_pred > 0.0)) return fail(c, NLC_ERR_BAD_ARG, "ts_pred must be > 0");
   if (N == 0) return NLC_OK;
   if (!obs || !window || !out || !ws) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
-  const double tn = ts_pred / c->md.time_div;
-  const int h = c->md.h, S = c->S;
-  if (!c->b1fold_fwd) NLC_HIP(c, hipMalloc((void**)&c->b1fold_fwd, h * sizeof(double)));
-  if (tn != c->fwd_tn) {
+  const double tn = ts_pred / c->nl.md.time_div;
+  const int h = c->nl.md.h;
+  NLC_HIP(c, (hipError_t)c->nl.b1fold_fwd.grow(h));
+  if (tn != c->nl.fwd_tn) {
     // fold the constant sphere inputs of layer 1 into its bias, as nlc_mppi_configure does for the planner
     // an earlier upload may still read the host copy, and a forward launched on a PREVIOUSLY bound stream may still read
     // the folded bias: a new query time is rare, so wait for the whole device
     NLC_HIP(c, hipDeviceSynchronize());
-    std::vector<double> sph;
-    sphere_inputs(c->md.ilt, tn, sph);
-    c->fwd_fold_host.resize(h);
-    for (int r = 0; r < h; ++r) {
-      double acc = c->b1_host[r];
-      for (int j = 0; j < 2 * S; ++j) acc += c->W1s_host[(size_t)r * 2 * S + j] * sph[j];
-      c->fwd_fold_host[r] = acc;
-    }
-    NLC_HIP(c, hipMemcpyAsync(c->b1fold_fwd, c->fwd_fold_host.data(), h * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    c->fwd_tn = tn;
+    fold_b1(c->nl, tn, c->nl.fwd_fold_host);
+    NLC_HIP(c, hipMemcpyAsync(c->nl.b1fold_fwd.get(), c->nl.fwd_fold_host.data(), h * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->nl.fwd_tn = tn;
   }
   double* pa = (double*)ws;
-  {
-    GruArgs a = c->gru;
-    a.mode = 0;
-    a.window = window;
-    a.N = N;
-    a.B = B;
-    a.out = pa;
-    ProfScope ps(c, "gru_encode_kernel");
-    NLC_HIP(c, launch_gru_encode(a, c->g, c->stream, gru_use_coop(c, a.N)));
-  }
+  if (int rc = encode_windows(c, window, N, B, pa)) return rc;
   ForwardArgs f{};
-  f.net = c->net;
-  f.net.b1 = c->b1fold_fwd;
+  f.net = c->nl.net;
+  f.net.b1 = c->nl.b1fold_fwd.get();
   f.N = N;
   f.obs = obs;
   f.pa = pa;
@@ -283,50 +252,40 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
                                  int B, double* out, void* ws) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
-  if (c->md.ilt.algo == NLC_ILT_DEHOOG && (c->S < 3 || c->S > 33 || c->S % 2 == 0))
-    return fail(c, NLC_ERR_UNSUPPORTED, "dehoog: ilt_reconstruction_terms must be odd, 3 .. 33 (2M+1 terms)");
+  if (!c->nl.has) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
+  if (int rc = check_dehoog_terms(c, c->nl.md.ilt)) return rc;
   if (N < 0 || B < 1) return fail(c, NLC_ERR_BAD_SHAPE, "bad N or B");
   if (N == 0) return NLC_OK;
   if (!obs || !window || !ts || !out || !ws) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   double* pa = (double*)ws;
-  {
-    GruArgs a = c->gru;
-    a.mode = 0;
-    a.window = window;
-    a.N = N;
-    a.B = B;
-    a.out = pa;
-    ProfScope ps(c, "gru_encode_kernel");
-    NLC_HIP(c, launch_gru_encode(a, c->g, c->stream, gru_use_coop(c, a.N)));
-  }
-  if (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST) {
+  if (int rc = encode_windows(c, window, N, B, pa)) return rc;
+  RepFuncArgs rf{};  // the representation launch of the staged algorithms, as far as they share it
+  rf.net = c->nl.net;
+  rf.N = N;
+  rf.obs = obs;
+  rf.obs_stride = c->nl.md.d;
+  rf.obs_per_sample = 1;
+  rf.pa = pa;
+  rf.pa_stride = 2;
+  rf.general_t = 1;
+  rf.slot = c->nl.slot_dev.get();
+  if (is_linear_ilt(c->nl.md.ilt)) {
     // staged (round 3): per-row query points s_k = node_k / t on the algorithm's own contour -> sphere inputs, the
     // representation kernel on explicit sphere inputs -> (theta, phi) rows, the Fourier kernel's stream with the algorithm's
     // per-term phase and weight
-    const int S = c->S, dd = c->md.d;
+    const int S = c->nl.S, dd = c->nl.md.d;
     double* sph = pa + (N * 2 + 63) / 64 * 64;
     double* th = sph + (N * 2 * S + 63) / 64 * 64;
     double* ph = th + N * dd * S;
     const double* tab = nullptr;
-    if (int r = linear_tables(c, &c->md.ilt, &tab)) return r;
+    if (int r = linear_tables(c, &c->nl.md.ilt, &tab)) return r;
     {
-      RepInArgs ra{ts, ts, sph, N, 1, 0, S, 1, c->md.ilt.alpha, std::log(c->md.ilt.tol), c->md.ilt.scale, tab, tab + S, c->md.time_div};
+      RepInArgs ra{ts, ts, sph, N, 1, 0, S, 1, c->nl.md.ilt.alpha, std::log(c->nl.md.ilt.tol), c->nl.md.ilt.scale, tab, tab + S, c->nl.md.time_div};
       ProfScope ps(c, "rep_inputs_kernel");
       NLC_HIP(c, launch_rep_inputs(ra, c->stream));
     }
-    RepFuncArgs rf{};
-    rf.net = c->net;
-    rf.N = N;
-    rf.obs = obs;
-    rf.obs_stride = dd;
-    rf.obs_per_sample = 1;
     rf.Kep = 1;
-    rf.pa = pa;
-    rf.pa_stride = 2;
-    rf.general_t = 1;
-    rf.slot = c->slot_dev;
     rf.fre = th;
     rf.fim = ph;
     rf.sph = sph;
@@ -336,46 +295,36 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
       ProfScope ps(c, "nl_repfunc_kernel");
       NLC_HIP(c, launch_nl_repfunc(rf, c->stream));
     }
-    IltArgs ia = ilt_args(c->md.ilt, th, ph, ts, out, N, dd);
-    ia.t_div = c->md.time_div;
+    IltArgs ia = ilt_args(c->nl.md.ilt, th, ph, ts, out, N, dd);
+    ia.t_div = c->nl.md.time_div;
     ia.lin_wr = tab + 2 * S;
     ia.lin_wi = tab + 3 * S;
     ProfScope ps(c, "ilt_linear_stream_kernel");
     NLC_HIP(c, launch_ilt_fourier(ia, c->stream));
     return NLC_OK;
   }
-  if (c->md.ilt.algo == NLC_ILT_DEHOOG) {
+  if (c->nl.md.ilt.algo == NLC_ILT_DEHOOG) {
     // staged: representation function -> F_k (re, im) in HBM -> de Hoog kernel (nonlinear in F: not an MFMA epilogue)
     double* fre = pa + (N * 2 + 63) / 64 * 64;
-    double* fim = fre + N * c->md.d * c->S;
-    RepFuncArgs rf{};
-    rf.net = c->net;
-    rf.N = N;
-    rf.obs = obs;
-    rf.obs_stride = c->md.d;
-    rf.obs_per_sample = 1;
-    rf.pa = pa;
-    rf.pa_stride = 2;
+    double* fim = fre + N * c->nl.md.d * c->nl.S;
     rf.ts = ts;
-    rf.general_t = 1;
-    rf.slot = c->slot_dev;
     rf.fre = fre;
     rf.fim = fim;
     {
       ProfScope ps(c, "nl_repfunc_kernel");
       NLC_HIP(c, launch_nl_repfunc(rf, c->stream));
     }
-    IltArgs ia = ilt_args(c->md.ilt, nullptr, nullptr, ts, out, N, c->md.d);
+    IltArgs ia = ilt_args(c->nl.md.ilt, nullptr, nullptr, ts, out, N, c->nl.md.d);
     ia.fre = fre;
     ia.fim = fim;
-    ia.t_div = c->md.time_div;
+    ia.t_div = c->nl.md.time_div;
     ProfScope ps(c, "ilt_dehoog_kernel");
     NLC_HIP(c, launch_ilt_dehoog(ia, c->stream));
     return NLC_OK;
   }
   {
     ForwardArgs f{};
-    f.net = c->net;
+    f.net = c->nl.net;
     f.N = N;
     f.obs = obs;
     f.pa = pa;
@@ -392,27 +341,27 @@ extern "C" int nlc_model_forward(nlc_ctx* c, const double* obs, const double* wi
 extern "C" int nlc_rep_func(nlc_ctx* c, const double* rep_in, int64_t N, double* theta, double* phi) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
+  if (!c->nl.has) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
   if (N < 0) return fail(c, NLC_ERR_BAD_SHAPE, "bad N");
   if (N == 0) return NLC_OK;
   if (!rep_in || !theta || !phi) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
-  const int64_t row = 2 * (int64_t)c->S + c->P;
+  const int64_t row = 2 * (int64_t)c->nl.S + c->nl.P;
   RepFuncArgs rf{};
-  rf.net = c->net;
+  rf.net = c->nl.net;
   for (int i = 0; i < NLC_MAX_D; ++i) {  // the rows hold the latent p as the module sees it: no normalisation
     rf.net.state_mean[i] = 0.0;
     rf.net.state_std[i] = 1.0;
   }
   rf.N = N;
-  rf.obs = rep_in + 2 * c->S;
+  rf.obs = rep_in + 2 * c->nl.S;
   rf.obs_stride = row;
   rf.obs_per_sample = 1;
   rf.Kep = 1;
-  rf.pa = rep_in + 2 * c->S + c->md.d;
+  rf.pa = rep_in + 2 * c->nl.S + c->nl.md.d;
   rf.pa_stride = row;
   rf.general_t = 1;
-  rf.slot = c->slot_dev;
+  rf.slot = c->nl.slot_dev.get();
   rf.fre = theta;
   rf.fim = phi;
   rf.sph = rep_in;

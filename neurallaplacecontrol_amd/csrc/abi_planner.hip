@@ -39,25 +39,24 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
   if (d->dynamics == NLC_DYN_EXTERNAL) {
     // the caller owns dynamics and cost
   } else if (d->dynamics == NLC_DYN_NL) {
-    if (!c->has_model) return fail(c, NLC_ERR_STATE, "NL dynamics need nlc_set_model first");
+    if (!c->nl.has) return fail(c, NLC_ERR_STATE, "NL dynamics need nlc_set_model first");
     // nin == nu + 1: an encode_obs_time model; the rollout appends the harness's constant time channel
-    if (c->md.d != d->d || (c->md.nin != d->nu && c->md.nin != d->nu + 1))
+    if (c->nl.md.d != d->d || (c->nl.md.nin != d->nu && c->nl.md.nin != d->nu + 1))
       return fail(c, NLC_ERR_BAD_SHAPE, "model state/action dims differ from the planner's");
-    if (c->md.ilt.algo == NLC_ILT_DEHOOG && (c->S < 3 || c->S > 33 || c->S % 2 == 0))
-      return fail(c, NLC_ERR_UNSUPPORTED, "dehoog: ilt_reconstruction_terms must be odd, 3 .. 33 (2M+1 terms)");
+    if (int rc = check_dehoog_terms(c, c->nl.md.ilt)) return rc;
   } else if (d->dynamics == NLC_DYN_ORACLE) {
     if (d->delay < 0 || d->delay > d->B - 1)
       return fail(c, NLC_ERR_BAD_ARG, "oracle dynamics: delay must be in [0, action_buffer_size-1]");
   } else if (d->dynamics == NLC_DYN_DTRNN) {
-    if (!c->has_rnn) return fail(c, NLC_ERR_STATE, "Delta-t RNN dynamics need nlc_set_rnn_model first");
-    if (c->rd.d != d->d || c->rd.nin != d->nu)
+    if (!c->rnnm.has) return fail(c, NLC_ERR_STATE, "Delta-t RNN dynamics need nlc_set_rnn_model first");
+    if (c->rnnm.rd.d != d->d || c->rnnm.rd.nin != d->nu)
       return fail(c, NLC_ERR_BAD_SHAPE, "model state/action dims differ from the planner's");
   } else if (d->dynamics == NLC_DYN_NODE) {
-    if (!c->has_node) return fail(c, NLC_ERR_STATE, "NODE dynamics need nlc_set_node_model first");
-    if (c->nd.d != d->d || c->nd.nu != d->nu)
+    if (!c->nodem.has) return fail(c, NLC_ERR_STATE, "NODE dynamics need nlc_set_node_model first");
+    if (c->nodem.nd.d != d->d || c->nodem.nd.nu != d->nu)
       return fail(c, NLC_ERR_BAD_SHAPE, "model state/action dims differ from the planner's");
     double h[8];
-    if (node_substeps(d->ts_pred / c->nd.time_div, c->nd.step_size, h, 8) < 0)
+    if (node_substeps(d->ts_pred / c->nodem.nd.time_div, c->nodem.nd.step_size, h, 8) < 0)
       return fail(c, NLC_ERR_UNSUPPORTED, "ts_pred needs more than 8 Euler sub-steps (or is <= 0)");
   } else {
     return fail(c, NLC_ERR_UNSUPPORTED, "unknown dynamics id");
@@ -65,42 +64,36 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
   NLC_HIP(c, hipSetDevice(c->device));
   const size_t un = (size_t)E * d->T * d->nu;
   for (int i = 0; i < 2; ++i) {
-    if (int rc = hold_doubles(c, c->U[i], un)) return rc;
+    NLC_HIP(c, (hipError_t)c->U[i].hold(un));
     // on the ctx's stream and waited for below: hipMemset runs asynchronously on the NULL stream, which is not
     // ordered against a non-blocking stream -- it could land after the nlc_mppi_set_U copy that follows configure
-    NLC_HIP(c, hipMemsetAsync(c->U[i], 0, un * sizeof(double), c->stream));
+    NLC_HIP(c, hipMemsetAsync(c->U[i].get(), 0, un * sizeof(double), c->stream));
   }
   NLC_HIP(c, hipStreamSynchronize(c->stream));
   c->ucur = 0;
-  if (int rc = hold_doubles(c, c->small, un + 2 * (size_t)E)) return rc;
+  NLC_HIP(c, (hipError_t)c->small.hold(un + 2 * (size_t)E));
   c->pin = plan::pin_layout(E, d->d, d->B, d->nu, d->T);
-  if (int rc = hold_pinned_doubles(c, c->pinned, c->pin.total, &c->pinned_n)) return rc;
-  std::memset(c->pinned, 0, c->pinned_n * sizeof(double));
+  NLC_HIP(c, (hipError_t)c->pinned.grow(c->pin.total));
+  std::memset(c->pinned.get(), 0, c->pinned.size() * sizeof(double));
   c->pd = *d;
   c->pd.E = E;
   c->nblk = weight_tiles(d->K);
   if (d->dynamics == NLC_DYN_NL) {
     // constant prediction time => the 2S sphere-coordinate inputs of layer 1 are constants: fold into the bias
-    c->tn = d->ts_pred / c->md.time_div;
-    std::vector<double> sph;
-    sphere_inputs(c->md.ilt, c->tn, sph);
-    const int h = c->md.h, S = c->S;
-    std::vector<double> bf(h);
-    for (int r = 0; r < h; ++r) {
-      double acc = c->b1_host[r];
-      for (int j = 0; j < 2 * S; ++j) acc += c->W1s_host[(size_t)r * 2 * S + j] * sph[j];
-      bf[r] = acc;
-    }
-    if (int rc = hold_doubles(c, c->b1fold, bf.size(), bf.data())) return rc;
-    if (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST) {
+    c->tn = d->ts_pred / c->nl.md.time_div;
+    const int S = c->nl.S;
+    std::vector<double> bf;
+    fold_b1(c->nl, c->tn, bf);
+    if (int rc = upload(c, c->nl.b1fold, bf.data(), bf.size())) return rc;
+    if (is_linear_ilt(c->nl.md.ilt)) {
       // coefficient fragments of the LIN rollout instances: lane -> (dim = lane & 15, slot 4 g + (lane >> 4)), as Cp
       std::vector<double> tab;
-      linear_tables_host(c->md.ilt.algo, S, tab);
-      const int ng = 2 * c->net.nt3;
+      linear_tables_host(c->nl.md.ilt.algo, S, tab);
+      const int ng = 2 * c->nl.net.nt3;
       std::vector<double> cp((size_t)2 * ng * 64, 0.0);
       for (int g = 0; g < ng; ++g)
         for (int lane = 0; lane < 64; ++lane) {
-          const auto el = c->slot_elems[(size_t)4 * g + (lane >> 4)];
+          const auto el = c->nl.slot_elems[(size_t)4 * g + (lane >> 4)];
           if (el.first != (lane & 15)) continue;
           cp[(size_t)g * 64 + lane] = tab[2 * S + el.second] / c->tn;
           cp[(size_t)(ng + g) * 64 + lane] = -tab[3 * S + el.second] / c->tn;
@@ -111,7 +104,7 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
           if (std::fabs(cp[i]) > std::fabs(cp[at])) at = i;
         cp[at] *= c->opt.test_lin_coeff_scale;  // (the largest weight: Stehfest's span many orders of magnitude)
       }
-      if (int rc = hold_doubles(c, c->cp_lin, cp.size(), cp.data())) return rc;
+      if (int rc = upload(c, c->nl.cp_lin, cp.data(), cp.size())) return rc;
     }
   }
   c->prefix.last_used = false;
@@ -130,8 +123,8 @@ namespace host {
 // fixed Talbot / Stehfest models whose rollout runs on the LIN instances of the rollout kernels (launch_nl_rollout_ht<HT, true>,
 // at the widths of with_width in nlc_kernels.h) instead of the staged path
 bool linear_on_rollout_kernels(const nlc_ctx* c) {
-  return c->has_model && (c->md.ilt.algo == NLC_ILT_FIXED_TALBOT || c->md.ilt.algo == NLC_ILT_STEHFEST) &&
-         (c->md.h == 64 || c->md.h == 128 || c->md.h == 256) && c->opt.linear_fused != 0;
+  return c->nl.has && is_linear_ilt(c->nl.md.ilt) &&
+         (c->nl.md.h == 64 || c->nl.md.h == 128 || c->nl.md.h == 256) && c->opt.linear_fused != 0;
 }
 
 WsLayout ws_layout(const nlc_ctx* c) {
@@ -153,11 +146,11 @@ WsLayout ws_layout(const nlc_ctx* c) {
   w.ccarry = take(d.dynamics == NLC_DYN_NL ? KE * 2 : 0);
   // (the staged buffers are laid out for every non-Fourier model, also when a linear-algorithm model runs on the LIN rollout
   // instances: the layout must not depend on an option that can change after the caller sized its workspace)
-  const bool staged = d.dynamics == NLC_DYN_NL && c->md.ilt.algo != NLC_ILT_FOURIER;
+  const bool staged = d.dynamics == NLC_DYN_NL && c->nl.md.ilt.algo != NLC_ILT_FOURIER;
   // slot-major (8*nt3, KE), >= KE*d*S; the persistent step chain cuts it into private (8*nt3) x 64 blocks, one per 64 samples
   const size_t KE64 = (KE + 63) / 64 * 64;
-  w.fre = take(staged ? KE64 * 8 * (size_t)c->net.nt3 : 0);
-  w.fim = take(staged ? KE64 * 8 * (size_t)c->net.nt3 : 0);
+  w.fre = take(staged ? KE64 * 8 * (size_t)c->nl.net.nt3 : 0);
+  w.fim = take(staged ? KE64 * 8 * (size_t)c->nl.net.nt3 : 0);
   w.dx = take(staged ? KE * d.d : 0);
   w.tconst = take(staged ? 8 : 0);
   w.rq = take(d.dynamics == NLC_DYN_DTRNN ? KE * d.T * d.d : 0);  // hidden part of linear_out, (T, K, d)
@@ -251,7 +244,7 @@ int launch_shift_perturb(nlc_ctx* c, RolloutCall& call) {
   return NLC_OK;
 }
 
-// the samples and the cost terms of the command's rollout, whichever body runs it; c->U[c->ucur] is the shifted sequence
+// the samples and the cost terms of the command's rollout, whichever body runs it; c->U[c->ucur].get() is the shifted sequence
 SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call) {
   const nlc_mppi_desc& d = c->pd;
   SampleCostArgs a{};
@@ -264,7 +257,7 @@ SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call) {
   a.state0 = call.state_dev;
   a.perturbed = call.buf->perturbed;
   a.noise = call.buf->noise;
-  a.U = c->U[c->ucur];
+  a.U = c->U[c->ucur].get();
   for (int i = 0; i < NLC_MAX_NU * NLC_MAX_NU; ++i) a.sigma_inv[i] = d.noise_sigma_inv[i];
   a.lambda_ = d.lambda_;
   a.u_scale = d.u_scale;
@@ -274,7 +267,7 @@ SampleCostArgs sample_cost_args(const nlc_ctx* c, const RolloutCall& call) {
   return a;
 }
 
-// the command's sampling / bounding, apart from the inline inputs; c->U[c->ucur] is the sequence BEFORE the shift
+// the command's sampling / bounding, apart from the inline inputs; c->U[c->ucur].get() is the sequence BEFORE the shift
 PerturbArgs perturb_args(const nlc_ctx* c, const nlc_mppi_buffers* buf, int rng, uint64_t seed, uint64_t counter) {
   const nlc_mppi_desc& d = c->pd;
   PerturbArgs p{};
@@ -285,8 +278,8 @@ PerturbArgs perturb_args(const nlc_ctx* c, const nlc_mppi_buffers* buf, int rng,
   p.k_offset = d.k_offset;
   p.T = d.T;
   p.nu = d.nu;
-  p.U_old = c->U[c->ucur];
-  p.U_new = c->U[c->ucur ^ 1];
+  p.U_old = c->U[c->ucur].get();
+  p.U_new = c->U[c->ucur ^ 1].get();
   p.noise = buf->noise;
   p.perturbed = buf->perturbed;
   p.actions = buf->actions;
@@ -306,7 +299,7 @@ PerturbArgs perturb_args(const nlc_ctx* c, const nlc_mppi_buffers* buf, int rng,
   return p;
 }
 
-// phase 2 over the partial rows of G ranks; c->U[c->ucur] is the shifted sequence.  The pinned action, the sequence word and
+// phase 2 over the partial rows of G ranks; c->U[c->ucur].get() is the shifted sequence.  The pinned action, the sequence word and
 // the sync block's clean-up are the caller's decisions.
 MergeArgs merge_args(nlc_ctx* c, const nlc_mppi_buffers* buf, const double* gathered, int G, int rank) {
   const nlc_mppi_desc& d = c->pd;
@@ -321,11 +314,11 @@ MergeArgs merge_args(nlc_ctx* c, const nlc_mppi_buffers* buf, const double* gath
   m.lambda_ = d.lambda_;
   m.u_scale = d.u_scale;
   m.gathered = gathered;
-  m.U = c->U[c->ucur];
+  m.U = c->U[c->ucur].get();
   m.cost_nz = buf->cost_nz;
   m.omega = buf->omega;
-  m.action = buf->action ? buf->action : c->small;
-  m.beta_eta = c->small + (size_t)d.E * d.T * d.nu;
+  m.action = buf->action ? buf->action : c->small.get();
+  m.beta_eta = c->small.get() + (size_t)d.E * d.T * d.nu;
   m.cost = buf->cost_total;
   m.status_pinned = pin_merge_status_word(c);
   return m;
@@ -343,7 +336,7 @@ extern "C" int nlc_mppi_set_U(nlc_ctx* c, const double* U) {
   if (!c->has_mppi) return fail(c, NLC_ERR_STATE, "planner not configured");
   if (!U) return fail(c, NLC_ERR_BAD_ARG, "NULL U");
   NLC_HIP(c, hipSetDevice(c->device));
-  NLC_HIP(c, hipMemcpyAsync(c->U[c->ucur], U, (size_t)c->pd.E * c->pd.T * c->pd.nu * sizeof(double), hipMemcpyHostToDevice,
+  NLC_HIP(c, hipMemcpyAsync(c->U[c->ucur].get(), U, (size_t)c->pd.E * c->pd.T * c->pd.nu * sizeof(double), hipMemcpyHostToDevice,
                             c->stream));
   NLC_HIP(c, hipStreamSynchronize(c->stream));
   return NLC_OK;
@@ -366,7 +359,7 @@ extern "C" int nlc_mppi_get_U(nlc_ctx* c, double* U) {
   if (!c->has_mppi) return fail(c, NLC_ERR_STATE, "planner not configured");
   if (!U) return fail(c, NLC_ERR_BAD_ARG, "NULL U");
   NLC_HIP(c, hipSetDevice(c->device));
-  NLC_HIP(c, hipMemcpyAsync(U, c->U[c->ucur], (size_t)c->pd.E * c->pd.T * c->pd.nu * sizeof(double), hipMemcpyDeviceToHost,
+  NLC_HIP(c, hipMemcpyAsync(U, c->U[c->ucur].get(), (size_t)c->pd.E * c->pd.T * c->pd.nu * sizeof(double), hipMemcpyDeviceToHost,
                             c->stream));
   NLC_HIP(c, hipStreamSynchronize(c->stream));
   return NLC_OK;
@@ -394,8 +387,8 @@ static int stage_inputs(nlc_ctx* c, RolloutCall& call, const double* state, cons
     // small inputs go through pinned staging (truly asynchronous copies).  The staging slots are rewritten
     // only after the previous command's copies out of them have completed (stage_ev).
     if (c->side.stage_ev) NLC_HIP(c, hipEventSynchronize(c->side.stage_ev));
-    double* pin_state = c->pinned + c->pin.state;
-    double* pin_abuf = c->pinned + c->pin.abuf;
+    double* pin_state = c->pinned.get() + c->pin.state;
+    double* pin_abuf = c->pinned.get() + c->pin.abuf;
     std::memcpy(pin_abuf, abuf_host, (size_t)d.B * d.nu * sizeof(double));
     if (state_per_sample) {
       // (K, d) from caller-owned pageable memory: wait for the copy, the source may be a temporary
@@ -420,12 +413,12 @@ static int rollout_baseline(nlc_ctx* c, RolloutCall& call) {
   const SampleCostArgs sc = sample_cost_args(c, call);
   if (d.dynamics == NLC_DYN_NODE) {
     NodeRolloutArgs r{sc};
-    r.net = c->node;
-    r.net.nsub = node_substeps(d.ts_pred / c->nd.time_div, c->nd.step_size, r.net.hsub, 8);
+    r.net = c->nodem.node;
+    r.net.nsub = node_substeps(d.ts_pred / c->nodem.nd.time_div, c->nodem.nd.step_size, r.net.hsub, 8);
     ProfScope ps(c, "node_rollout_kernel");
-    NLC_HIP(c, launch_node_rollout(r, c->node_ht, c->stream));
+    NLC_HIP(c, launch_node_rollout(r, c->nodem.node_ht, c->stream));
   } else if (d.dynamics == NLC_DYN_DTRNN) {
-    RnnArgs g = c->rnn;
+    RnnArgs g = c->rnnm.rnn;
     g.mode = 1;
     g.perturbed = call.buf->perturbed;
     g.abuf = call.abuf_dev;
@@ -438,10 +431,10 @@ static int rollout_baseline(nlc_ctx* c, RolloutCall& call) {
     g.out = call.ws + call.w.rq;
     {
       ProfScope ps(c, "rnn_encode_kernel");
-      NLC_HIP(c, launch_rnn_encode(g, c->rd.hidden, c->stream));
+      NLC_HIP(c, launch_rnn_encode(g, c->rnnm.rd.hidden, c->stream));
     }
     RnnRolloutArgs r{sc};
-    r.head = c->rnn_head;
+    r.head = c->rnnm.rnn_head;
     r.q = g.out;
     r.ts = d.ts_pred;
     ProfScope ps(c, "rnn_rollout_kernel");
@@ -523,10 +516,10 @@ static int mppi_rollout_impl(nlc_ctx* c, const double* state, int state_per_samp
       std::memcpy(L.abuf_in, p.abuf_in, sizeof(L.abuf_in));
     }
   }
-  c->ucur ^= 1;  // from here on c->U[c->ucur] is the shifted sequence the kernels below produce
+  c->ucur ^= 1;  // from here on c->U[c->ucur].get() is the shifted sequence the kernels below produce
   call.inline_inputs = inline_inputs;
   const bool lin_direct = d.dynamics == NLC_DYN_NL && linear_on_rollout_kernels(c);
-  const bool nl_fourier = d.dynamics == NLC_DYN_NL && (c->md.ilt.algo == NLC_ILT_FOURIER || lin_direct);  // one rollout kernel
+  const bool nl_fourier = d.dynamics == NLC_DYN_NL && (c->nl.md.ilt.algo == NLC_ILT_FOURIER || lin_direct);  // one rollout kernel
   // (the fused planner body's argument block carries the sampling arguments to the device itself: rollout_nl launches the
   // perturb kernel on the paths that still need it)
   if (!nl_fourier)
@@ -567,11 +560,11 @@ int native_all_gather(nlc_ctx* c, const nlc_mppi_buffers* buf, int G, int rank, 
   if (G != c->comm_world || rank != c->comm_rank) return fail(c, NLC_ERR_BAD_ARG, "G / rank differ from the communicator's");
   if (!buf->partials) return fail(c, NLC_ERR_BAD_ARG, "NULL buf->partials");
   const size_t per_rank = (size_t)d.E * (size_t)(2 + d.T * d.nu);
-  if (int rc = hold_doubles(c, c->comm_gather, per_rank * (size_t)G, nullptr, &c->comm_gather_n)) return rc;
+  NLC_HIP(c, (hipError_t)c->comm_gather.grow(per_rank * (size_t)G));
   ProfScope ps(c, "rccl_all_gather");
-  const int rc = rccl()->AllGather(buf->partials, c->comm_gather, per_rank, kNcclFloat64, c->comm, c->stream);
+  const int rc = rccl()->AllGather(buf->partials, c->comm_gather.get(), per_rank, kNcclFloat64, c->comm, c->stream);
   if (rc != 0) return fail(c, NLC_ERR_COMM, std::string("ncclAllGather: ") + rccl()->GetErrorString(rc));
-  *gathered = c->comm_gather;
+  *gathered = c->comm_gather.get();
   return NLC_OK;
 }
 
@@ -645,7 +638,7 @@ extern "C" int nlc_mppi_finish(nlc_ctx* c, const double* gathered, int G, int ra
   MergeArgs m = merge_args(c, buf, gathered, G, rank);
   // the returned action is stored by the kernel straight into pinned (host-coherent) memory: the only thing left
   // on the host's critical path is the wait for it
-  double* pin_act = c->pinned + c->pin.action;
+  double* pin_act = c->pinned.get() + c->pin.action;
   m.action_pinned = action_host ? pin_act : nullptr;
   unsigned long long* seq_word = pin_seq_word(c);
   const bool spin = action_host && c->opt.host_spin && d.E == 1 && !c->profiling;
@@ -690,7 +683,7 @@ extern "C" int nlc_mppi_finish(nlc_ctx* c, const double* gathered, int G, int ra
     c->ucur ^= 1;  // back to the control sequence before this command's shift
     const FusedState::LastCommand L = c->fused.last;
     if (int rc = mppi_rollout_impl(c, L.state_in, L.state_per_sample, L.abuf_in, buf, L.rng, L.seed, L.counter, true)) return rc;
-    m.U = c->U[c->ucur];
+    m.U = c->U[c->ucur].get();
     if (G == 1) {
       m.gathered = buf->partials;
     } else if (native) {

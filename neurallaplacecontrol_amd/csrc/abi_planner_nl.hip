@@ -24,11 +24,11 @@ int dbg_between(nlc_ctx* c) {
   if (c->opt.dbg_l2_mb > 0.0) {
     const size_t bytes = (size_t)(c->opt.dbg_l2_mb * 1048576.0);
     const size_t n = bytes / 8 + 1;  // the sweep's doubles and its sink
-    if (c->dbg_scratch_n < n) {
-      if (int rc = hold_doubles(c, c->dbg_scratch, n, nullptr, &c->dbg_scratch_n)) return rc;
-      NLC_HIP(c, hipMemsetAsync(c->dbg_scratch, 0, n * sizeof(double), c->stream));
+    if (c->dbg_scratch.size() < n) {
+      NLC_HIP(c, (hipError_t)c->dbg_scratch.hold(n));
+      NLC_HIP(c, hipMemsetAsync(c->dbg_scratch.get(), 0, n * sizeof(double), c->stream));
     }
-    hipLaunchKernelGGL(dbg_touch_kernel, dim3(2048), dim3(256), 0, c->stream, c->dbg_scratch, bytes / 8, c->dbg_scratch + bytes / 8);
+    hipLaunchKernelGGL(dbg_touch_kernel, dim3(2048), dim3(256), 0, c->stream, c->dbg_scratch.get(), bytes / 8, c->dbg_scratch.get() + bytes / 8);
   }
   return NLC_OK;
 }
@@ -100,7 +100,7 @@ int gru_encode_chunks(nlc_ctx* c, GruArgs& g, int64_t KE, int C, int Tc, bool co
     g.N = KE * g.Tc;
     {
       ProfScope ps(c, "gru_encode_kernel", c->side.gru_stream, true);
-      NLC_HIP(c, launch_gru_encode(g, c->g, c->side.gru_stream, coop, lds_pad));
+      NLC_HIP(c, launch_gru_encode(g, c->nl.g, c->side.gru_stream, coop, lds_pad));
     }
     NLC_HIP(c, hipEventRecord(c->side.ev_gru[ch], c->side.gru_stream));
   }
@@ -153,8 +153,8 @@ int launch_dehoog_chain(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc,
   ca.net = r.net;
   ca.pa = pa;
   ca.tn = c->tn;
-  ca.slot = c->slot_dev;
-  ca.eidx = c->eidx_dev;
+  ca.slot = c->nl.slot_dev.get();
+  ca.eidx = c->nl.eidx_dev.get();
   ca.fre = call.ws + call.w.fre;  // one private (8 nt3) x 64 block per 64 samples
   ca.fim = call.ws + call.w.fim;
   ca.phases = c->opt.dehoog_chain_phases;
@@ -188,18 +188,18 @@ int launch_staged_steps(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc,
   rf.pa_stride = (int64_t)d.T * 2;
   rf.tn = c->tn;
   rf.general_t = 0;
-  rf.slot = c->slot_dev;
+  rf.slot = c->nl.slot_dev.get();
   rf.fre = ws + w.fre;
   rf.fim = ws + w.fim;
   // F travels slot-major between the two kernels of a step: four 128-B runs per store instruction of the MFMA
   // epilogue, one full line per de Hoog load (kernels_ilt.hip, FMODE 2)
   rf.slot_major = 1;
-  rf.split = c->md.h == 128 && c->opt.repfunc_split != 0;
-  IltArgs ia = ilt_args(c->md.ilt, nullptr, nullptr, tconst, ws + w.dx, KE, d.d);
+  rf.split = c->nl.md.h == 128 && c->opt.repfunc_split != 0;
+  IltArgs ia = ilt_args(c->nl.md.ilt, nullptr, nullptr, tconst, ws + w.dx, KE, d.d);
   ia.fre = rf.fre;
   ia.fim = rf.fim;
   ia.t_stride = 0;  // one prediction time for every sample
-  ia.eidx = c->eidx_dev;
+  ia.eidx = c->nl.eidx_dev.get();
   StepTailArgs st{sc};
   st.d = d.d;
   st.x = r.xcarry;
@@ -212,7 +212,7 @@ int launch_staged_steps(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc,
     NLC_HIP(c, hipEventRecord(side.ev_fork, c->stream));  // behind the GRU encode and the staged inputs
     for (int h = 1; h < P; ++h) NLC_HIP(c, hipStreamWaitEvent(side.aux_streams[h - 1], side.ev_fork, 0));
   }
-  const size_t f_per_sample = 8 * (size_t)c->net.nt3;
+  const size_t f_per_sample = 8 * (size_t)c->nl.net.nt3;
   RepFuncArgs rfs[4];
   IltArgs ias[4];
   StepTailArgs sts[4];
@@ -293,12 +293,12 @@ int launch_staged_steps(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc,
 int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc, GruArgs& g, RolloutArgs& r, double* pa) {
   const nlc_mppi_desc& d = c->pd;
   const int64_t KE = call.KE;
-  const bool dehoog = c->md.ilt.algo == NLC_ILT_DEHOOG;
+  const bool dehoog = c->nl.md.ilt.algo == NLC_ILT_DEHOOG;
   const double* lin_tab = nullptr;
   if (!dehoog)
-    if (int rc = linear_tables(c, &c->md.ilt, &lin_tab)) return rc;
+    if (int rc = linear_tables(c, &c->nl.md.ilt, &lin_tab)) return rc;
   // option "dehoog_chain": -1 auto, 0 the staged launches, 1 (2: two workgroups per CU) the persistent kernel required
-  const bool chain_ok = dehoog && d.E == 1 && nl_dehoog_chain_available(c->md.h, c->net.nt3, c->S);
+  const bool chain_ok = dehoog && d.E == 1 && nl_dehoog_chain_available(c->nl.md.h, c->nl.net.nt3, c->nl.S);
   if (c->opt.dehoog_chain >= 1 && !chain_ok)
     return fail(c, NLC_ERR_UNSUPPORTED, "dehoog_chain: single planner, hidden_units 128 and 17 or 33 de Hoog terms only");
   int calib_variant = -1;
@@ -314,7 +314,7 @@ int rollout_nl_staged(nlc_ctx* c, RolloutCall& call, const SampleCostArgs& sc, G
     g.Tc = d.T;
     g.N = KE * d.T;
     ProfScope ps(c, "gru_encode_kernel");
-    NLC_HIP(c, launch_gru_encode(g, c->g, c->stream, gru_use_coop(c, g.N)));
+    NLC_HIP(c, launch_gru_encode(g, c->nl.g, c->stream, gru_use_coop(c, g.N)));
   }
   c->last_body = chain ? 5 : 4;
   if (chain) {
@@ -348,7 +348,7 @@ int rollout_nl_fused(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r, 
   const int rng = call.rng;
   const bool inline_inputs = call.inline_inputs;
   PerturbArgs& p = call.p;
-  const plan::FusedSchedule s = plan::fused_schedule(c->prop.multiProcessorCount, KE, d.T, c->md.h, c->fused.blocks_per_cu,
+  const plan::FusedSchedule s = plan::fused_schedule(c->prop.multiProcessorCount, KE, d.T, c->nl.md.h, c->fused.blocks_per_cu,
                                                      c->fused.blocks_per_cu3, c->opt.fused);
   FusedArgs f{};
   f.r = r;
@@ -392,7 +392,7 @@ int rollout_nl_fused(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs& r, 
   if (fc.inline_weights) f.w = make_weight_args(c, buf);
   {
     ProfScope ps(c, "nl_plan_fused_kernel");
-    NLC_HIP(c, launch_nl_plan_fused(f, c->g, s.grid, s.built, c->stream));
+    NLC_HIP(c, launch_nl_plan_fused(f, c->nl.g, s.grid, s.built, c->stream));
   }
   *weights_done = fc.inline_weights != 0;
   return NLC_OK;
@@ -413,16 +413,16 @@ int gru_prefix_begin(nlc_ctx* c, RolloutCall& call, const GruArgs& g, int64_t N,
   if (why) return c->opt.gru_prefix == 1 ? fail(c, NLC_ERR_UNSUPPORTED, why) : NLC_OK;
   const int64_t stride = (N + 63) / 64 * 64;
   const size_t need = 64 + (size_t)prefix::kLists * (size_t)stride / 2;  // doubles: a row of counters, then 32-bit lists
-  if (need > ps.lists_n) {
+  if (need > ps.lists.size()) {
     NLC_HIP(c, hipStreamSynchronize(c->stream));  // (an earlier command may still read the buffer this replaces)
-    if (int rc = hold_doubles(c, ps.lists, need, nullptr, &ps.lists_n)) return rc;
+    NLC_HIP(c, (hipError_t)ps.lists.hold(need));
   }
-  double* base = c->arena.base + ps.arena_off;
+  double* base = c->nl.arena.get() + ps.arena_off;
   px->table = base;
-  px->out_tab = base + (size_t)prefix::kEntries * 2 * c->g;
-  px->products = base + gru_prefix_products_off(c->g);
-  px->counts = reinterpret_cast<unsigned*>(ps.lists);
-  px->lists = reinterpret_cast<unsigned*>(ps.lists + 64);
+  px->out_tab = base + (size_t)prefix::kEntries * 2 * c->nl.g;
+  px->products = base + gru_prefix_products_off(c->nl.g);
+  px->counts = reinterpret_cast<unsigned*>(ps.lists.get());
+  px->lists = reinterpret_cast<unsigned*>(ps.lists.get() + 64);
   px->list_stride = stride;
   px->img_max = ps.img_max;
   px->img_min = ps.img_min;
@@ -461,11 +461,11 @@ int rollout_nl_two_launch(nlc_ctx* c, RolloutCall& call, GruArgs& g, RolloutArgs
         NLC_HIP(c, launch_gru_prefix_index(g, px, c->stream));
       }
       ProfScope ps(c, "gru_encode_kernel");
-      NLC_HIP(c, launch_gru_encode_prefix(g, px, c->g, c->stream));
+      NLC_HIP(c, launch_gru_encode_prefix(g, px, c->nl.g, c->stream));
       c->prefix.last_used = true;
     } else {
       ProfScope ps(c, "gru_encode_kernel");
-      NLC_HIP(c, launch_gru_encode(g, c->g, c->stream, gru_use_coop(c, g.N)));
+      NLC_HIP(c, launch_gru_encode(g, c->nl.g, c->stream, gru_use_coop(c, g.N)));
     }
     if (c->opt.dbg_gap_us > 0.0 || c->opt.dbg_l2_mb > 0.0)
       if (int rc3 = dbg_between(c)) return rc3;
@@ -499,22 +499,22 @@ int nlc::host::gru_prefix_configure(nlc_ctx* c) {
   ps.last_used = false;
   const double img[2] = {prefix::bound_image(d.u_max[0], d.u_scale), prefix::bound_image(d.u_min[0], d.u_scale)};
   bool finite = true;
-  for (double v : img) finite = finite && std::isfinite((d.u_scale * v - c->gru.mean[0]) / c->gru.std[0]);
-  ps.why_not = prefix::out_of_scope(d.nu, c->md.nin, d.has_bounds, d.B, 0, finite);
+  for (double v : img) finite = finite && std::isfinite((d.u_scale * v - c->nl.gru.mean[0]) / c->nl.gru.std[0]);
+  ps.why_not = prefix::out_of_scope(d.nu, c->nl.md.nin, d.has_bounds, d.B, 0, finite);
   if (ps.why_not) return NLC_OK;
   ps.img_max = prefix::bits_of(img[0]);
   ps.img_min = prefix::bits_of(img[1]);
   std::vector<double> syn((size_t)16 * d.B, 0.0);  // column c, GRU step s (window element B - 1 - s): bit s of c picks u_min
   for (int col = 0; col < 16; ++col)
     for (int s = 0; s < prefix::cap(d.B); ++s) syn[(size_t)col * d.B + (d.B - 1 - s)] = img[(col >> s) & 1];
-  double* base = c->arena.base + ps.arena_off;
+  double* base = c->nl.arena.get() + ps.arena_off;
   GruPrefixArgs px{};
   px.table = base;
-  px.out_tab = base + (size_t)prefix::kEntries * 2 * c->g;
-  px.products = base + gru_prefix_products_off(c->g);
+  px.out_tab = base + (size_t)prefix::kEntries * 2 * c->nl.g;
+  px.products = base + gru_prefix_products_off(c->nl.g);
   double* syn_dev = px.out_tab + 64;
   NLC_HIP(c, hipMemcpy(syn_dev, syn.data(), syn.size() * sizeof(double), hipMemcpyHostToDevice));
-  GruArgs a = c->gru;
+  GruArgs a = c->nl.gru;
   a.mode = 1;
   a.perturbed = syn_dev;
   a.abuf = syn_dev;  // (never read: every element of window (k, B - 1) is a perturbed one)
@@ -526,7 +526,7 @@ int nlc::host::gru_prefix_configure(nlc_ctx* c) {
   a.B = d.B;
   a.nact = 1;
   a.out = nullptr;
-  NLC_HIP(c, launch_gru_prefix_table(a, px, c->g, c->stream));
+  NLC_HIP(c, launch_gru_prefix_table(a, px, c->nl.g, c->stream));
   NLC_HIP(c, hipStreamSynchronize(c->stream));
   return NLC_OK;
 }
@@ -540,7 +540,7 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
   const bool replay = call.replay;
   const bool lin_direct = linear_on_rollout_kernels(c);
   double* pa = ws + w.pa;
-  GruArgs g = c->gru;
+  GruArgs g = c->nl.gru;
   g.mode = 1;
   g.perturbed = buf->perturbed;
   g.abuf = call.abuf_dev;
@@ -554,30 +554,30 @@ int nlc::host::rollout_nl(nlc_ctx* c, RolloutCall& call) {
   RolloutArgs r{};
   put_sample_cost(r, sc);
   r.Kep = sc.Kep;
-  r.net = c->net;
-  r.net.b1 = c->b1fold;
+  r.net = c->nl.net;
+  r.net.b1 = c->nl.b1fold.get();
   r.B = d.B;
   r.pa = pa;
   r.tn = c->tn;
   r.xcarry = ws + w.xcarry;
   r.ccarry = ws + w.ccarry;
   if (lin_direct) {
-    if (!c->cp_lin) return fail(c, NLC_ERR_STATE, "linear-algorithm coefficient tables missing (nlc_mppi_configure)");
-    const size_t ng = (size_t)2 * c->net.nt3 * 64;
-    r.net.Cp = c->cp_lin;
-    r.net.Cp2 = c->cp_lin + ng;
+    if (!c->nl.cp_lin.get()) return fail(c, NLC_ERR_STATE, "linear-algorithm coefficient tables missing (nlc_mppi_configure)");
+    const size_t ng = (size_t)2 * c->nl.net.nt3 * 64;
+    r.net.Cp = c->nl.cp_lin.get();
+    r.net.Cp2 = c->nl.cp_lin.get() + ng;
     r.net.lin = 1;
   }
   c->prefix.last_used = false;
   const char* prefix_two_launch_only = "gru_prefix: the encoder launch of the two-launch body only (rollout_variant 1 / 2)";
-  if (c->md.ilt.algo != NLC_ILT_FOURIER && !lin_direct) {
+  if (c->nl.md.ilt.algo != NLC_ILT_FOURIER && !lin_direct) {
     if (c->opt.gru_prefix == 1) return fail(c, NLC_ERR_UNSUPPORTED, prefix_two_launch_only);
     return rollout_nl_staged(c, call, sc, g, r, pa);
   }
   // rollout_variant (nlc_set_option): 0 auto, 1 wave-per-tile, 2 latency-split, 3 fused one-launch body
   int variant = c->opt.rollout_variant;
-  const int h_ = c->md.h;
-  const bool fused_ok = (h_ == 64 || h_ == 128 || h_ == 256) && 2 * c->g == h_ && c->net.nt3 <= 21 &&
+  const int h_ = c->nl.md.h;
+  const bool fused_ok = (h_ == 64 || h_ == 128 || h_ == 256) && 2 * c->nl.g == h_ && c->nl.net.nt3 <= 21 &&
                         KE * d.T * 16 < (int64_t)1 << 31 && !lin_direct;  // (no LIN instance of the one-launch body)
   if (variant == 3 && !fused_ok) return fail(c, NLC_ERR_UNSUPPORTED, "fused planner body: model shape not instantiated");
   // instances per width: 3 and 4 workgroups per CU at hidden_units 64 / 128, 2 at 256 (68 KB of LDS per workgroup)

@@ -45,7 +45,7 @@ void plan_group(Plan& p, int M, int64_t N, int64_t data_rows) {
 // (slabs sized for the longest window)
 Plan plan_of(const nlc_ctx* c, int64_t N) {
   Plan p{};
-  const nlc_model_desc& md = c->md;
+  const nlc_model_desc& md = c->nl.md;
   p.g = md.h / 2;
   p.S = md.ilt.terms;
   p.d = md.d;
@@ -57,7 +57,7 @@ Plan plan_of(const nlc_ctx* c, int64_t N) {
 
 Plan rnn_plan_of(const nlc_ctx* c, int64_t N) {
   Plan p{};
-  const nlc_rnn_desc& rd = c->rd;
+  const nlc_rnn_desc& rd = c->rnnm.rd;
   p.d = rd.d;
   rnn_blob_offsets(rd.d, rd.nin, rd.hidden, rd.time_input, p.off);
   p.A = rnn_act_layout(rd.nin, rd.hidden, kMaxB).total;
@@ -74,14 +74,12 @@ WsPtrs ws_ptrs(const Plan& p, void* base) {
   return WsPtrs{b + p.ws.partial, b + p.ws.tile_loss, b + p.ws.act, b + p.ws.grad, b + p.ws.sq};
 }
 
-// fixed Talbot / Stehfest: fixed nodes and weights (linear_tables), the <true> instance of train_fwd_bwd_kernel
-bool linear_ilt(const nlc_ilt_desc& ilt) { return ilt.algo == NLC_ILT_FIXED_TALBOT || ilt.algo == NLC_ILT_STEHFEST; }
-
-// the NL model the kernels take: uploaded, and with one of the three ILT algorithms they are written for
+// the NL model the kernels take: uploaded, and with one of the three ILT algorithms they are written for (fixed Talbot /
+// Stehfest: fixed nodes and weights from linear_tables, the <true> instance of train_fwd_bwd_kernel)
 int check_nl_model(nlc_ctx* c) {
-  if (!c->has_model) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
-  const nlc_ilt_desc& ilt = c->md.ilt;
-  if (linear_ilt(ilt)) {
+  if (!c->nl.has) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
+  const nlc_ilt_desc& ilt = c->nl.md.ilt;
+  if (is_linear_ilt(ilt)) {
     // what linear_tables cannot build: an odd or too long Stehfest series, terms past the tables
     if (check_ilt(c, &ilt) != NLC_OK)
       return fail(c, NLC_ERR_UNSUPPORTED,
@@ -96,7 +94,7 @@ int check_nl_model(nlc_ctx* c) {
 
 // what every training and evaluation entry checks first, in this order: the family's model, the call's shape, the group
 int check_call(nlc_ctx* c, bool rnn, int M, int64_t data_rows, int64_t N, int B) {
-  if (rnn && !c->has_rnn) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
+  if (rnn && !c->rnnm.has) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
   if (!rnn)
     if (int rc = check_nl_model(c)) return rc;
   if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
@@ -192,14 +190,14 @@ void fill_call(Args& a, const Desc& m, int B, const Batch& b, const Plan& p) {
 // the NL model's own part of a launch: widths, the Fourier constants, or the tables of a linear algorithm
 template <class Args>
 int fill_nl(nlc_ctx* c, Args& a, const Plan& p) {
-  const nlc_model_desc& md = c->md;
+  const nlc_model_desc& md = c->nl.md;
   a.g = p.g;
   a.h = md.h;
   a.S = p.S;
   a.alpha = md.ilt.alpha;
   a.log_tol = std::log(md.ilt.tol);
   // one table for all members of a group (they share the descriptor); NULL selects the Fourier instance
-  return linear_ilt(md.ilt) ? linear_tables(c, &md.ilt, &a.lin_tab) : NLC_OK;
+  return is_linear_ilt(md.ilt) ? linear_tables(c, &md.ilt, &a.lin_tab) : NLC_OK;
 }
 
 // the workspace of a forward + backward launch
@@ -214,17 +212,17 @@ void fill_train_ws(Args& a, const Plan& p, const WsPtrs& w) {
 
 int nl_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w) {
   TrainArgs a{};
-  fill_call(a, c->md, B, b, p);
+  fill_call(a, c->nl.md, B, b, p);
   if (int rc = fill_nl(c, a, p)) return rc;
   fill_train_ws(a, p, w);
-  a.L = act_layout(p.d, c->md.nin, p.g, c->md.h, p.S, B);
+  a.L = act_layout(p.d, c->nl.md.nin, p.g, c->nl.md.h, p.S, B);
   ProfScope ps(c, "train_fwd_bwd_kernel");
   NLC_HIP(c, launch_train_fwd_bwd(a, p.nblk, p.M, c->stream));
   return NLC_OK;
 }
 
 int rnn_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w) {
-  const nlc_rnn_desc& rd = c->rd;
+  const nlc_rnn_desc& rd = c->rnnm.rd;
   RnnTrainArgs a{};
   fill_call(a, rd, B, b, p);
   a.time_input = rd.time_input;
@@ -238,10 +236,10 @@ int rnn_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& 
 // held-out loss (kernels_train_eval.hip): forward and squared error only; p.gs is the evaluation's (group_eval_entry)
 int nl_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss) {
   EvalArgs a{};
-  fill_call(a, c->md, B, b, p);
+  fill_call(a, c->nl.md, B, b, p);
   if (int rc = fill_nl(c, a, p)) return rc;
   a.tile_loss = tile_loss;
-  a.L = eval_lds_layout(p.d, c->md.nin, p.g, c->md.h, p.S, B);
+  a.L = eval_lds_layout(p.d, c->nl.md.nin, p.g, c->nl.md.h, p.S, B);
   // one workgroup per compute unit: the kernel's registers leave room for one wave per SIMD, whatever its LDS
   ProfScope ps(c, "train_eval_kernel");
   NLC_HIP(c, launch_train_eval(a, eval_grid(a.ntiles, c->prop.multiProcessorCount, 1, p.M), p.M, c->stream));
@@ -249,7 +247,7 @@ int nl_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss)
 }
 
 int rnn_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss) {
-  const nlc_rnn_desc& rd = c->rd;
+  const nlc_rnn_desc& rd = c->rnnm.rd;
   RnnEvalArgs a{};
   fill_call(a, rd, B, b, p);
   a.time_input = rd.time_input;
@@ -262,7 +260,7 @@ int rnn_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss
 
 // ---- the three entries of a family (rnn: DeltaTRNN / RNN, else NeuralLaplaceModel), written once for both and for any M
 int64_t group_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
-  if (!c || !(rnn ? c->has_rnn : c->has_model) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+  if (!c || !(rnn ? c->rnnm.has : c->nl.has) || N < 1 || M < 1 || M > kMaxGroup) return -1;
   const Plan p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
   return (int64_t)M * p.ws.total * (int64_t)sizeof(double);
 }
@@ -275,7 +273,7 @@ int group_loss_grad(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double
                     double* grad, double* loss, void* ws, Plan* plan, const int64_t* step = nullptr, bool more_null = false) {
   if (int rc = check_call(c, rnn, M, data_rows, N, B)) return rc;
   if (step && *step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
-  const bool need_ts = rnn ? c->rd.time_input != 0 : true;
+  const bool need_ts = rnn ? c->rnnm.rd.time_input != 0 : true;
   if (!params || !obs || !window || (!ts && need_ts) || !target || !idx || (!step && !grad) || !loss || !ws || more_null)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
@@ -316,7 +314,7 @@ int group_step_entry(nlc_ctx* c, bool rnn, const nlc_train_desc* desc, int M, in
 // checks are group_loss_grad's, in its order; idx may be NULL (rows 0 .. N - 1).  The workspace is the tile losses
 // (nlc_train_eval.h eval_ws_layout), M regions back to back
 int64_t group_eval_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
-  if (!c || !(rnn ? c->has_rnn : c->has_model) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+  if (!c || !(rnn ? c->rnnm.has : c->nl.has) || N < 1 || M < 1 || M > kMaxGroup) return -1;
   return (int64_t)M * eval_ws_layout(N).total * (int64_t)sizeof(double);
 }
 
@@ -326,7 +324,7 @@ int group_eval_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const doubl
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
   if (int rc = check_call(c, rnn, M, data_rows, N, B)) return rc;
-  const bool need_ts = rnn ? c->rd.time_input != 0 : true;
+  const bool need_ts = rnn ? c->rnnm.rd.time_input != 0 : true;
   if (!params || !obs || !window || (!ts && need_ts) || !target || !loss || !ws)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));

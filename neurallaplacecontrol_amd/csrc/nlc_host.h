@@ -8,6 +8,9 @@
 //   abi_baselines.hip   env step, Delta-t RNN and NODE baseline models
 //   abi_planner.hip     nlc_mppi_*: configure, workspace layout, phase 1 (sampling + rollout), weights, finish
 //   abi_planner_nl.hip  phase 1 with Neural-Laplace dynamics: staged (de Hoog / linear), one-launch fused body, two launches
+//   abi_train.hip       fused training step, held-out loss and loss gradient of the NL and Delta-t RNN models (groups of them)
+//   abi_train_select.hip  keep_best / restore_best: the best weights of a group's members, kept on the device
+//   abi_synth.hip       synthetic transition dataset, generated on the device
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -22,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "nlc_devbuf.h"
 #include "nlc_gru_prefix.h"
 #include "nlc_kernels.h"
 #include "nlc_pack.h"
@@ -39,9 +43,8 @@ struct ProfEntry {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// a model's packed weights on the host, as one block for upload_arena
 struct DeviceArena {
-  double* base = nullptr;
-  size_t n = 0;
   std::vector<double> host;
   size_t push(const std::vector<double>& v) {
     // 64-double (512 B) alignment so every fragment row starts on a cache line
@@ -139,15 +142,14 @@ struct DehoogCalib {
   }
 };
 
-// "gru_prefix" (nlc_gru_prefix.h): the table sits in the model's arena (c->arena, reserved by nlc_set_model) and is built by
+// "gru_prefix" (nlc_gru_prefix.h): the table sits in the model's arena (c->nl.arena, reserved by nlc_set_model) and is built by
 // nlc_mppi_configure -- a new model, other bounds / u_scale / normalisation or another B all pass through there; the window
 // lists and their counters are the ctx's own buffer, grown at the first command that needs it
 struct GruPrefixState {
   size_t arena_off = 0;          // table, out_tab, the table build's 16 synthetic windows and the products, in doubles from the arena's base
   const char* why_not = "gru_prefix: planner not configured";  // out of scope (nullptr: the table is built)
   unsigned long long img_max = 0, img_min = 0;
-  double* lists = nullptr;       // counters (one 64-double row) + kLists lists
-  size_t lists_n = 0;
+  DevDoubles lists;              // counters (one 64-double row) + kLists lists
   bool last_used = false;        // the last command's encoder launch started from the table
   int last_B = 0;
 };
@@ -185,6 +187,48 @@ struct SideStreams {
   }
 };
 
+// ---- the uploaded models, by family (members of nlc_ctx).  A setter builds a local group and moves it into the ctx once
+// every check, allocation and copy has succeeded: the move frees the previous model's buffers, and a fresh group's defaults
+// are what a new model invalidates inside the group.  Outside it the setter clears has_mppi (RNN / NODE: of their own
+// dynamics) and, for NL, the gru_prefix table.  The pointers inside gru / net / rnn / node are kernel arguments.
+struct NlModel {
+  bool has = false;
+  nlc_model_desc md{};
+  int g = 0, S = 0, P = 0;
+  DevDoubles arena;     // packed weights + the room of the gru_prefix table
+  nlc::GruArgs gru{};   // weight pointers + normalisation filled in
+  nlc::NlNetArgs net{}; // general-t variant (b1 = raw bias)
+  std::vector<double> W1s_host, b1_host;  // for folding the constant sphere inputs (fold_b1)
+  DevInts slot_dev;                       // (8*nt3) layer-3 slot -> c*S + k (de Hoog path)
+  DevInts eidx_dev;                       // (d*S) inverse: term k of dim c -> slot (slot-major F of the planner path)
+  std::vector<std::pair<int, int>> slot_elems;  // (dim, term) of every layer-3 slot (nlc_pack.h)
+  DevDoubles lin_tab;                     // nodes / weights of the linear ILT algorithms, cached per (algo, terms)
+  int lin_algo = -1, lin_S = 0;
+  DevDoubles b1fold;                      // (h): layer 1's bias with the sphere inputs of the planner's ts_pred folded in
+  DevDoubles cp_lin;                      // [2][2 nt3][64]: w_re / t and -w_im / t coefficient fragments (configure time)
+  DevDoubles b1fold_fwd;                  // (h): the same fold for nlc_model_forward_const_t's query time
+  double fwd_tn = -1.0;                   // normalised time b1fold_fwd was folded for
+  std::vector<double> fwd_fold_host;      // its host copy (kept alive for the asynchronous upload)
+};
+
+// Delta-t RNN baseline
+struct RnnModel {
+  bool has = false;
+  nlc_rnn_desc rd{};
+  DevDoubles arena;
+  nlc::RnnArgs rnn{};
+  nlc::RnnHead rnn_head{};
+};
+
+// NODE baseline
+struct NodeModel {
+  bool has = false;
+  nlc_node_desc nd{};
+  DevDoubles arena;
+  nlc::NodeNetArgs node{};
+  int node_ht = 0;
+};
+
 }  // namespace host
 }  // namespace nlc
 
@@ -195,47 +239,19 @@ struct nlc_ctx {
   std::string err;
   hipDeviceProp_t prop;
 
-  // model
-  bool has_model = false;
-  nlc_model_desc md{};
-  int g = 0, S = 0, P = 0;
-  nlc::host::DeviceArena arena;
-  nlc::GruArgs gru{};   // weight pointers + normalisation filled in
-  nlc::NlNetArgs net{}; // general-t variant (b1 = raw bias)
-  std::vector<double> W1s_host, b1_host;  // for folding the constant sphere inputs at configure time
-  int* slot_dev = nullptr;                // (8*nt3) layer-3 slot -> c*S + k (de Hoog path)
-  double* lin_tab = nullptr;              // nodes / weights of the linear ILT algorithms, cached per (algo, terms)
-  int lin_algo = -1, lin_S = 0;
-  int* eidx_dev = nullptr;                // (d*S) inverse: term k of dim c -> slot (slot-major F of the planner path)
-
-  // Delta-t RNN baseline model
-  bool has_rnn = false;
-  nlc_rnn_desc rd{};
-  double* rnn_base = nullptr;  // packed weights (device)
-  nlc::RnnArgs rnn{};
-  nlc::RnnHead rnn_head{};
-
-  // NODE baseline model
-  bool has_node = false;
-  nlc_node_desc nd{};
-  double* node_base = nullptr;
-  nlc::NodeNetArgs node{};
-  int node_ht = 0;
+  // models
+  nlc::host::NlModel nl;
+  nlc::host::RnnModel rnnm;
+  nlc::host::NodeModel nodem;
 
   // planner
   bool has_mppi = false;
   nlc_mppi_desc pd{};
-  double* U[2] = {nullptr, nullptr};
+  nlc::host::DevDoubles U[2];
   int ucur = 0;
-  double* b1fold = nullptr;   // (h) device
-  double* b1fold_fwd = nullptr;          // (h) device: the same fold for nlc_model_forward_const_t's query time
-  double fwd_tn = -1.0;                  // normalised time b1fold_fwd was folded for
-  std::vector<double> fwd_fold_host;     // its host copy (kept alive for the asynchronous upload)
-  double* small = nullptr;    // action (<= T*nu) + beta_eta (2)
+  nlc::host::DevDoubles small;  // action (<= T*nu) + beta_eta (2)
   double tn = 0.0;
   int nblk = 0;
-  double* cp_lin = nullptr;             // [2][2 nt3][64] device: w_re / t and -w_im / t coefficient fragments (configure time)
-  std::vector<std::pair<int, int>> slot_elems;  // (dim, term) of every layer-3 slot (nlc_pack.h), kept from nlc_set_model
   int64_t commands = 0;                 // nlc_mppi_rollout calls since nlc_create
   int last_body = 0;                    // body phase 1 of the last command ran on (nlc_get_stat "rollout_body")
 
@@ -245,8 +261,7 @@ struct nlc_ctx {
 
   // pinned host block of the configured planner (nlc_plan.h): staging for the per-command small transfers, the action, and the
   // control words the kernels store
-  double* pinned = nullptr;
-  size_t pinned_n = 0;
+  nlc::host::PinnedDoubles pinned;
   nlc::plan::PinLayout pin{};
   // the planner's state by group; each group's reset rule is its own (who calls which: nlc_mppi_configure, nlc_set_option,
   // nlc_destroy)
@@ -257,13 +272,11 @@ struct nlc_ctx {
   nlc::host::SideStreams side;
   nlc::host::GruPrefixState prefix;
   // tools only (options "dbg_gap_us" / "dbg_l2_mb")
-  double* dbg_scratch = nullptr;
-  size_t dbg_scratch_n = 0;
+  nlc::host::DevDoubles dbg_scratch;
   // optional native collective (nlc_comm_init): an RCCL communicator over the ranks of a K-sharded planner
   void* comm = nullptr;
   int comm_world = 0, comm_rank = 0;
-  double* comm_gather = nullptr;  // (world, E, 2+T*nu) receive buffer of the per-command all-gather
-  size_t comm_gather_n = 0;
+  nlc::host::DevDoubles comm_gather;  // (world, E, 2+T*nu) receive buffer of the per-command all-gather
 };
 
 namespace nlc {
@@ -346,16 +359,36 @@ struct Blob {
 };
 
 bool is_device_ptr(const void* p);
-// "this device buffer must hold n doubles": frees what p held, allocates, and uploads n doubles from `upload` when given (a
-// synchronous copy).  With `have` (the buffer's size so far) the buffer only grows: nothing happens while n <= *have.
-int hold_doubles(nlc_ctx* c, double*& p, size_t n, const double* upload = nullptr, size_t* have = nullptr);
-// its twin for mapped, coherent pinned host memory; grows only
-int hold_pinned_doubles(nlc_ctx* c, double*& p, size_t n, size_t* have);
+// b holds exactly n elements, copied from src (a synchronous copy); a failure leaves it empty
+template <class T>
+int upload(nlc_ctx* c, Buf<T, DeviceMem>& b, const T* src, size_t n) {
+  NLC_HIP(c, (hipError_t)b.hold(n));
+  const hipError_t e = hipMemcpy(b.get(), src, n * sizeof(T), hipMemcpyHostToDevice);
+  if (e != hipSuccess) b.reset();
+  return e == hipSuccess ? NLC_OK : fail(c, NLC_ERR_HIP, std::string("weight upload: ") + hipGetErrorString(e));
+}
+inline int upload_arena(nlc_ctx* c, const DeviceArena& ar, DevDoubles& b) { return upload(c, b, ar.host.data(), ar.host.size()); }
 bool gru_use_coop(const nlc_ctx* c, int64_t n_windows);
+// the window-mode GRU encode of N windows of B actions -> out (N, 2), on the ctx's stream
+int encode_windows(nlc_ctx* c, const double* window, int64_t N, int B, double* out);
 
 // ---- abi_ilt.hip
 int check_ilt(nlc_ctx* c, const nlc_ilt_desc* d);
+// fixed Talbot / Stehfest: the two algorithms that are linear in F (nodes and weights from linear_tables)
+inline bool is_linear_ilt(const nlc_ilt_desc& ilt) { return ilt.algo == NLC_ILT_FIXED_TALBOT || ilt.algo == NLC_ILT_STEHFEST; }
+// the term counts the de Hoog kernels take (any count goes for the other algorithms)
+inline int check_dehoog_terms(nlc_ctx* c, const nlc_ilt_desc& ilt) {
+  if (ilt.algo == NLC_ILT_DEHOOG && (ilt.terms < 3 || ilt.terms > 33 || ilt.terms % 2 == 0))
+    return fail(c, NLC_ERR_UNSUPPORTED, "dehoog: ilt_reconstruction_terms must be odd, 3 .. 33 (2M+1 terms)");
+  return NLC_OK;
+}
 void sphere_inputs(const nlc_ilt_desc& ilt, double tn, std::vector<double>& sph);
+// layer 1's bias of model m with the constant sphere inputs of the normalised time tn folded in (nlc_devbuf.h)
+inline void fold_b1(const NlModel& m, double tn, std::vector<double>& out) {
+  std::vector<double> sph;
+  sphere_inputs(m.md.ilt, tn, sph);
+  fold_b1(m.W1s_host.data(), m.b1_host.data(), m.md.h, m.S, sph.data(), out);
+}
 void linear_tables_host(int algo, int S, std::vector<double>& h);
 int linear_tables(nlc_ctx* c, const nlc_ilt_desc* d, const double** tab);
 // The ILT kernels' argument blocks, filled by name: the arrays, the shape and the contour's options, with t_div = 1,
@@ -424,9 +457,9 @@ struct WsLayout {
 };
 WsLayout ws_layout(const nlc_ctx* c);
 // the control words of the pinned block (nlc_plan.h PinLayout)
-inline unsigned* pin_giveup_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned + c->pin.giveup); }
-inline unsigned long long* pin_seq_word(nlc_ctx* c) { return reinterpret_cast<unsigned long long*>(c->pinned + c->pin.seq); }
-inline unsigned* pin_merge_status_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned + c->pin.merge_status); }
+inline unsigned* pin_giveup_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned.get() + c->pin.giveup); }
+inline unsigned long long* pin_seq_word(nlc_ctx* c) { return reinterpret_cast<unsigned long long*>(c->pinned.get() + c->pin.seq); }
+inline unsigned* pin_merge_status_word(nlc_ctx* c) { return reinterpret_cast<unsigned*>(c->pinned.get() + c->pin.merge_status); }
 WeightArgs make_weight_args(nlc_ctx* c, const nlc_mppi_buffers* buf);
 int run_weights(nlc_ctx* c, const nlc_mppi_buffers* buf);
 // The configured cost variant, 0 with cost_external; a flipped bit without NLC_COST_CHANGE_GOAL selects nothing.
