@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 17
+#define NLC_ABI_VERSION 18
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -487,6 +487,38 @@ int nlc_set_node_model(nlc_ctx* ctx, const nlc_node_desc* desc, const double* we
  * (the reference integrates every row to ts_pred[0], :719) -> out_dev (N,d) integrated normalised state. */
 int nlc_node_forward(nlc_ctx* ctx, const double* obs_dev, const double* action_dev, double ts_pred, int64_t N,
                      double* out_dev);
+/* ---- training of the NODE: the same iteration (train_utils.py:388-408 over NODE.forward :696-724; the loss is the MSE of
+ *      the integrated normalised state against target), signatures and contract of nlc_rnn_train_group_* above plus row_times.
+ *      The model comes from nlc_set_node_model on the same ctx (without it: NLC_ERR_STATE); N < 1 or M < 1:
+ *      NLC_ERR_BAD_SHAPE; M > 65535 or B outside 1..16: NLC_ERR_UNSUPPORTED; all checked on the host before any launch.
+ *   params_dev, grad_dev, m_dev, v_dev [M][P], P = nlc_node_blob_size, in nlc_set_node_model's blob order (unpadded).
+ *   window_dev (rows, B, nu): the newest action window[:, B-1, :] is read, raw.  ts_dev (rows): raw prediction times.
+ *   row_times == 0: every row of a member's batch integrates to the time of its first row, ts[idx[0]] (:719, what NODE.forward
+ *   does); != 0: each row to its own ts[idx[r]].  The sub-step counts are formed on the device (torchdiffeq's fixed grid:
+ *   ceil(t / step_size + 1) points); nothing reads ts on the host.  A row takes at most 256 sub-steps: the workspace is a
+ *   function of (M, N) and the model's shape alone, and a row whose time is not positive, is NaN, or needs more sub-steps gets
+ *   a NaN squared error (so the member's loss is NaN) and touches no memory outside the workspace.
+ *   The single-model forms are M = 1, data_row_stride = 0.  Three launches (training) or two (evaluation) on the ctx's stream,
+ *   no atomics, no host synchronisation. */
+/* train_utils.py:388-408, run_exp_multi.py:105-110 */
+int64_t nlc_node_train_group_workspace_bytes(nlc_ctx* ctx, int M, int64_t N);
+/* train_utils.py:391-402 per member, run_exp_multi.py:105-110 */
+int nlc_node_train_group_loss_grad(nlc_ctx* ctx, int M, int64_t data_row_stride, const double* params_dev,
+                                   const double* obs_dev, const double* window_dev, const double* ts_dev,
+                                   const double* target_dev, const int64_t* idx_dev, int64_t N, int B, double* grad_dev,
+                                   double* loss_dev, void* ws_dev, int row_times);
+/* train_utils.py:391-404 per member, run_exp_multi.py:105-110 */
+int nlc_node_train_group_step(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_t data_row_stride, double* params_dev,
+                              double* m_dev, double* v_dev, int64_t step, const double* obs_dev, const double* window_dev,
+                              const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
+                              double* loss_dev, double* gradnorm_dev, void* ws_dev, int row_times);
+/* overlay.py:112-115, :175-177, run_exp_multi.py:105-110 */
+int64_t nlc_node_train_group_eval_workspace_bytes(nlc_ctx* ctx, int M, int64_t N);
+/* overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110 */
+int nlc_node_train_group_eval(nlc_ctx* ctx, int M, int64_t data_row_stride, const double* params_dev, const double* obs_dev,
+                              const double* window_dev, const double* ts_dev, const double* target_dev,
+                              const int64_t* idx_dev /* NULL: rows 0..N-1 */, int64_t N, int B, double* loss_dev /* [M] */,
+                              void* ws_dev, int row_times);
 
 /* ---- planner: MPPIDelay (planners/mppi_delay.py:54-381) ------------------------------------- */
 typedef struct {

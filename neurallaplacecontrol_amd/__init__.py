@@ -22,7 +22,8 @@ from .laplace import ilt_reconstruct, laplace_reconstruct, rep_func_inputs  # no
 from .nl_model import LaplaceRepresentationFunc, NeuralLaplaceModel, ReverseGRUEncoder  # noqa: F401
 from .node_model import NODE, xOdeFuncInXAndU  # noqa: F401
 from .rnn_model import RNN, DeltaTRNN  # noqa: F401
-from .training import NLTrainer, NLTrainerGroup, RNNTrainer, RNNTrainerGroup  # noqa: F401
+from .training import (NLTrainer, NLTrainerGroup, NODETrainer, NODETrainerGroup, RNNTrainer,  # noqa: F401
+                       RNNTrainerGroup)
 from .synthetic import generate_synthetic_dataset, synthetic_dataset_shape  # noqa: F401
 from .planners.mppi_batch import BatchedMPPIDelay  # noqa: F401
 from .planners.mppi_delay import MPPIDelay  # noqa: F401
@@ -40,6 +41,8 @@ __all__ = [
     "NeuralLaplaceModel",
     "NLTrainer",
     "NLTrainerGroup",
+    "NODETrainer",
+    "NODETrainerGroup",
     "RNNTrainer",
     "RNNTrainerGroup",
     "DeltaTRNN",

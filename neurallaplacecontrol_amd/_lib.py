@@ -87,6 +87,11 @@ SYMBOLS = [
     "nlc_node_blob_size",
     "nlc_set_node_model",
     "nlc_node_forward",
+    "nlc_node_train_group_workspace_bytes",
+    "nlc_node_train_group_loss_grad",
+    "nlc_node_train_group_step",
+    "nlc_node_train_group_eval_workspace_bytes",
+    "nlc_node_train_group_eval",
     "nlc_mppi_configure",
     "nlc_mppi_workspace_bytes",
     "nlc_mppi_set_U",
@@ -316,6 +321,14 @@ def load_library():
             getattr(lib, fam + "_group_eval_workspace_bytes").argtypes = [vp, i32, i64]
             getattr(lib, fam + "_group_eval_workspace_bytes").restype = i64
             getattr(lib, fam + "_group_eval").argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]
+        # NODE: the group entries plus a trailing row_times
+        lib.nlc_node_train_group_workspace_bytes.argtypes = lib.nlc_train_group_workspace_bytes.argtypes
+        lib.nlc_node_train_group_workspace_bytes.restype = i64
+        lib.nlc_node_train_group_loss_grad.argtypes = lib.nlc_train_group_loss_grad.argtypes + [i32]
+        lib.nlc_node_train_group_step.argtypes = lib.nlc_train_group_step.argtypes + [i32]
+        lib.nlc_node_train_group_eval_workspace_bytes.argtypes = lib.nlc_train_group_eval_workspace_bytes.argtypes
+        lib.nlc_node_train_group_eval_workspace_bytes.restype = i64
+        lib.nlc_node_train_group_eval.argtypes = lib.nlc_train_group_eval.argtypes + [i32]
         # snapshot selection: M, P, loss, params, best_loss, best_params, best_tag, tag, improved
         lib.nlc_train_keep_best.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, i64, vp]
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]

@@ -1,7 +1,7 @@
 // Host side of libnlc_hip.so, training unit: the fused training step of a NeuralLaplaceModel (kernels_train.hip; the Fourier
 // ILT, or fixed Talbot / Stehfest with the node and weight tables of abi_ilt.hip's linear_tables) and of the
-// DeltaTRNN / RNN baselines (kernels_train_rnn.hip), one iteration of the reference's loop, train_utils.py:388-408 (forward,
-// MSELoss, backward, clip_grad_norm_, Adam.step).  The two models differ in the forward + backward launch and the blob's
+// DeltaTRNN / RNN (kernels_train_rnn.hip) and NODE (kernels_train_node.hip) baselines, one iteration of the reference's loop, train_utils.py:388-408 (forward,
+// MSELoss, backward, clip_grad_norm_, Adam.step).  The models differ in the forward + backward launch and the blob's
 // tensors; the workspace, the reduction and the Adam launch are written once.  Every entry is the group path: M same-shaped
 // models (run_exp_multi.py:105-110) in the same three launches, the member on the grid's y axis; a single model is M = 1.
 #include <cmath>
@@ -10,12 +10,16 @@
 #include "nlc_host.h"
 #include "nlc_train.h"
 #include "nlc_train_eval.h"
+#include "nlc_train_node.h"
 
 using namespace nlc;
 using namespace nlc::host;
 using namespace nlc::train;
 
 namespace {
+
+// the model families of the entries below: NeuralLaplaceModel, DeltaTRNN / RNN, NODE
+enum Family { kFamNl, kFamRnn, kFamNode };
 
 struct Plan {
   int g, S, nblk, chunks, d;
@@ -25,6 +29,7 @@ struct Plan {
   TrainWsLayout ws;      // one member's workspace region
   GroupStrides gs;  // for a group whose gradient lives in the workspace (a step); loss_grad overrides gs.grad
   int M;
+  int row_times;  // NODE: every row integrates to its own time (0: to the batch's first row's, as the reference)
 };
 
 // workgroups, partial size and the reduce / Adam chunking of a call with N rows, once p.off, p.A and p.d are set
@@ -65,6 +70,25 @@ Plan rnn_plan_of(const nlc_ctx* c, int64_t N) {
   return p;
 }
 
+// (the slab is a function of the shape alone: it holds the state tape of kNodeTrainMaxSub sub-steps, whatever ts says)
+Plan node_plan_of(const nlc_ctx* c, int64_t N) {
+  Plan p{};
+  const nlc_node_desc& nd = c->nodem.nd;
+  p.d = nd.d;
+  node_blob_offsets(nd.d, nd.augment_dim, nd.nu, nd.hidden, p.off);
+  p.A = node_act_layout(nd.hidden, nd.d + nd.augment_dim + nd.nu).total;
+  plan_rows(p, N);
+  return p;
+}
+
+Plan family_plan(const nlc_ctx* c, Family fam, int64_t N) {
+  return fam == kFamRnn ? rnn_plan_of(c, N) : fam == kFamNode ? node_plan_of(c, N) : plan_of(c, N);
+}
+
+bool family_has(const nlc_ctx* c, Family fam) {
+  return fam == kFamRnn ? c->rnnm.has : fam == kFamNode ? c->nodem.has : c->nl.has;
+}
+
 // member 0's arrays in the workspace (nlc_train.h TrainWsLayout; member m's are gs.ws doubles further on)
 struct WsPtrs {
   double *partial, *tile_loss, *act, *grad, *sq;
@@ -93,10 +117,12 @@ int check_nl_model(nlc_ctx* c) {
 }
 
 // what every training and evaluation entry checks first, in this order: the family's model, the call's shape, the group
-int check_call(nlc_ctx* c, bool rnn, int M, int64_t data_rows, int64_t N, int B) {
-  if (rnn && !c->rnnm.has) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
-  if (!rnn)
+int check_call(nlc_ctx* c, Family fam, int M, int64_t data_rows, int64_t N, int B) {
+  if (fam == kFamRnn && !c->rnnm.has) return fail(c, NLC_ERR_STATE, "nlc_set_rnn_model has not been called");
+  if (fam == kFamNode && !c->nodem.has) return fail(c, NLC_ERR_STATE, "nlc_set_node_model has not been called");
+  if (fam == kFamNl)
     if (int rc = check_nl_model(c)) return rc;
+  // (a NODE reads the window's newest action only, but keeps the families' one contract)
   if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
   if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
   if (M < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: a group needs M >= 1 members");
@@ -258,53 +284,95 @@ int rnn_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss
   return NLC_OK;
 }
 
-// ---- the three entries of a family (rnn: DeltaTRNN / RNN, else NeuralLaplaceModel), written once for both and for any M
-int64_t group_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
-  if (!c || !(rnn ? c->rnnm.has : c->nl.has) || N < 1 || M < 1 || M > kMaxGroup) return -1;
-  const Plan p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
+// nlc_node_desc as fill_call reads a descriptor: the state half of the constants, no normalised input (the ODE function takes
+// the window's newest action raw)
+struct NodeDescView {
+  int d, nin;
+  double time_div;
+  const double *state_mean, *state_std, *action_mean, *action_std;
+};
+
+// the NODE's launch arguments, shared by training and evaluation (kernels_train_node.hip)
+NodeTrainArgs node_args(const nlc_ctx* c, const Batch& b, int B, const Plan& p) {
+  const nlc_node_desc& nd = c->nodem.nd;
+  NodeTrainArgs a{};
+  fill_call(a, NodeDescView{nd.d, 0, nd.time_div, nd.state_mean, nd.state_std, nullptr, nullptr}, B, b, p);
+  a.aug = nd.augment_dim;
+  a.nu = nd.nu;
+  a.H = nd.hidden;
+  a.step_size = nd.step_size;
+  a.row_times = p.row_times;
+  return a;
+}
+
+int node_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w) {
+  NodeTrainArgs a = node_args(c, b, B, p);
+  fill_train_ws(a, p, w);
+  a.L = node_act_layout(a.H, a.d + a.aug + a.nu);
+  ProfScope ps(c, "node_train_fwd_bwd_kernel");
+  NLC_HIP(c, launch_node_train_fwd_bwd(a, p.nblk, p.M, c->stream));
+  return NLC_OK;
+}
+
+int node_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss) {
+  NodeTrainArgs a = node_args(c, b, B, p);
+  a.tile_loss = tile_loss;
+  const int per_cu = eval_per_cu(node_lds_doubles(false) * (int64_t)sizeof(double));
+  ProfScope ps(c, "node_eval_kernel");
+  NLC_HIP(c, launch_node_eval(a, eval_grid(a.ntiles, c->prop.multiProcessorCount, per_cu, p.M), p.M, c->stream));
+  return NLC_OK;
+}
+
+// ---- the three entries of a family, written once for all of them and for any M
+int64_t group_workspace_bytes(nlc_ctx* c, Family fam, int M, int64_t N) {
+  if (!c || !family_has(c, fam) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+  const Plan p = family_plan(c, fam, N);
   return (int64_t)M * p.ws.total * (int64_t)sizeof(double);
 }
 
 // checks (all on the host, before any launch, in the single entries' order: model state and shape, the group, the step count,
 // NULL pointers), then forward + backward + reduce of every member.  A step (step != NULL: its Adam step count; more_null: one
 // of its own pointers is NULL) keeps the summed gradients in the workspace; else they go to the caller's grad [M][P]
-int group_loss_grad(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
+int group_loss_grad(nlc_ctx* c, Family fam, int M, int64_t data_rows, const double* params, const double* obs,
                     const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
-                    double* grad, double* loss, void* ws, Plan* plan, const int64_t* step = nullptr, bool more_null = false) {
-  if (int rc = check_call(c, rnn, M, data_rows, N, B)) return rc;
+                    double* grad, double* loss, void* ws, Plan* plan, int row_times, const int64_t* step = nullptr,
+                    bool more_null = false) {
+  if (int rc = check_call(c, fam, M, data_rows, N, B)) return rc;
   if (step && *step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
-  const bool need_ts = rnn ? c->rnnm.rd.time_input != 0 : true;
+  const bool need_ts = fam == kFamRnn ? c->rnnm.rd.time_input != 0 : true;
   if (!params || !obs || !window || (!ts && need_ts) || !target || !idx || (!step && !grad) || !loss || !ws || more_null)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   Plan& p = *plan;
-  p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
+  p = family_plan(c, fam, N);
   plan_group(p, M, N, data_rows);
+  p.row_times = row_times;
   const WsPtrs w = ws_ptrs(p, ws);
   const Batch b{params, obs, window, ts, target, idx, N};
-  if (int rc = (rnn ? rnn_fwd_bwd : nl_fwd_bwd)(c, b, B, p, w)) return rc;
+  if (int rc = (fam == kFamRnn ? rnn_fwd_bwd : fam == kFamNode ? node_fwd_bwd : nl_fwd_bwd)(c, b, B, p, w)) return rc;
   return reduce(c, N, step ? w.grad : grad, step ? p.gs.ws : p.P, loss, p, w);
 }
 
-int group_loss_grad_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
+int group_loss_grad_entry(nlc_ctx* c, Family fam, int M, int64_t data_rows, const double* params, const double* obs,
                           const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N,
-                          int B, double* grad, double* loss, void* ws) {
+                          int B, double* grad, double* loss, void* ws, int row_times = 0) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
   Plan p;
-  return group_loss_grad(c, rnn, M, data_rows, params, obs, window, ts, target, idx, N, B, grad, loss, ws, &p);
+  return group_loss_grad(c, fam, M, data_rows, params, obs, window, ts, target, idx, N, B, grad, loss, ws, &p, row_times);
   NLC_GUARD_END(c)
 }
 
-int group_step_entry(nlc_ctx* c, bool rnn, const nlc_train_desc* desc, int M, int64_t data_rows, double* params, double* m,
+int group_step_entry(nlc_ctx* c, Family fam, const nlc_train_desc* desc, int M, int64_t data_rows, double* params, double* m,
                      double* v, int64_t step, const double* obs, const double* window, const double* ts,
-                     const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws) {
+                     const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws,
+                     int row_times = 0) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
   if (!desc) return fail(c, NLC_ERR_BAD_ARG, "NULL train desc");
   Plan p;
-  if (int rc = group_loss_grad(c, rnn, M, data_rows, params, obs, window, ts, target, idx, N, B, nullptr, loss, ws, &p, &step,
-                               !m || !v))
+  if (int rc = group_loss_grad(c, fam, M, data_rows, params, obs, window, ts, target, idx, N, B, nullptr, loss, ws, &p,
+                               row_times, &step, !m || !v))
     return rc;
   return adam(c, desc, params, m, v, step, gradnorm, p, ws_ptrs(p, ws));
   NLC_GUARD_END(c)
@@ -313,28 +381,29 @@ int group_step_entry(nlc_ctx* c, bool rnn, const nlc_train_desc* desc, int M, in
 // ---- held-out loss (kernels_train_eval.hip): the forward and the squared error of every member, then one reduction.  The
 // checks are group_loss_grad's, in its order; idx may be NULL (rows 0 .. N - 1).  The workspace is the tile losses
 // (nlc_train_eval.h eval_ws_layout), M regions back to back
-int64_t group_eval_workspace_bytes(nlc_ctx* c, bool rnn, int M, int64_t N) {
-  if (!c || !(rnn ? c->rnnm.has : c->nl.has) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+int64_t group_eval_workspace_bytes(nlc_ctx* c, Family fam, int M, int64_t N) {
+  if (!c || !family_has(c, fam) || N < 1 || M < 1 || M > kMaxGroup) return -1;
   return (int64_t)M * eval_ws_layout(N).total * (int64_t)sizeof(double);
 }
 
-int group_eval_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const double* params, const double* obs,
+int group_eval_entry(nlc_ctx* c, Family fam, int M, int64_t data_rows, const double* params, const double* obs,
                      const double* window, const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
-                     double* loss, void* ws) {
+                     double* loss, void* ws, int row_times = 0) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
-  if (int rc = check_call(c, rnn, M, data_rows, N, B)) return rc;
-  const bool need_ts = rnn ? c->rnnm.rd.time_input != 0 : true;
+  if (int rc = check_call(c, fam, M, data_rows, N, B)) return rc;
+  const bool need_ts = fam == kFamRnn ? c->rnnm.rd.time_input != 0 : true;
   if (!params || !obs || !window || (!ts && need_ts) || !target || !loss || !ws)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   const EvalWsLayout w = eval_ws_layout(N);
-  Plan p = rnn ? rnn_plan_of(c, N) : plan_of(c, N);
+  Plan p = family_plan(c, fam, N);
   p.M = M;
+  p.row_times = row_times;
   p.gs = GroupStrides{p.P, w.total, 0, N, data_rows};
   double* tile_loss = (double*)ws + w.tile_loss;
   const Batch b{params, obs, window, ts, target, idx, N};
-  if (int rc = (rnn ? rnn_eval : nl_eval)(c, b, B, p, tile_loss)) return rc;
+  if (int rc = (fam == kFamRnn ? rnn_eval : fam == kFamNode ? node_eval : nl_eval)(c, b, B, p, tile_loss)) return rc;
   EvalReduceArgs r{tile_loss, w.ntiles, N, w.total, p.d, loss};
   ProfScope ps(c, "eval_reduce_kernel");
   NLC_HIP(c, launch_eval_reduce(r, M, c->stream));
@@ -349,107 +418,143 @@ int group_eval_entry(nlc_ctx* c, bool rnn, int M, int64_t data_rows, const doubl
 // or the rows per member of a stacked one; the single entries are its M = 1 case
 // train_utils.py:388-408, run_exp_multi.py:105-110
 extern "C" int64_t nlc_train_group_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
-  return group_workspace_bytes(c, false, M, N);
+  return group_workspace_bytes(c, kFamNl, M, N);
 }
 // train_utils.py:391-402 per member, run_exp_multi.py:105-110
 extern "C" int nlc_train_group_loss_grad(nlc_ctx* c, int M, int64_t data_row_stride, const double* params,
                                          const double* obs, const double* window, const double* ts, const double* target,
                                          const int64_t* idx, int64_t N, int B, double* grad, double* loss, void* ws) {
-  return group_loss_grad_entry(c, false, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
+  return group_loss_grad_entry(c, kFamNl, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
 }
 // train_utils.py:391-404 per member, run_exp_multi.py:105-110
 extern "C" int nlc_train_group_step(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride, double* params,
                                     double* m, double* v, int64_t step, const double* obs, const double* window,
                                     const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                                     double* loss, double* gradnorm, void* ws) {
-  return group_step_entry(c, false, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+  return group_step_entry(c, kFamNl, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
                           gradnorm, ws);
 }
 // train_utils.py:388-408
-extern "C" int64_t nlc_train_workspace_bytes(nlc_ctx* c, int64_t N) { return group_workspace_bytes(c, false, 1, N); }
+extern "C" int64_t nlc_train_workspace_bytes(nlc_ctx* c, int64_t N) { return group_workspace_bytes(c, kFamNl, 1, N); }
 // train_utils.py:391-402 (zero_grad, forward, MSELoss, backward)
 extern "C" int nlc_train_loss_grad(nlc_ctx* c, const double* params, const double* obs, const double* window,
                                    const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                                    double* grad, double* loss, void* ws) {
-  return group_loss_grad_entry(c, false, 1, 0, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
+  return group_loss_grad_entry(c, kFamNl, 1, 0, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
 }
 // train_utils.py:391-404 (one whole iteration: + clip_grad_norm_ + optimizer.step())
 extern "C" int nlc_train_step(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, double* v, int64_t step,
                               const double* obs, const double* window, const double* ts, const double* target,
                               const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws) {
-  return group_step_entry(c, false, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
+  return group_step_entry(c, kFamNl, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
 }
 
 // ---- DeltaTRNN / RNN (train_utils.py:550-631): the same entries and contract; params, m, v flat in nlc_set_rnn_model's blob
 // order; ts may be NULL for a model without time input
 // train_utils.py:388-408, run_exp_multi.py:105-110
 extern "C" int64_t nlc_rnn_train_group_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
-  return group_workspace_bytes(c, true, M, N);
+  return group_workspace_bytes(c, kFamRnn, M, N);
 }
 // train_utils.py:391-402 per member, run_exp_multi.py:105-110
 extern "C" int nlc_rnn_train_group_loss_grad(nlc_ctx* c, int M, int64_t data_row_stride, const double* params,
                                              const double* obs, const double* window, const double* ts,
                                              const double* target, const int64_t* idx, int64_t N, int B, double* grad,
                                              double* loss, void* ws) {
-  return group_loss_grad_entry(c, true, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
+  return group_loss_grad_entry(c, kFamRnn, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
 }
 // train_utils.py:391-404 per member, run_exp_multi.py:105-110
 extern "C" int nlc_rnn_train_group_step(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride,
                                         double* params, double* m, double* v, int64_t step, const double* obs,
                                         const double* window, const double* ts, const double* target, const int64_t* idx,
                                         int64_t N, int B, double* loss, double* gradnorm, void* ws) {
-  return group_step_entry(c, true, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+  return group_step_entry(c, kFamRnn, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
                           gradnorm, ws);
 }
 // train_utils.py:388-408
-extern "C" int64_t nlc_rnn_train_workspace_bytes(nlc_ctx* c, int64_t N) { return group_workspace_bytes(c, true, 1, N); }
+extern "C" int64_t nlc_rnn_train_workspace_bytes(nlc_ctx* c, int64_t N) { return group_workspace_bytes(c, kFamRnn, 1, N); }
 // train_utils.py:391-402 (zero_grad, forward, MSELoss, backward)
 extern "C" int nlc_rnn_train_loss_grad(nlc_ctx* c, const double* params, const double* obs, const double* window,
                                        const double* ts, const double* target, const int64_t* idx, int64_t N, int B,
                                        double* grad, double* loss, void* ws) {
-  return group_loss_grad_entry(c, true, 1, 0, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
+  return group_loss_grad_entry(c, kFamRnn, 1, 0, params, obs, window, ts, target, idx, N, B, grad, loss, ws);
 }
 // train_utils.py:391-404 (one whole iteration: + clip_grad_norm_ + optimizer.step())
 extern "C" int nlc_rnn_train_step(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, double* v,
                                   int64_t step, const double* obs, const double* window, const double* ts,
                                   const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm,
                                   void* ws) {
-  return group_step_entry(c, true, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
+  return group_step_entry(c, kFamRnn, desc, 1, 0, params, m, v, step, obs, window, ts, target, idx, N, B, loss, gradnorm, ws);
 }
 
 // ---- held-out loss of both families: the forward and MSE of the reference's validation loss on the training entries' data
 // conventions; no gradient, no update.  loss [M]; idx may be NULL (rows 0 .. N - 1)
 // overlay.py:112-115, :175-177, run_exp_multi.py:105-110
 extern "C" int64_t nlc_train_group_eval_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
-  return group_eval_workspace_bytes(c, false, M, N);
+  return group_eval_workspace_bytes(c, kFamNl, M, N);
 }
 // overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110
 extern "C" int nlc_train_group_eval(nlc_ctx* c, int M, int64_t data_row_stride, const double* params, const double* obs,
                                     const double* window, const double* ts, const double* target, const int64_t* idx,
                                     int64_t N, int B, double* loss, void* ws) {
-  return group_eval_entry(c, false, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws);
+  return group_eval_entry(c, kFamNl, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws);
 }
 // overlay.py:112-115, :175-177
-extern "C" int64_t nlc_train_eval_workspace_bytes(nlc_ctx* c, int64_t N) { return group_eval_workspace_bytes(c, false, 1, N); }
+extern "C" int64_t nlc_train_eval_workspace_bytes(nlc_ctx* c, int64_t N) { return group_eval_workspace_bytes(c, kFamNl, 1, N); }
 // overlay.py:112-115, :175-177
 extern "C" int nlc_train_eval(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
                               const double* target, const int64_t* idx, int64_t N, int B, double* loss, void* ws) {
-  return group_eval_entry(c, false, 1, 0, params, obs, window, ts, target, idx, N, B, loss, ws);
+  return group_eval_entry(c, kFamNl, 1, 0, params, obs, window, ts, target, idx, N, B, loss, ws);
 }
 // overlay.py:112-115, :175-177, run_exp_multi.py:105-110
 extern "C" int64_t nlc_rnn_train_group_eval_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
-  return group_eval_workspace_bytes(c, true, M, N);
+  return group_eval_workspace_bytes(c, kFamRnn, M, N);
 }
 // overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110
 extern "C" int nlc_rnn_train_group_eval(nlc_ctx* c, int M, int64_t data_row_stride, const double* params, const double* obs,
                                         const double* window, const double* ts, const double* target, const int64_t* idx,
                                         int64_t N, int B, double* loss, void* ws) {
-  return group_eval_entry(c, true, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws);
+  return group_eval_entry(c, kFamRnn, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws);
 }
 // overlay.py:112-115, :175-177
-extern "C" int64_t nlc_rnn_train_eval_workspace_bytes(nlc_ctx* c, int64_t N) { return group_eval_workspace_bytes(c, true, 1, N); }
+extern "C" int64_t nlc_rnn_train_eval_workspace_bytes(nlc_ctx* c, int64_t N) { return group_eval_workspace_bytes(c, kFamRnn, 1, N); }
 // overlay.py:112-115, :175-177
 extern "C" int nlc_rnn_train_eval(nlc_ctx* c, const double* params, const double* obs, const double* window, const double* ts,
                                   const double* target, const int64_t* idx, int64_t N, int B, double* loss, void* ws) {
-  return group_eval_entry(c, true, 1, 0, params, obs, window, ts, target, idx, N, B, loss, ws);
+  return group_eval_entry(c, kFamRnn, 1, 0, params, obs, window, ts, target, idx, N, B, loss, ws);
+}
+
+// ---- NODE (train_utils.py:637-724): the RNN entries' signatures and contract plus row_times -- 0: every row of a member's batch
+// integrates to the time of its first row, ts[idx[0]] (train_utils.py:719; what NODE.forward does), non-zero: each row to its
+// own ts[idx[r]].  params, m, v flat in nlc_set_node_model's blob order; the model comes from nlc_set_node_model on the ctx.
+// The workspace is a function of (M, N) and the shape alone: a row's sub-step count is at most 256, a row whose time is not
+// positive or needs more gets a NaN squared error.  The single-model forms are M = 1, data_row_stride 0
+// train_utils.py:388-408, run_exp_multi.py:105-110
+extern "C" int64_t nlc_node_train_group_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
+  return group_workspace_bytes(c, kFamNode, M, N);
+}
+// train_utils.py:391-402 per member, run_exp_multi.py:105-110
+extern "C" int nlc_node_train_group_loss_grad(nlc_ctx* c, int M, int64_t data_row_stride, const double* params,
+                                              const double* obs, const double* window, const double* ts,
+                                              const double* target, const int64_t* idx, int64_t N, int B, double* grad,
+                                              double* loss, void* ws, int row_times) {
+  return group_loss_grad_entry(c, kFamNode, M, data_row_stride, params, obs, window, ts, target, idx, N, B, grad, loss, ws,
+                               row_times != 0);
+}
+// train_utils.py:391-404 per member, run_exp_multi.py:105-110
+extern "C" int nlc_node_train_group_step(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                         double* params, double* m, double* v, int64_t step, const double* obs,
+                                         const double* window, const double* ts, const double* target, const int64_t* idx,
+                                         int64_t N, int B, double* loss, double* gradnorm, void* ws, int row_times) {
+  return group_step_entry(c, kFamNode, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+                          gradnorm, ws, row_times != 0);
+}
+// overlay.py:112-115, :175-177, run_exp_multi.py:105-110
+extern "C" int64_t nlc_node_train_group_eval_workspace_bytes(nlc_ctx* c, int M, int64_t N) {
+  return group_eval_workspace_bytes(c, kFamNode, M, N);
+}
+// overlay.py:112-115, :175-177 per member, run_exp_multi.py:105-110
+extern "C" int nlc_node_train_group_eval(nlc_ctx* c, int M, int64_t data_row_stride, const double* params, const double* obs,
+                                         const double* window, const double* ts, const double* target, const int64_t* idx,
+                                         int64_t N, int B, double* loss, void* ws, int row_times) {
+  return group_eval_entry(c, kFamNode, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws, row_times != 0);
 }

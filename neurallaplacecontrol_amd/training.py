@@ -1,5 +1,5 @@
-"""Fused training step of ``NeuralLaplaceModel`` (``NLTrainer``) and of the ``DeltaTRNN`` / ``RNN`` baselines
-(``RNNTrainer``): the reference's training iteration (``train_utils.py:388-408``) --
+"""Fused training step of ``NeuralLaplaceModel`` (``NLTrainer``), of the ``DeltaTRNN`` / ``RNN`` baselines
+(``RNNTrainer``) and of the ``NODE`` baseline (``NODETrainer``): the reference's training iteration (``train_utils.py:388-408``) --
 
     pred_sd = model(bs0, ba0, bts); loss = nn.MSELoss()(pred_sd.squeeze(), bsd.squeeze())
     loss.backward(); torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()   # Adam
@@ -86,6 +86,10 @@ class _FusedTrainer:
     def _unsupported(self, model):
         """Why no fused kernels exist for ``model`` whatever its shape (None: ask the library)."""
         return None
+
+    def _extra_args(self):
+        """What the family's entries take after the workspace pointer (NODE: ``row_times``)."""
+        return ()
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
         self._init([model], lr, betas, eps, weight_decay, clip_grad_norm)
@@ -318,7 +322,8 @@ class _FusedTrainer:
         with ctx.stream():
             rc = getattr(ctx.lib, self._entries[1])(
                 ctx.h, self._M, rows, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt),
-                _i64_ptr(self._idx(N)), N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)))
+                _i64_ptr(self._idx(N)), N, win.shape[1], _f64_ptr(grad), _f64_ptr(loss), _f64_ptr(self._workspace(N)),
+                *self._extra_args())
         why = self._refused(rc)
         if why is not None:
             self._host_path(why)
@@ -358,7 +363,8 @@ class _FusedTrainer:
         with ctx.stream():
             rc = getattr(ctx.lib, self._eval_entries[1])(
                 ctx.h, M, stride, _f64_ptr(self._flat), _f64_ptr(obs), _f64_ptr(win), _f64_ptr(tsd), _f64_ptr(tgt),
-                C.c_void_p(0) if idx is None else _i64_ptr(idx), N, win.shape[1], _f64_ptr(loss), _f64_ptr(ws))
+                C.c_void_p(0) if idx is None else _i64_ptr(idx), N, win.shape[1], _f64_ptr(loss), _f64_ptr(ws),
+                *self._extra_args())
         why = self._refused(rc)
         if why is not None:
             self._host_path(why)
@@ -411,7 +417,7 @@ class _FusedTrainer:
         ctx.check(getattr(ctx.lib, self._entries[2])(
             ctx.h, C.byref(desc if desc is not None else self._desc()), self._M, rows, _f64_ptr(self._flat),
             _f64_ptr(self._m), _f64_ptr(self._v), self._step + 1, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt),
-            idx_ptr, N, win.shape[1], loss_ptr, None, _f64_ptr(ws)))
+            idx_ptr, N, win.shape[1], loss_ptr, None, _f64_ptr(ws), *self._extra_args()))
         self._step += 1
 
     def _refused(self, rc):
@@ -752,6 +758,67 @@ class RNNTrainer(_FusedTrainer):
         return bool(self.model._time_input)
 
 
+class NODETrainer(_FusedTrainer):
+    """``tr = NODETrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1,
+    row_times=False)`` for a ``NODE`` (``nlc_node_train_group_step``, M = 1): the methods and semantics of ``NLTrainer``.
+    The loss is the reference loop's: the MSE of the model's output (the integrated normalised state) against ``bsd``.
+
+    ``row_times=False`` is the reference's time semantics: every row of a batch integrates to the time of the batch's FIRST
+    row (``train_utils.py:719``; what ``model.forward`` does), which is why the reference trains NODE at batch size 1.
+    ``row_times=True`` integrates each row to its own time; on the grad-mode fallback that loops the rows one by one.
+
+    A row takes at most ``MAX_SUBSTEPS`` Euler sub-steps.  The first call with a given ``ts`` tensor reads it once on the host
+    and raises ``ValueError`` if a time is not positive or needs more; after that the tensor is not read again."""
+
+    _entries = ("nlc_node_train_group_workspace_bytes", "nlc_node_train_group_loss_grad", "nlc_node_train_group_step")
+    _eval_entries = ("nlc_node_train_group_eval_workspace_bytes", "nlc_node_train_group_eval")
+    MAX_SUBSTEPS = 256  # csrc/nlc_train_node.h kNodeTrainMaxSub
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1, row_times=False):
+        self.row_times = bool(row_times)
+        self._ts_seen = {}
+        self._init([model], lr, betas, eps, weight_decay, clip_grad_norm)
+
+    def _unsupported(self, model):
+        if getattr(model, "method", "euler") != "euler":
+            return f"method {model.method!r} has no fused training kernels (the fixed-grid Euler solver has)"
+        return None
+
+    def _extra_args(self):
+        return (int(self.row_times),)
+
+    def _check_ts(self, ts):
+        """One host read per dataset tensor: every time positive and within ``MAX_SUBSTEPS`` sub-steps of the model's grid
+        (torchdiffeq's ``ceil(t / step_size + 1)`` points), else ValueError -- before any launch."""
+        ts = torch.as_tensor(ts)
+        key = (ts.data_ptr(), ts._version, ts.numel(), self._model_key[0])
+        if key in self._ts_seen:
+            return
+        t_end = ts.detach().to(torch.float64).reshape(-1) / self.model._time_div()
+        ok = (t_end > 0) & (torch.ceil(t_end / float(self.model.step_size) + 1.0) <= self.MAX_SUBSTEPS + 1)
+        if not bool(ok.all()):
+            raise ValueError(f"{self._name}: every prediction time must be positive and need at most {self.MAX_SUBSTEPS} "
+                             f"Euler sub-steps of {self.model.step_size} (after normalize_time); ts holds one that does not")
+        if len(self._ts_seen) >= 64:
+            self._ts_seen.clear()
+        self._ts_seen[key] = True
+
+    def _group_data(self, s0, a0, ts, target):
+        self._check_ts(ts)
+        out = super()._group_data(s0, a0, ts, target)
+        if out[1].shape[2] != self.model.action_dim:
+            raise ValueError(f"{self._name}: a0 must be (N, B, {self.model.action_dim}) or (N, {self.model.action_dim})")
+        return out
+
+    def _ref_loss(self, bs0, ba0, bts, bsd, i=0):
+        if not self.row_times:
+            return super()._ref_loss(bs0, ba0, bts, bsd, i)
+        # _forward_train integrates a batch to its first row's time: one row at a time
+        mdl, bts = self.models[i], torch.as_tensor(bts).reshape(-1, 1)
+        pred = torch.cat([mdl(bs0[r : r + 1], ba0[r : r + 1], bts[r : r + 1]) for r in range(bs0.shape[0])])
+        return torch.nn.functional.mse_loss(pred.squeeze(), bsd.squeeze())
+
+
 class NLTrainerGroup(_Group, NLTrainer):
     """``grp = NLTrainerGroup(models, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)``: M
     ``NeuralLaplaceModel`` s of one descriptor (run_exp_multi.py:105-110: the delays and seeds of one env) trained by the
@@ -771,3 +838,13 @@ class NLTrainerGroup(_Group, NLTrainer):
 class RNNTrainerGroup(_Group, RNNTrainer):
     """``grp = RNNTrainerGroup(models, ...)``: M ``DeltaTRNN`` s or M ``RNN`` s of one descriptor; the methods and
     semantics of ``NLTrainerGroup``."""
+
+
+class NODETrainerGroup(_Group, NODETrainer):
+    """``grp = NODETrainerGroup(models, ..., row_times=False)``: M ``NODE`` s of one descriptor; the methods and semantics of
+    ``NLTrainerGroup``.  ``row_times`` is the group's: one value for all members, like the optimiser's hyper-parameters."""
+
+    def __init__(self, models, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1, row_times=False):
+        self.row_times = bool(row_times)
+        self._ts_seen = {}
+        self._init(models, lr, betas, eps, weight_decay, clip_grad_norm)

@@ -1,5 +1,7 @@
-"""Training-step throughput on cartpole of NeuralLaplaceModel (d = 5, h = 128, S = 17, B = 4; --model nl, the default) or of
-the DeltaTRNN baseline (d = 5, H = 160, B = 4; --model delta_t_rnn, RNNTrainer), one JSON line:
+"""Training-step throughput on cartpole of NeuralLaplaceModel (d = 5, h = 128, S = 17, B = 4; --model nl, the default), of
+the DeltaTRNN baseline (d = 5, H = 160, B = 4; --model delta_t_rnn, RNNTrainer) or of the NODE baseline (d = 5, augment 1,
+H = 270; --model node, NODETrainer; give it --batches 1 16: the reference trains NODE at batch 1, train_utils.py:319-320, and
+every variant is then timed --repeats times, median and min .. max), one JSON line:
 
   (a) the reference's iteration (train_utils.py:391-408) through the existing grad-mode model(...): forward, MSELoss,
       backward, clip_grad_norm_(0.1), torch.optim.Adam.step(), loss.item() every iteration;
@@ -65,14 +67,18 @@ from oracle import nl_model as onl  # noqa: E402
 
 ENV, D, NU, H, S, B = "oderl-cartpole", 5, 1, 128, 17, 4
 RNN_H = 160  # rnn_hidden_units, config.py:43
+NODE_H, NODE_AUG = 270, 1  # node_hidden_units, node_augment_dim, config.py:41-42
 MODEL = "nl"
 ILT = "fourier"  # --ilt-algorithm (NL model)
 WORKLOADS = {"nl": "NeuralLaplaceModel training step, cartpole d=5 h=128 S=17 B=4, float64",
-             "delta_t_rnn": "DeltaTRNN training step, cartpole d=5 H=160 B=4, float64"}
+             "delta_t_rnn": "DeltaTRNN training step, cartpole d=5 H=160 B=4, float64",
+             "node": "NODE training step, cartpole d=5 augment=1 H=270 (Euler, step 0.05, normalize_time), float64"}
+TRAINERS = {"nl": ("NLTrainer", "NLTrainerGroup"), "delta_t_rnn": ("RNNTrainer", "RNNTrainerGroup"),
+            "node": ("NODETrainer", "NODETrainerGroup")}
 
 
 def make_trainer(model):
-    tr = nlc.RNNTrainer(model) if MODEL == "delta_t_rnn" else nlc.NLTrainer(model)
+    tr = getattr(nlc, TRAINERS[MODEL][0])(model)
     assert tr.fused, "the benchmark times the fused step"
     return tr
 
@@ -85,6 +91,14 @@ def make_model(seed=0):
         sd = orn.make_synthetic_state_dict(seed, D, NU, RNN_H, st["state_std"], [st["act_high"] / 2])
         m = nlc.DeltaTRNN(D, NU, hidden_units=RNN_H, state_mean=np.zeros(D), state_std=np.ones(D), action_mean=np.array([0]),
                           action_std=np.array([1.0]), normalize=True, normalize_time=True).double()
+        m.load_state_dict(sd)
+        return m.to("cuda")
+    if MODEL == "node":
+        from oracle import node_model as ond
+
+        sd = ond.make_synthetic_state_dict(seed, D, NU, NODE_H, NODE_AUG, st["state_std"], None)
+        m = nlc.NODE(D, NU, D, hidden_units=NODE_H, state_mean=np.zeros(D), state_std=np.ones(D), action_mean=np.array([0]),
+                     action_std=np.array([1.0]), normalize=True, normalize_time=True, augment_dim=NODE_AUG).double()
         m.load_state_dict(sd)
         return m.to("cuda")
     sd = onl.make_synthetic_state_dict(seed, D, NU, H, S, st["state_std"], [st["act_high"] / 2], tame=True)
@@ -178,7 +192,7 @@ def time_group(bs, iters, warm, M, repeats):
     if M == 0:
         tr, perms = make_trainer(models[0]), perms[0]
     else:
-        tr = (nlc.RNNTrainerGroup if MODEL == "delta_t_rnn" else nlc.NLTrainerGroup)(models)
+        tr = getattr(nlc, TRAINERS[MODEL][1])(models)
     assert tr.fused
     tr.run(s0, a0, sn, ts, perms[..., : bs * warm], batch_size=bs)
     torch.cuda.synchronize()
@@ -319,6 +333,9 @@ def flops_per_iter(bs):
     and element-wise work not counted."""
     if MODEL == "delta_t_rnn":
         return int(2 * bs * 3 * (B * 3 * RNN_H * (NU + RNN_H) + D * (RNN_H + D + 1)))
+    if MODEL == "node":  # at the fixed grid's 3 sub-steps (ts = dt under normalize_time)
+        dy = D + NODE_AUG
+        return int(2 * bs * 3 * 3 * (NODE_H * (dy + NU) + NODE_H * NODE_H + dy * NODE_H))
     g, K0, O = H // 2, 2 * S + D + 2, 2 * D * S
     gru = B * (3 * g * (NU + g) + 3 * g * (g + g))  # both layers, per row per window
     mlp = K0 * H + H * H + H * O
@@ -429,7 +446,8 @@ def main():
         bs = args.batches[0]
         res = {"device": torch.cuda.get_device_name(0), "batch": bs, "run_iters": args.run_iters, "repeats": args.repeats,
                "families": {}}
-        for MODEL in sorted(WORKLOADS):
+        # --model node: that family alone, at its own batch size; else the two families the tool has always timed together
+        for MODEL in (["node"] if args.model == "node" else ["delta_t_rnn", "nl"]):
             fam = {"workload": WORKLOADS[MODEL], "groups": {}}
             for M in [0] + list(args.group):  # 0: the single trainer, in the same session
                 r = spread(measure(bs, f"group{M}"))
@@ -450,7 +468,8 @@ def main():
             res["families"][MODEL] = fam
         line = json.dumps(res)
         print(line)
-        with open(args.out or os.path.join(REPO, "profiles", "train_bench_group.json"), "w") as f:
+        default = "train_bench_node_group.json" if args.model == "node" else "train_bench_group.json"
+        with open(args.out or os.path.join(REPO, "profiles", default), "w") as f:
             f.write(line + "\n")
         return
 
@@ -459,12 +478,21 @@ def main():
         res["ilt_algorithm"], res["terms"] = ILT, S
     for bs in args.batches:
         r = {"flops_per_iter": flops_per_iter(bs)}
+
+        def timed(variant):
+            """One measurement; --model node: --repeats of them (a child process each), the median kept as VARIANT_it_s."""
+            if MODEL != "node":
+                return measure(bs, variant)
+            s = spread([measure(bs, variant) for _ in range(args.repeats)])
+            r[f"{variant}_it_s_min"], r[f"{variant}_it_s_max"] = s["it_s_min"], s["it_s_max"]
+            return s["it_s"]
+
         if args.only in (None, "ref"):
-            r["ref_it_s"] = measure(bs, "ref")
+            r["ref_it_s"] = timed("ref")
         if args.only in (None, "step"):
-            r["step_it_s"] = measure(bs, "step")
+            r["step_it_s"] = timed("step")
         if args.only in (None, "run"):
-            r["run_it_s"] = measure(bs, "run")
+            r["run_it_s"] = timed("run")
             r["run_iters"] = args.run_iters
         if args.kernel_ms:
             r["kernel_ms"] = measure(bs, "kernel_ms")
