@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 18
+#define NLC_ABI_VERSION 19
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -519,6 +519,48 @@ int nlc_node_train_group_eval(nlc_ctx* ctx, int M, int64_t data_row_stride, cons
                               const double* window_dev, const double* ts_dev, const double* target_dev,
                               const int64_t* idx_dev /* NULL: rows 0..N-1 */, int64_t N, int B, double* loss_dev /* [M] */,
                               void* ws_dev, int row_times);
+
+/* ---- per-member settings and patience of a group: a sweep over learning rate, weight decay or clip norm (config.py:
+ *      sweep_mode, learning_rate, weight_decay, clip_grad_norm) as one group, each member stopping when it stops improving
+ *      (waiting / patience, train_utils.py:315-317, :439-448).
+ *   The three _members entries are their _group_step with a trailing nlc_train_members: four device arrays [M] read by the
+ *   clip + Adam launch in place of desc's lr, weight_decay and max_grad_norm (which are then not read; the betas, eps and the
+ *   step count stay one per group).  max_norm <= 0: no clipping; wd == 0: no decay term.  A member with active == 0 is frozen:
+ *   its rows of params_dev, m_dev and v_dev are neither read nor written by the update; its forward, backward and reduction
+ *   still run, so loss_dev and gradnorm_dev report it.  An active member's results are bit-identical to _group_step's with
+ *   its scalars.  The checks are _group_step's, in their order; a NULL struct or a NULL array in it: NLC_ERR_BAD_ARG, before
+ *   any launch. */
+typedef struct {
+  const double* lr_dev;       /* [M] learning rates */
+  const double* wd_dev;       /* [M] weight decays */
+  const double* max_norm_dev; /* [M] clip_grad_norm_'s max_norm; <= 0: no clipping */
+  const int32_t* active_dev;  /* [M] 0: frozen */
+} nlc_train_members;
+/* train_utils.py:391-404 per member, config.py (sweep_mode) */
+int nlc_train_group_step_members(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_t data_row_stride, double* params_dev,
+                                 double* m_dev, double* v_dev, int64_t step, const double* obs_dev, const double* window_dev,
+                                 const double* ts_dev, const double* target_dev, const int64_t* idx_dev, int64_t N, int B,
+                                 double* loss_dev, double* gradnorm_dev, void* ws_dev, const nlc_train_members* members);
+/* train_utils.py:391-404 per member, config.py (sweep_mode) */
+int nlc_rnn_train_group_step_members(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                     double* params_dev, double* m_dev, double* v_dev, int64_t step, const double* obs_dev,
+                                     const double* window_dev, const double* ts_dev, const double* target_dev,
+                                     const int64_t* idx_dev, int64_t N, int B, double* loss_dev, double* gradnorm_dev,
+                                     void* ws_dev, const nlc_train_members* members);
+/* train_utils.py:391-404 per member, config.py (sweep_mode) */
+int nlc_node_train_group_step_members(nlc_ctx* ctx, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                      double* params_dev, double* m_dev, double* v_dev, int64_t step, const double* obs_dev,
+                                      const double* window_dev, const double* ts_dev, const double* target_dev,
+                                      const int64_t* idx_dev, int64_t N, int B, double* loss_dev, double* gradnorm_dev,
+                                      void* ws_dev, int row_times, const nlc_train_members* members);
+/* The reference's early-stopping counter at one check, per member and on the device, after nlc_train_keep_best in stream
+ * order (improved_dev is its flags): an active member that improved gets waiting = 0; else, if waiting > patience, active = 0
+ * and stopped_at = tag; else waiting += 1.  A member with active == 0 is left alone.  patience may be +inf (the reference's
+ * default: nobody stops).  Needs no model in the ctx.  Refused on the host before any launch: a NULL pointer or a NaN
+ * patience: NLC_ERR_BAD_ARG; M < 1: NLC_ERR_BAD_SHAPE; M > 65535: NLC_ERR_UNSUPPORTED. */
+/* train_utils.py:315-317, :439-448 */
+int nlc_train_patience(nlc_ctx* ctx, int M, const int32_t* improved_dev, int64_t* waiting_dev, int32_t* active_dev,
+                       int64_t* stopped_at_dev, double patience, int64_t tag);
 
 /* ---- planner: MPPIDelay (planners/mppi_delay.py:54-381) ------------------------------------- */
 typedef struct {

@@ -92,6 +92,10 @@ SYMBOLS = [
     "nlc_node_train_group_step",
     "nlc_node_train_group_eval_workspace_bytes",
     "nlc_node_train_group_eval",
+    "nlc_train_group_step_members",
+    "nlc_rnn_train_group_step_members",
+    "nlc_node_train_group_step_members",
+    "nlc_train_patience",
     "nlc_mppi_configure",
     "nlc_mppi_workspace_bytes",
     "nlc_mppi_set_U",
@@ -163,6 +167,12 @@ class ModelDesc(C.Structure):
 class TrainDesc(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("max_grad_norm", C.c_double)]
+
+
+class TrainMembers(C.Structure):
+    """``nlc_train_members``: the per-member settings of a ``_members`` step, four device arrays [M]."""
+
+    _fields_ = [("lr_dev", C.c_void_p), ("wd_dev", C.c_void_p), ("max_norm_dev", C.c_void_p), ("active_dev", C.c_void_p)]
 
 
 class MppiDesc(C.Structure):
@@ -329,6 +339,11 @@ def load_library():
         lib.nlc_node_train_group_eval_workspace_bytes.argtypes = lib.nlc_train_group_eval_workspace_bytes.argtypes
         lib.nlc_node_train_group_eval_workspace_bytes.restype = i64
         lib.nlc_node_train_group_eval.argtypes = lib.nlc_train_group_eval.argtypes + [i32]
+        # per-member settings: the _group_step entries plus a trailing nlc_train_members; the patience counter: M, improved,
+        # waiting, active, stopped_at, patience, tag
+        for fam in ("nlc_train", "nlc_rnn_train", "nlc_node_train"):
+            getattr(lib, fam + "_group_step_members").argtypes = getattr(lib, fam + "_group_step").argtypes + [P(TrainMembers)]
+        lib.nlc_train_patience.argtypes = [vp, i32, vp, vp, vp, vp, dbl, i64]
         # snapshot selection: M, P, loss, params, best_loss, best_params, best_tag, tag, improved
         lib.nlc_train_keep_best.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, i64, vp]
         lib.nlc_rnn_blob_size.argtypes = [P(RnnDesc)]

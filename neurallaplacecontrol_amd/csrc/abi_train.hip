@@ -10,6 +10,7 @@
 #include "nlc_host.h"
 #include "nlc_train.h"
 #include "nlc_train_eval.h"
+#include "nlc_train_members.h"
 #include "nlc_train_node.h"
 
 using namespace nlc;
@@ -182,6 +183,38 @@ int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, doub
   a.gs = p.gs;
   ProfScope ps(c, "train_adam_kernel");
   NLC_HIP(c, launch_train_adam(a, p.M, c->stream));
+  return NLC_OK;
+}
+
+// the same launch with lr, weight decay, clip norm and the active flag per member, from device arrays (kernels_train_members.hip);
+// desc gives the betas and eps, its lr / weight_decay / max_grad_norm are not read
+int adam_members(nlc_ctx* c, const nlc_train_desc* desc, const nlc_train_members* mem, double* params, double* m, double* v,
+                 int64_t step, double* gradnorm, const Plan& p, const WsPtrs& w) {
+  MembersAdamArgs a{};
+  a.params = params;
+  a.m = m;
+  a.v = v;
+  a.grad = w.grad;
+  a.sq = w.sq;
+  a.lr = mem->lr_dev;
+  a.wd = mem->wd_dev;
+  a.max_norm = mem->max_norm_dev;
+  a.active = mem->active_dev;
+  const double bc2 = 1.0 - std::pow(desc->beta2, (double)step);
+  a.omb1 = 1.0 - desc->beta1;
+  a.beta2 = desc->beta2;
+  a.omb2 = 1.0 - desc->beta2;
+  a.eps = desc->eps;
+  a.bc1 = 1.0 - std::pow(desc->beta1, (double)step);
+  a.bc2_sqrt = std::pow(bc2, 0.5);
+  a.gradnorm = gradnorm;
+  for (int i = 0; i <= kTensors; ++i) {
+    a.off[i] = p.off[i];
+    a.cstart[i] = p.cstart[i];
+  }
+  a.gs = p.gs;
+  ProfScope ps(c, "train_adam_members_kernel");
+  NLC_HIP(c, launch_train_adam_members(a, p.M, c->stream));
   return NLC_OK;
 }
 
@@ -366,14 +399,18 @@ int group_loss_grad_entry(nlc_ctx* c, Family fam, int M, int64_t data_rows, cons
 int group_step_entry(nlc_ctx* c, Family fam, const nlc_train_desc* desc, int M, int64_t data_rows, double* params, double* m,
                      double* v, int64_t step, const double* obs, const double* window, const double* ts,
                      const double* target, const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws,
-                     int row_times = 0) {
+                     int row_times = 0, bool per_member = false, const nlc_train_members* mem = nullptr) {
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
   if (!desc) return fail(c, NLC_ERR_BAD_ARG, "NULL train desc");
+  // (a _members entry: its struct and the four arrays count among the step's own pointers)
+  const bool mem_null = per_member && (!mem || !mem->lr_dev || !mem->wd_dev || !mem->max_norm_dev || !mem->active_dev);
   Plan p;
   if (int rc = group_loss_grad(c, fam, M, data_rows, params, obs, window, ts, target, idx, N, B, nullptr, loss, ws, &p,
-                               row_times, &step, !m || !v))
+                               row_times, &step, !m || !v || mem_null))
     return rc;
+  // only the last launch differs
+  if (per_member) return adam_members(c, desc, mem, params, m, v, step, gradnorm, p, ws_ptrs(p, ws));
   return adam(c, desc, params, m, v, step, gradnorm, p, ws_ptrs(p, ws));
   NLC_GUARD_END(c)
 }
@@ -557,4 +594,54 @@ extern "C" int nlc_node_train_group_eval(nlc_ctx* c, int M, int64_t data_row_str
                                          const double* window, const double* ts, const double* target, const int64_t* idx,
                                          int64_t N, int B, double* loss, void* ws, int row_times) {
   return group_eval_entry(c, kFamNode, M, data_row_stride, params, obs, window, ts, target, idx, N, B, loss, ws, row_times != 0);
+}
+
+// ---- per-member settings (kernels_train_members.hip): the _group_step entries with lr, weight decay, clip norm and an active
+// flag per member from device arrays [M]; desc gives the betas and eps (its lr, weight_decay and max_grad_norm are not read).
+// The checks are the _group_step entries', in their order; a NULL struct or a NULL array in it is a NULL device pointer.  A
+// member with active == 0 keeps its params / m / v untouched; its forward, backward, loss and gradnorm are still computed
+// train_utils.py:391-404 per member, config.py (sweep_mode: learning_rate, weight_decay, clip_grad_norm)
+extern "C" int nlc_train_group_step_members(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                            double* params, double* m, double* v, int64_t step, const double* obs,
+                                            const double* window, const double* ts, const double* target, const int64_t* idx,
+                                            int64_t N, int B, double* loss, double* gradnorm, void* ws,
+                                            const nlc_train_members* members) {
+  return group_step_entry(c, kFamNl, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+                          gradnorm, ws, 0, true, members);
+}
+// train_utils.py:391-404 per member, config.py (sweep_mode)
+extern "C" int nlc_rnn_train_group_step_members(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                                double* params, double* m, double* v, int64_t step, const double* obs,
+                                                const double* window, const double* ts, const double* target,
+                                                const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws,
+                                                const nlc_train_members* members) {
+  return group_step_entry(c, kFamRnn, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+                          gradnorm, ws, 0, true, members);
+}
+// train_utils.py:391-404 per member, config.py (sweep_mode)
+extern "C" int nlc_node_train_group_step_members(nlc_ctx* c, const nlc_train_desc* desc, int M, int64_t data_row_stride,
+                                                 double* params, double* m, double* v, int64_t step, const double* obs,
+                                                 const double* window, const double* ts, const double* target,
+                                                 const int64_t* idx, int64_t N, int B, double* loss, double* gradnorm, void* ws,
+                                                 int row_times, const nlc_train_members* members) {
+  return group_step_entry(c, kFamNode, desc, M, data_row_stride, params, m, v, step, obs, window, ts, target, idx, N, B, loss,
+                          gradnorm, ws, row_times != 0, true, members);
+}
+
+// the reference's waiting / patience counter per member, after nlc_train_keep_best in stream order; reads no model from the ctx
+// train_utils.py:315-317, :439-448
+extern "C" int nlc_train_patience(nlc_ctx* c, int M, const int32_t* improved, int64_t* waiting, int32_t* active,
+                                  int64_t* stopped_at, double patience, int64_t tag) {
+  if (!c) return NLC_ERR_BAD_ARG;
+  NLC_GUARD_BEGIN
+  if (!improved || !waiting || !active || !stopped_at) return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
+  if (M < 1) return fail(c, NLC_ERR_BAD_SHAPE, "patience: a group needs M >= 1 members");
+  if (M > kMaxGroup) return fail(c, NLC_ERR_UNSUPPORTED, "patience: at most 65535 members in a group");
+  if (patience != patience) return fail(c, NLC_ERR_BAD_ARG, "patience: patience must not be NaN");
+  NLC_HIP(c, hipSetDevice(c->device));
+  const PatienceArgs a{improved, waiting, active, stopped_at, patience, tag, M};
+  ProfScope ps(c, "train_patience_kernel");
+  NLC_HIP(c, launch_train_patience(a, c->stream));
+  return NLC_OK;
+  NLC_GUARD_END(c)
 }

@@ -24,6 +24,11 @@ the normalisation constants -- in the same three launches, the member on the gri
 (``nlc_train_group_step`` / ``nlc_rnn_train_group_step``).  ``_FusedTrainer`` is written over a list of members: a single
 trainer is the group of one, and the group classes only change what a call takes (stacked data, ``(M, L)`` permutations) and
 returns (``(M,)`` losses, a list of optimiser states).  A member's results are bit-identical to its single trainer's.
+
+A group's ``lr``, ``weight_decay`` and ``clip_grad_norm`` may be sequences of M numbers (the reference's sweeps, ``config.py``
+``sweep_mode``), members can be frozen (``freeze`` / ``unfreeze``), and ``fit(patience=)`` freezes each member when it stops
+improving (``train_utils.py:315-317``, ``:439-448``): the step is then ``nlc_*_train_group_step_members``, whose Adam launch
+reads the settings and an ``active`` flag per member from device arrays; a group of scalar settings calls what it always has.
 """
 
 import ctypes as C
@@ -107,9 +112,17 @@ class _FusedTrainer:
             mdl._require_float64()
             if not next(mdl.parameters()).is_cuda:
                 raise RuntimeError("training: move the model to the GPU first (model.to('cuda'))")
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.weight_decay, self.clip_grad_norm = float(weight_decay), float(clip_grad_norm)
+        self._hyper, self._members_dirty, self._mem = {}, True, None
+        self.lr, self.betas, self.eps = lr, (float(betas[0]), float(betas[1])), float(eps)
+        self.weight_decay, self.clip_grad_norm = weight_decay, clip_grad_norm
         self._dev = compute_device(next(model.parameters()))
+        # per-member state (a group's freeze / unfreeze, fit's patience): the flags the _members step reads, the Adam step
+        # count at which a member was frozen (-1: active), and the patience counter's waiting / stopped_at
+        self._active = torch.ones(self._M, dtype=torch.int32, device=self._dev)
+        self._frozen_step = torch.full((self._M,), -1, dtype=torch.int64, device=self._dev)
+        self._waiting = torch.zeros(self._M, dtype=torch.int64, device=self._dev)
+        self._stopped_at = torch.full((self._M,), -1, dtype=torch.int64, device=self._dev)
+        self._frozen_any = False  # True from the first freeze on: the group then calls the _members entries
         # blob order (= model.parameters() order), per member
         self._mparams = [[dict(mdl.named_parameters())[k] for k in mdl._BLOB_KEYS] for mdl in self.models]
         self._params = self._mparams[0]
@@ -139,6 +152,72 @@ class _FusedTrainer:
     def fused(self):
         """True when the fused HIP step runs (False: the fallback's torch optimiser)."""
         return self._fallback is None
+
+    # ------------------------------------------------------------------ settings: one number, or one per member of a group
+    def _set_hyper(self, name, value):
+        """A single trainer takes a number; a group a number or a sequence of M numbers (kept as a tuple).  A group refuses a
+        negative ``lr`` / ``weight_decay`` as ``torch.optim.Adam`` does."""
+        if self._grouped and not isinstance(value, (int, float)) and hasattr(value, "__len__") and not (
+                torch.is_tensor(value) and value.dim() == 0):
+            value = tuple(float(x) for x in value)
+            if len(value) != self._M:
+                raise ValueError(f"{self._name}: {name} must be a number or a sequence of {self._M} numbers, one per member "
+                                 f"(got {len(value)})")
+            each = value
+        else:
+            value = float(value)
+            each = (value,)
+        if self._grouped and name != "clip_grad_norm" and not all(0.0 <= x for x in each):
+            raise ValueError(f"{self._name}: Invalid {name} value: {value}")
+        self._hyper[name] = value
+        self._members_dirty = True
+
+    lr = property(lambda self: self._hyper["lr"], lambda self, v: self._set_hyper("lr", v))
+    weight_decay = property(lambda self: self._hyper["weight_decay"], lambda self, v: self._set_hyper("weight_decay", v))
+    clip_grad_norm = property(lambda self: self._hyper["clip_grad_norm"], lambda self, v: self._set_hyper("clip_grad_norm", v))
+
+    def _of(self, name, i):
+        """Member ``i``'s value of a setting."""
+        v = self._hyper[name]
+        return v[i] if isinstance(v, tuple) else v
+
+    def _per_member(self):
+        """True once a setting is a sequence or a member has been frozen: the step is then the library's ``_members`` entry,
+        which reads the settings and the flags from device arrays.  Otherwise the step is the entry it has always been."""
+        return self._frozen_any or any(isinstance(v, tuple) for v in self._hyper.values())
+
+    def _members_arg(self):
+        """``nlc_train_members`` of the group; the three setting arrays are uploaded again only after one was assigned."""
+        if self._members_dirty or self._mem is None:
+            up = lambda k: torch.tensor([self._of(k, i) for i in range(self._M)], dtype=torch.float64, device=self._dev)  # noqa: E731
+            self._mem_arrays = (up("lr"), up("weight_decay"), up("clip_grad_norm"))
+            self._mem = _lib.TrainMembers(*(t.data_ptr() for t in self._mem_arrays), self._active.data_ptr())
+            self._members_dirty = False
+        return self._mem
+
+    def _mask(self, mask):
+        mask = torch.as_tensor(mask).to(self._dev).reshape(-1) != 0
+        if mask.numel() != self._M:
+            raise ValueError(f"{self._name}: a member mask holds {self._M} values")
+        return mask
+
+    def _freeze(self, mask):
+        mask = self._mask(mask)
+        newly = mask & (self._active != 0)
+        self._frozen_step.copy_(torch.where(newly, torch.full_like(self._frozen_step, self._step_count()), self._frozen_step))
+        self._active.masked_fill_(mask, 0)
+        self._frozen_any = True
+
+    def _unfreeze(self, mask):
+        mask = self._mask(mask)
+        self._active.masked_fill_(mask, 1)
+        self._frozen_step.masked_fill_(mask, -1)
+        self._stopped_at.masked_fill_(mask, -1)
+        self._waiting.masked_fill_(mask, 0)
+
+    def _frozen_host(self):
+        """Which members are frozen, read on the host (only the paths that synchronise anyway use it)."""
+        return [a == 0 for a in self._active.tolist()] if self._frozen_any else [False] * self._M
 
     # ------------------------------------------------------------------ plumbing
     def _model_state_key(self, model=None):
@@ -248,7 +327,9 @@ class _FusedTrainer:
         return self._sync_model() if self.fused else ""
 
     def _desc(self):
-        return _lib.TrainDesc(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.clip_grad_norm)
+        # (with per-member settings the library reads lr, weight decay and clip norm from _members_arg(), not from here)
+        return _lib.TrainDesc(self._of("lr", 0), self.betas[0], self.betas[1], self.eps, self._of("weight_decay", 0),
+                              self._of("clip_grad_norm", 0))
 
     def _data(self, s0, a0, ts, target):
         f64 = lambda t: torch.as_tensor(t).detach().to(self._dev, torch.float64).contiguous()  # noqa: E731
@@ -412,12 +493,16 @@ class _FusedTrainer:
     def _launch_step(self, idx_ptr, obs, win, ts, tgt, N, loss_ptr, ws, desc=None, rows=0):
         """One ``nlc_train_group_step`` / ``nlc_rnn_train_group_step`` (idx ``[M][N]``, loss ``[M]``, ``rows`` the
         data_row_stride); the Adam step count moves only once the library has accepted the call (it checks everything on
-        the host before the first launch)."""
+        the host before the first launch).  With per-member settings or a frozen member it is the ``_members`` entry of the
+        same signature plus the group's ``nlc_train_members``."""
         ctx = self._ctx
-        ctx.check(getattr(ctx.lib, self._entries[2])(
+        entry, more = self._entries[2], ()
+        if self._per_member():
+            entry, more = entry + "_members", (C.byref(self._members_arg()),)
+        ctx.check(getattr(ctx.lib, entry)(
             ctx.h, C.byref(desc if desc is not None else self._desc()), self._M, rows, _f64_ptr(self._flat),
             _f64_ptr(self._m), _f64_ptr(self._v), self._step + 1, _f64_ptr(obs), _f64_ptr(win), _f64_ptr(ts), _f64_ptr(tgt),
-            idx_ptr, N, win.shape[1], loss_ptr, None, _f64_ptr(ws), *self._extra_args()))
+            idx_ptr, N, win.shape[1], loss_ptr, None, _f64_ptr(ws), *self._extra_args(), *more))
         self._step += 1
 
     def _refused(self, rc):
@@ -443,8 +528,11 @@ class _FusedTrainer:
         transient torch.optim.Adam that starts from the trainer's step count and the member's moments and hands them back:
         the trainer keeps one optimiser state.  Returns the ``(M, iterations)`` losses."""
         self._host_path(why)
-        out, step = [], self._step
+        out, step, frozen = [], self._step, self._frozen_host()
         for i, mine in enumerate(batches):
+            if frozen[i]:  # skipped: its losses on the weights it stopped with, no optimiser
+                out.append([self._frozen_loss(*b, i=i) for b in mine])
+                continue
             opt = self._adam(i)
             self._export_state(opt, i)
             out.append([self._fallback_step(*b, opt=opt, i=i) for b in mine])
@@ -455,22 +543,31 @@ class _FusedTrainer:
                         m.copy_(opt.state[p]["exp_avg"])
                         v.copy_(opt.state[p]["exp_avg_sq"])
                 step = int(st["step"])
-        self._step = step  # every member made the same number of steps from the same count
+        self._step = step  # every active member made the same number of steps from the same count
         if not out[0]:
             return torch.empty(self._M, 0, dtype=torch.float64, device=self._dev)
         return torch.stack([torch.stack(o) for o in out])
 
     def _fallback_step(self, bs0, ba0, bts, bsd, opt=None, i=0):
-        opt = self._fallback[i] if opt is None else opt
+        if opt is None:  # a non-fused trainer's own optimiser: a frozen member is skipped (this path synchronises anyway)
+            if self._frozen_any and int(self._active[i]) == 0:
+                return self._frozen_loss(bs0, ba0, bts, bsd, i=i)
+            opt = self._fallback[i]
         for grp in opt.param_groups:
-            grp["lr"] = self.lr
+            grp["lr"] = self._of("lr", i)
         opt.zero_grad()
         loss = self._ref_loss(bs0, ba0, bts, bsd, i=i)
         loss.backward()
-        if self.clip_grad_norm > 0:
-            torch.nn.utils.clip_grad_norm_(self.models[i].parameters(), self.clip_grad_norm)
+        clip = self._of("clip_grad_norm", i)
+        if clip > 0:
+            torch.nn.utils.clip_grad_norm_(self.models[i].parameters(), clip)
         opt.step()
         return loss.detach()
+
+    def _frozen_loss(self, bs0, ba0, bts, bsd, i=0):
+        """What a frozen member reports on the grad-mode path: the loss on its weights, no gradient, no update."""
+        with torch.no_grad():
+            return self._ref_loss(bs0, ba0, bts, bsd, i=i).detach()
 
     def run(self, s0, a0, sn, ts, permutation, batch_size=16):
         """Every full batch of ``permutation`` (train_utils.py:388-408 with ``bsd = bsn - bs0``): returns the (iters,) losses
@@ -600,7 +697,30 @@ class _FusedTrainer:
                 for p, v in zip(ps, self._views(self._best, i)):
                     p.copy_(v)
 
-    def fit(self, data, val=None, *, epochs=1, batch_size=16, eval_every=1000, seed=0, step_lr=None, restore_best=True):
+    def _patience(self, improved, patience, tag):
+        """The reference's waiting / patience counter (train_utils.py:439-448) after a ``keep_best``, without a host read: an
+        active member that improved waits from 0 again; one that did not and has ``waiting > patience`` is frozen, with
+        ``stopped_at = tag``; else its ``waiting`` grows by one.  Fused: ``nlc_train_patience``, one launch; a non-fused
+        trainer applies the same rule in torch ops."""
+        improved = improved.reshape(-1).contiguous()
+        if self.fused:
+            ctx = self._ctx
+            with ctx.stream():
+                ctx.check(ctx.lib.nlc_train_patience(
+                    ctx.h, self._M, C.c_void_p(improved.data_ptr()), _i64_ptr(self._waiting),
+                    C.c_void_p(self._active.data_ptr()), _i64_ptr(self._stopped_at), float(patience), int(tag)))
+        else:
+            live, better = self._active != 0, improved != 0
+            stop = live & ~better & (self._waiting.to(torch.float64) > float(patience))
+            self._waiting.copy_(torch.where(live & better, torch.zeros_like(self._waiting),
+                                            torch.where(live & ~better & ~stop, self._waiting + 1, self._waiting)))
+            self._stopped_at.masked_fill_(stop, int(tag))
+            self._active.masked_fill_(stop, 0)
+        newly = (self._active == 0) & (self._frozen_step < 0)
+        self._frozen_step.copy_(torch.where(newly, torch.full_like(self._frozen_step, self._step_count()), self._frozen_step))
+
+    def fit(self, data, val=None, *, epochs=1, batch_size=16, eval_every=1000, seed=0, step_lr=None, restore_best=True,
+            patience=None):
         """The reference's epoch loop (train_utils.py:345-468) with nothing read on the host inside.
 
         ``data`` is ``(s0, a0, sn, ts)`` or a callable ``epoch -> (s0, a0, sn, ts)`` (the reference regenerates the
@@ -610,13 +730,26 @@ class _FusedTrainer:
         the slice's summed training losses (the reference's ``cum_loss``, :440) -- then ``keep_best(criterion,
         tag=iterations so far)``.  A last slice without a full batch is skipped.  ``step_lr = (step_size, gamma)`` moves
         ``tr.lr`` after every epoch as ``torch.optim.lr_scheduler.StepLR.step()`` would.  At the end the best weights are
-        restored unless ``restore_best`` is False.  No patience: the reference's is ``inf``.
+        restored unless ``restore_best`` is False.
+
+        ``patience=None`` (the reference's is ``inf``) stops nobody.  With a number, every check runs the reference's
+        counter after ``keep_best`` (``nlc_train_patience``): a member whose criterion has not improved for more than
+        ``patience`` checks in a row is frozen from then on -- the loop runs to the end, the Adam update skips the member, and
+        its criterion no longer reaches ``keep_best`` (the reference's ``break``).  Its forward and backward still run, so
+        ``train_loss`` and ``criterion`` go on reporting it.  The waiting counts start from 0 at every call.
 
         Returns device tensors: ``train_loss`` (iters,) / (M, iters), ``criterion`` (checks,) / (M, checks), ``best_loss``
-        and ``best_iter`` (the iteration count at the best check)."""
+        and ``best_iter`` (the iteration count at the best check); with ``patience`` also ``active`` (bool) and ``stopped_at``
+        (the iteration count of the check that stopped the member, -1: none)."""
         bs, every = int(batch_size), int(eval_every)
         if bs < 1 or every < 1:
             raise ValueError(f"{self._name}.fit: batch_size and eval_every must be >= 1")
+        if patience is not None:
+            patience = float(patience)
+            if patience != patience or patience < 0:
+                raise ValueError(f"{self._name}.fit: patience must be None or a number >= 0 (inf: nobody stops)")
+            self._waiting.zero_()
+            self._frozen_any = True  # members may stop at any check from here on, and no host read will tell
         train_loss, criterion, done = [], [], 0
         for epoch in range(int(epochs)):
             s0, a0, sn, ts = data(epoch) if callable(data) else data
@@ -629,38 +762,52 @@ class _FusedTrainer:
                 losses = self.run(s0, a0, sn, ts, chunk, bs)
                 done += chunk.numel() // bs
                 crit = self.evaluate(*val) if val is not None else losses.sum(-1)
-                self.keep_best(crit, tag=done)
+                if patience is None:
+                    self.keep_best(crit, tag=done)
+                else:  # a stopped member is no longer checked: +inf never improves
+                    live = self._active != 0
+                    improved = self.keep_best(torch.where(live, crit.reshape(-1), torch.full_like(crit.reshape(-1), float("inf"))),
+                                              tag=done)
+                    self._patience(improved, patience, done)
                 train_loss.append(losses)
                 criterion.append(crit)
             if step_lr is not None:
-                self.lr = step_lr_after_epoch(self.lr, epoch + 1, *step_lr)
+                lr = self.lr
+                self.lr = ([step_lr_after_epoch(x, epoch + 1, *step_lr) for x in lr] if isinstance(lr, tuple)
+                           else step_lr_after_epoch(lr, epoch + 1, *step_lr))
         if not criterion:
             raise ValueError(f"{self._name}.fit: no epoch held a full batch")
         if restore_best:
             self.restore_best()
-        return {"train_loss": torch.cat(train_loss, dim=-1), "criterion": torch.stack(criterion, dim=-1),
-                "best_loss": self.best_loss.clone(), "best_iter": self.best_tag.clone()}
+        out = {"train_loss": torch.cat(train_loss, dim=-1), "criterion": torch.stack(criterion, dim=-1),
+               "best_loss": self.best_loss.clone(), "best_iter": self.best_tag.clone()}
+        if patience is not None:
+            out["active"], out["stopped_at"] = self._out(self._active != 0), self._out(self._stopped_at.clone())
+        return out
 
     # ------------------------------------------------------------------ optimiser state
     def _adam(self, i=0):
-        return torch.optim.Adam(self.models[i].parameters(), lr=self.lr, betas=self.betas, eps=self.eps,
-                                weight_decay=self.weight_decay)
+        return torch.optim.Adam(self.models[i].parameters(), lr=self._of("lr", i), betas=self.betas, eps=self.eps,
+                                weight_decay=self._of("weight_decay", i))
 
-    def _export_state(self, opt, i=0):
-        """The trainer's step count and member ``i``'s moments as ``opt.state`` (copies)."""
-        if self._step > 0:
+    def _export_state(self, opt, i=0, step=None):
+        """The trainer's step count (``step``: a frozen member's own) and member ``i``'s moments as ``opt.state`` (copies)."""
+        step = self._step if step is None else step
+        if step > 0:
             sdt = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32
             for p, m, v in zip(self._mparams[i], self._views(self._m, i), self._views(self._v, i)):
-                opt.state[p] = {"step": torch.tensor(float(self._step), dtype=sdt), "exp_avg": m.clone(),
+                opt.state[p] = {"step": torch.tensor(float(step), dtype=sdt), "exp_avg": m.clone(),
                                 "exp_avg_sq": v.clone()}
 
     def _state_dicts(self):
         if not self.fused:
             return [opt.state_dict() for opt in self._fallback]
+        # a frozen member's step is the count it stopped at (one device read, only once a member has been frozen)
+        at = self._frozen_step.tolist() if self._frozen_any else [-1] * self._M
         out = []
         for i in range(self._M):
             opt = self._adam(i)
-            self._export_state(opt, i)
+            self._export_state(opt, i, at[i] if at[i] >= 0 else None)
             out.append(opt.state_dict())
         return out
 
@@ -684,24 +831,38 @@ class _FusedTrainer:
                         raise ValueError(f"{self._name}.load_state_dict: an Adam state with {flag}=True is not supported "
                                          "(the trainer runs plain Adam)")
         opts = [self._adam(i) for i in range(self._M)]
-        hypers, steps = set(), set()
+        # a group that already has per-member settings takes states whose lr or weight decay differ between members, and a
+        # frozen member's own step count; a group of uniform settings keeps one of each, as it always has
+        per_member, frozen = self._per_member(), self._frozen_host()
+        hypers, shared, steps, own = [], set(), set(), []
         for i, (opt, sd) in enumerate(zip(opts, sds)):
             opt.load_state_dict(sd)
             grp = opt.param_groups[0]
-            hypers.add((float(grp["lr"]), tuple(float(b) for b in grp["betas"]), float(grp["eps"]), float(grp["weight_decay"])))
-            mine = {int(opt.state[p]["step"]) for p in self._mparams[i] if p in opt.state}
-            steps |= mine if mine else {0}
+            hypers.append((float(grp["lr"]), float(grp["weight_decay"])))
+            shared.add((tuple(float(b) for b in grp["betas"]), float(grp["eps"])))
+            mine = {int(opt.state[p]["step"]) for p in self._mparams[i] if p in opt.state} or {0}
+            own.append(mine)
+            if len(mine) > 1 or not frozen[i]:
+                steps |= mine
         if len(steps) > 1:
             raise ValueError(f"{self._name} keeps one Adam step count for all parameters" +
-                             (" of all members" if self._grouped else ""))
-        if len(hypers) > 1:
+                             (" of all members" if self._grouped else "") + (" that are not frozen" if any(frozen) else ""))
+        if len(shared) > 1 or (len(set(hypers)) > 1 and not per_member):
             raise ValueError(f"{self._name}.load_state_dict: the members' Adam hyper-parameters differ (one lr, betas, eps "
-                             "and weight_decay for the group)")
-        (self.lr, self.betas, self.eps, self.weight_decay), = hypers
+                             "and weight_decay for the group" +
+                             ("; a group with per-member settings takes its own lr and weight_decay per member)"
+                              if self._grouped else ")"))
+        (self.betas, self.eps), = shared
+        for k, name in enumerate(("lr", "weight_decay")):
+            vals = [h[k] for h in hypers]
+            setattr(self, name, vals[0] if len(set(vals)) == 1 and not isinstance(self._hyper[name], tuple) else vals)
         if not self.fused:
             self._fallback = opts
             return
-        self._step = steps.pop()
+        if steps:
+            self._step = steps.pop()
+        if any(frozen):
+            self._frozen_step.copy_(torch.tensor([next(iter(s)) if f else -1 for s, f in zip(own, frozen)], dtype=torch.int64))
         with torch.no_grad():
             for i, opt in enumerate(opts):
                 for p, m, v in zip(self._mparams[i], self._views(self._m, i), self._views(self._v, i)):
@@ -719,13 +880,32 @@ class _Group:
     def __init__(self, models, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
         self._init(models, lr, betas, eps, weight_decay, clip_grad_norm)
 
+    @property
+    def active(self):
+        """Which members the Adam update still moves: a bool device tensor ``(M,)`` (all True until ``freeze`` or ``fit``'s
+        patience stopped one)."""
+        return self._active != 0
+
+    def freeze(self, mask):
+        """Stop updating the members ``mask`` marks (``(M,)`` bools, on the host or the device; no host read).  A frozen
+        member's parameters and Adam moments are not written again; its forward and backward still run, so its losses are
+        still reported.  From the first call on the group steps through the library's ``_members`` entries."""
+        self._freeze(mask)
+
+    def unfreeze(self, mask):
+        """Let the members ``mask`` marks step again, with the group's step count; their patience counters start over."""
+        self._unfreeze(mask)
+
     def state_dict(self):
-        """A list of M ``torch.optim.Adam`` state dicts, one per member."""
+        """A list of M ``torch.optim.Adam`` state dicts, one per member, each with the member's own ``lr`` and
+        ``weight_decay``; a frozen member's ``step`` is the count it stopped at (read from the device)."""
         return self._state_dicts()
 
     def load_state_dict(self, sds):
-        """A list of M ``torch.optim.Adam`` states; ValueError when their step counts or hyper-parameters differ (the group
-        keeps one of each) or one has ``amsgrad`` / ``maximize``."""
+        """A list of M ``torch.optim.Adam`` states; ValueError when the betas, eps or the step counts of the members that are
+        not frozen differ (the group keeps one of each) or one has ``amsgrad`` / ``maximize``.  A group that has per-member
+        settings takes each state's own ``lr`` and ``weight_decay``; a group of uniform settings refuses states whose ``lr``
+        or ``weight_decay`` differ, as it always has."""
         self._load_state_dicts(list(sds))
 
 
@@ -829,10 +1009,17 @@ class NLTrainerGroup(_Group, NLTrainer):
     * ``grp.run(s0, a0, sn, ts, permutations, batch_size=16)`` -- ``(M, iters)`` losses; ``permutations`` (M, L), or (L,) to
       share; the datasets shared or stacked by the same rule;
     * ``grp.state_dict()`` / ``grp.load_state_dict(list)`` -- a list of M ``torch.optim.Adam`` states;
-    * ``grp.lr``, ``grp.fused``, ``grp.models``.
+    * ``grp.lr``, ``grp.weight_decay``, ``grp.clip_grad_norm`` -- a number, or a sequence of M numbers (a sweep: member m
+      trains with its own, bit-identical to a single trainer built with them); they return what was set, and assigning
+      either form takes effect at the next call.  A wrong length, or a negative ``lr`` / ``weight_decay``: ValueError;
+    * ``grp.active``, ``grp.freeze(mask)``, ``grp.unfreeze(mask)`` -- members the Adam update skips; ``fit(...,
+      patience=k)`` freezes each member when it stops improving;
+    * ``grp.fused``, ``grp.models``.
 
     The members must agree on all the descriptor holds (class, shapes, buffers by value, settings), at construction and at
-    every call: ValueError names the first member and field that differ.  One lr, betas, eps, weight decay and step count."""
+    every call: ValueError names the first member and field that differ.  One betas, eps and step count.  With numbers for
+    all three settings and no frozen member the group calls ``nlc_train_group_step`` as it always has; otherwise
+    ``nlc_train_group_step_members``, which reads the settings and the flags from device arrays."""
 
 
 class RNNTrainerGroup(_Group, RNNTrainer):

@@ -47,6 +47,14 @@ improving at every call and with none.  One child process per (family, M) under 
 profiles/train_select_bench.json unless --out says otherwise.
 
     python tools/train_bench.py --fit [--group 1 8 64] [--repeats 3] [--fit-iters 2000] [--eval-every 100]
+
+`--members` times per-member settings: run() at the first --batches size (16) over --run-iters iterations of a group of
+--group members (default 64) built with a learning rate per member (the library's ``_members`` step) against the same group
+with one learning rate (the step it has always called), both families (--model node: that family), the two variants taking
+turns in one child process per family: a warm-up run of --warmup iterations each, then --repeats timed runs each (median and
+min .. max, iterations / s).  Writes profiles/train_members_bench.json unless --out says otherwise.
+
+    python tools/train_bench.py --members [--group 64] [--repeats 3] [--run-iters 10000]
 """
 
 import argparse
@@ -203,6 +211,33 @@ def time_group(bs, iters, warm, M, repeats):
         torch.cuda.synchronize()
         out.append(iters / (time.perf_counter() - t0))
         assert bool(torch.isfinite(losses).all())
+    return out
+
+
+def time_members(bs, iters, warm, M, repeats):
+    """run() of two groups of the same M models over one shared dataset, a permutation per member: one with a learning rate
+    per member (all equal to the other's, so the two do the same arithmetic), one with a number.  Iterations / s of `repeats`
+    timed runs each, taken in turns, after a warm-up run of `warm` iterations each."""
+    import copy
+
+    s0, a0, sn, ts = dataset(bs * iters)
+    perms = torch.stack([torch.randperm(s0.shape[0], generator=torch.Generator().manual_seed(i)) for i in range(M)]).cuda()
+    models = [make_model(seed=i) for i in range(M)]
+    Group = getattr(nlc, TRAINERS[MODEL][1])
+    groups = {"scalar": Group([copy.deepcopy(m) for m in models], lr=1e-4), "members": Group(models, lr=[1e-4] * M)}
+    assert groups["members"]._per_member() and not groups["scalar"]._per_member()
+    out = {k: [] for k in groups}
+    for tr in groups.values():
+        assert tr.fused
+        tr.run(s0, a0, sn, ts, perms[..., : bs * warm], batch_size=bs)
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        for k, tr in groups.items():
+            t0 = time.perf_counter()
+            losses = tr.run(s0, a0, sn, ts, perms, batch_size=bs)
+            torch.cuda.synchronize()
+            out[k].append(iters / (time.perf_counter() - t0))
+            assert bool(torch.isfinite(losses).all())
     return out
 
 
@@ -368,6 +403,7 @@ def main():
     ap.add_argument("--fit", action="store_true", help="time fit() against the host loop it replaces, and nlc_train_keep_best")
     ap.add_argument("--fit-iters", type=int, default=2000, help="--fit: iterations per timed run (one epoch)")
     ap.add_argument("--eval-every", type=int, default=100, help="--fit: iterations between checks")
+    ap.add_argument("--members", action="store_true", help="time a group with per-member learning rates against the scalar group")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     MODEL, ILT, S = args.model, args.ilt_algorithm, args.terms
@@ -381,6 +417,9 @@ def main():
             return
         if variant.startswith("fit"):
             print("RESULT " + json.dumps(time_fit(int(variant[3:]), args.fit_iters, args.eval_every, args.repeats)))
+            return
+        if variant.startswith("members"):
+            print("RESULT " + json.dumps(time_members(bs, args.run_iters, args.warmup, int(variant[7:]), args.repeats)))
             return
         if variant.startswith("group"):
             print("RESULT " + json.dumps(time_group(bs, args.run_iters, args.warmup, int(variant[5:]), args.repeats)))
@@ -439,6 +478,24 @@ def main():
                 print(f"# {fam} M={M}: {r}", file=sys.stderr, flush=True)
         print(json.dumps(res))
         with open(args.out or os.path.join(REPO, "profiles", "train_select_bench.json"), "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
+    if args.members:
+        bs = args.batches[0]
+        res = {"device": torch.cuda.get_device_name(0), "batch": bs, "run_iters": args.run_iters, "repeats": args.repeats,
+               "families": {}}
+        for MODEL in (["node"] if args.model == "node" else ["delta_t_rnn", "nl"]):
+            fam = {"workload": WORKLOADS[MODEL], "groups": {}}
+            for M in args.group or [64]:
+                r = measure(bs, f"members{M}")
+                r = {"scalar": spread(r["scalar"]), "members": spread(r["members"])}
+                r["members_over_scalar"] = r["members"]["it_s"] / r["scalar"]["it_s"]
+                fam["groups"][str(M)] = r
+                print(f"# {MODEL} M={M}: {r}", file=sys.stderr, flush=True)
+            res["families"][MODEL] = fam
+        print(json.dumps(res))
+        with open(args.out or os.path.join(REPO, "profiles", "train_members_bench.json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
         return
