@@ -175,6 +175,14 @@ int nlc_synchronize(nlc_ctx* ctx);
  *   "linear_fused"       NLC_ILT_FIXED_TALBOT / NLC_ILT_STEHFEST models: 1 (default) = the rollout runs on LIN instances of the
  *                        rollout kernels (two epilogue MFMAs per slot group, coefficient fragments folded for the constant
  *                        prediction time at nlc_mppi_configure); 0 = the staged path de Hoog models take
+ *   "train_dehoog"       training and evaluation entries of the NL family (nlc_train_*): 0 (default) = an NLC_ILT_DEHOOG model is
+ *                        refused with NLC_ERR_UNSUPPORTED, as ever; 1 = it is accepted at odd ilt terms 3 .. 33 and any ILT
+ *                        scale, and a call runs the forward half of the step, the de Hoog ILT, the loss, the ILT's backward
+ *                        and the backward half as five launches before the reduction and Adam (csrc/nlc_train_dehoog.h).
+ *                        One 16-row tile per workgroup: N <= 2048 rows per member and call, a larger N is
+ *                        NLC_ERR_UNSUPPORTED; an even term count likewise.  The workspace sizes the *_workspace_bytes entries
+ *                        return (nlc_train_group_eval_workspace_bytes included) are then the de Hoog layout's.  Other
+ *                        algorithms are not affected
  *   "fused_keep_sync"    tools only: the merge kernel does not zero the fused body's sync block (tools/fused_debug.py reads
  *                        the launch's progress counters / timeline from it); the next command pays a memset instead
  *   "test_lin_coeff_scale"  tests only: the largest coefficient of the LIN rollout instances' folded w_re / t fragment is

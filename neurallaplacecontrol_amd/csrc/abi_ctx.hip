@@ -164,6 +164,9 @@ extern "C" int nlc_set_option(nlc_ctx* c, const char* name, double value) {
     c->opt.fused_spin_limit = (int64_t)value;
   } else if (n == "linear_fused") {
     c->opt.linear_fused = value != 0.0;
+  } else if (n == "train_dehoog") {
+    if (value != 0 && value != 1) return fail(c, NLC_ERR_BAD_ARG, "train_dehoog must be 0 or 1");
+    c->opt.train_dehoog = (int)value;
   } else if (n == "test_lin_coeff_scale") {
     c->opt.test_lin_coeff_scale = value;
     c->has_mppi = false;  // folded at nlc_mppi_configure

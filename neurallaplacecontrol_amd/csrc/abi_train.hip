@@ -9,6 +9,7 @@
 
 #include "nlc_host.h"
 #include "nlc_train.h"
+#include "nlc_train_dehoog.h"
 #include "nlc_train_eval.h"
 #include "nlc_train_members.h"
 #include "nlc_train_node.h"
@@ -31,6 +32,8 @@ struct Plan {
   GroupStrides gs;  // for a group whose gradient lives in the workspace (a step); loss_grad overrides gs.grad
   int M;
   int row_times;  // NODE: every row integrates to its own time (0: to the batch's first row's, as the reference)
+  bool dehoog;        // NL, option "train_dehoog": the de Hoog launch sequence (nlc_train_dehoog.h); dh is its workspace
+  DehoogWsLayout dh;  // (set by plan_group: the ILT arrays hold the M members back to back)
 };
 
 // workgroups, partial size and the reduce / Adam chunking of a call with N rows, once p.off, p.A and p.d are set
@@ -46,7 +49,11 @@ void plan_rows(Plan& p, int64_t N) {
 void plan_group(Plan& p, int M, int64_t N, int64_t data_rows) {
   p.M = M;
   p.gs = GroupStrides{p.P, p.ws.total, p.ws.total, N, data_rows};
+  if (p.dehoog) p.dh = dehoog_ws_layout(M, N, p.d, p.S, p.ws.total);
 }
+
+// whether the ctx's NL model trains through the de Hoog launch sequence: a de Hoog model and option "train_dehoog" = 1
+bool nl_dehoog(const nlc_ctx* c) { return c->nl.has && c->nl.md.ilt.algo == NLC_ILT_DEHOOG && c->opt.train_dehoog != 0; }
 
 // (slabs sized for the longest window)
 Plan plan_of(const nlc_ctx* c, int64_t N) {
@@ -57,6 +64,7 @@ Plan plan_of(const nlc_ctx* c, int64_t N) {
   p.d = md.d;
   blob_offsets(md.d, md.nin, p.g, md.h, p.S, p.off);
   p.A = act_layout(md.d, md.nin, p.g, md.h, p.S, kMaxB).total;
+  p.dehoog = nl_dehoog(c);
   plan_rows(p, N);
   return p;
 }
@@ -93,18 +101,23 @@ bool family_has(const nlc_ctx* c, Family fam) {
 // member 0's arrays in the workspace (nlc_train.h TrainWsLayout; member m's are gs.ws doubles further on)
 struct WsPtrs {
   double *partial, *tile_loss, *act, *grad, *sq;
+  double* base;  // the workspace's first double (a de Hoog call's ILT arrays are offsets of Plan::dh from it)
 };
 WsPtrs ws_ptrs(const Plan& p, void* base) {
   double* b = (double*)base;
-  return WsPtrs{b + p.ws.partial, b + p.ws.tile_loss, b + p.ws.act, b + p.ws.grad, b + p.ws.sq};
+  return WsPtrs{b + p.ws.partial, b + p.ws.tile_loss, b + p.ws.act, b + p.ws.grad, b + p.ws.sq, b};
 }
 
 // the NL model the kernels take: uploaded, and with one of the three ILT algorithms they are written for (fixed Talbot /
-// Stehfest: fixed nodes and weights from linear_tables, the <true> instance of train_fwd_bwd_kernel)
+// Stehfest: fixed nodes and weights from linear_tables, the <true> instance of train_fwd_bwd_kernel); with option
+// "train_dehoog" also de Hoog at the term counts its ILT kernels take, at any ILT scale (kernels_train_dehoog.hip)
 int check_nl_model(nlc_ctx* c) {
   if (!c->nl.has) return fail(c, NLC_ERR_STATE, "nlc_set_model has not been called");
   const nlc_ilt_desc& ilt = c->nl.md.ilt;
-  if (is_linear_ilt(ilt)) {
+  if (nl_dehoog(c)) {
+    if (ilt.terms < 3 || ilt.terms > 33 || ilt.terms % 2 == 0)
+      return fail(c, NLC_ERR_UNSUPPORTED, "fused training step (dehoog): ilt_reconstruction_terms must be odd, 3 .. 33");
+  } else if (is_linear_ilt(ilt)) {
     // what linear_tables cannot build: an odd or too long Stehfest series, terms past the tables
     if (check_ilt(c, &ilt) != NLC_OK)
       return fail(c, NLC_ERR_UNSUPPORTED,
@@ -126,6 +139,9 @@ int check_call(nlc_ctx* c, Family fam, int M, int64_t data_rows, int64_t N, int 
   // (a NODE reads the window's newest action only, but keeps the families' one contract)
   if (B < 1 || B > kMaxB) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: window length must be in 1..16");
   if (N < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: N must be >= 1");
+  // (de Hoog: one tile per workgroup, its slab lives across the ILT launches)
+  if (fam == kFamNl && nl_dehoog(c) && N > kDehoogMaxRows)
+    return fail(c, NLC_ERR_UNSUPPORTED, "fused training step (dehoog): at most 2048 rows in a call");
   if (M < 1) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: a group needs M >= 1 members");
   if (M > kMaxGroup) return fail(c, NLC_ERR_UNSUPPORTED, "fused training step: at most 65535 members in a group");
   if (data_rows < 0) return fail(c, NLC_ERR_BAD_SHAPE, "fused training step: data_row_stride must be >= 0");
@@ -269,7 +285,10 @@ void fill_train_ws(Args& a, const Plan& p, const WsPtrs& w) {
   a.act = w.act;
 }
 
+int nl_dehoog_launches(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w, bool backward);
+
 int nl_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w) {
+  if (p.dehoog) return nl_dehoog_launches(c, b, B, p, w, true);
   TrainArgs a{};
   fill_call(a, c->nl.md, B, b, p);
   if (int rc = fill_nl(c, a, p)) return rc;
@@ -277,6 +296,51 @@ int nl_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w
   a.L = act_layout(p.d, c->nl.md.nin, p.g, c->nl.md.h, p.S, B);
   ProfScope ps(c, "train_fwd_bwd_kernel");
   NLC_HIP(c, launch_train_fwd_bwd(a, p.nblk, p.M, c->stream));
+  return NLC_OK;
+}
+
+// the de Hoog step's launches 1 .. 3 (forward half, ILT, loss; what evaluation needs) and, with backward, 4 and 5.  The group is
+// one batch of M * rows points for the two ILT launches
+int nl_dehoog_launches(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs& w, bool backward) {
+  const nlc_model_desc& md = c->nl.md;
+  const DehoogWsLayout& dh = p.dh;
+  const int64_t R = (int64_t)p.M * dh.rows;
+  DehoogTrainArgs a{};
+  fill_call(a.t, md, B, b, p);
+  if (int rc = fill_nl(c, a.t, p)) return rc;
+  fill_train_ws(a.t, p, w);
+  a.t.L = act_layout(p.d, md.nin, p.g, md.h, p.S, B);
+  a.scale = md.ilt.scale;
+  a.rows = dh.rows;
+  a.theta = w.base + dh.theta;
+  a.phi = w.base + dh.phi;
+  a.tq = w.base + dh.t;
+  a.gtheta = w.base + dh.gtheta;
+  a.gphi = w.base + dh.gphi;
+  {
+    ProfScope ps(c, "train_dehoog_fwd_kernel");
+    NLC_HIP(c, launch_train_dehoog_fwd(a, p.nblk, p.M, c->stream));
+  }
+  {
+    // (the times are normalised already: t_div stays 1)
+    const IltArgs ia = ilt_args(md.ilt, a.theta, a.phi, a.tq, w.base + dh.pred, R, p.d);
+    ProfScope ps(c, "ilt_dehoog_kernel");
+    NLC_HIP(c, launch_ilt_dehoog(ia, c->stream));
+  }
+  {
+    const DehoogLossArgs la{w.base + dh.pred, w.act, w.base + dh.gx, w.tile_loss, dh.rows, b.N, p.A, a.t.L.tgt, p.gs.ws, p.d};
+    ProfScope ps(c, "train_dehoog_loss_kernel");
+    NLC_HIP(c, launch_train_dehoog_loss(la, p.nblk, p.M, c->stream));
+  }
+  if (!backward) return NLC_OK;
+  {
+    const IltDehoogBwdArgs ba = ilt_dehoog_bwd_args(md.ilt, a.theta, a.phi, a.tq, w.base + dh.gx, w.base + dh.gtheta,
+                                                    w.base + dh.gphi, R, p.d, w.base + dh.scratch);
+    ProfScope ps(c, "ilt_dehoog_bwd_kernel");
+    NLC_HIP(c, launch_ilt_dehoog_bwd(ba, c->stream));
+  }
+  ProfScope ps(c, "train_dehoog_bwd_kernel");
+  NLC_HIP(c, launch_train_dehoog_bwd(a, p.nblk, p.M, c->stream));
   return NLC_OK;
 }
 
@@ -359,8 +423,10 @@ int node_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_los
 // ---- the three entries of a family, written once for all of them and for any M
 int64_t group_workspace_bytes(nlc_ctx* c, Family fam, int M, int64_t N) {
   if (!c || !family_has(c, fam) || N < 1 || M < 1 || M > kMaxGroup) return -1;
-  const Plan p = family_plan(c, fam, N);
-  return (int64_t)M * p.ws.total * (int64_t)sizeof(double);
+  Plan p = family_plan(c, fam, N);
+  if (!p.dehoog) return (int64_t)M * p.ws.total * (int64_t)sizeof(double);
+  plan_group(p, M, N, 0);
+  return p.dh.total * (int64_t)sizeof(double);
 }
 
 // checks (all on the host, before any launch, in the single entries' order: model state and shape, the group, the step count,
@@ -420,6 +486,8 @@ int group_step_entry(nlc_ctx* c, Family fam, const nlc_train_desc* desc, int M, 
 // (nlc_train_eval.h eval_ws_layout), M regions back to back
 int64_t group_eval_workspace_bytes(nlc_ctx* c, Family fam, int M, int64_t N) {
   if (!c || !family_has(c, fam) || N < 1 || M < 1 || M > kMaxGroup) return -1;
+  // (de Hoog evaluates through the training step's forward half: its slabs and ILT arrays)
+  if (fam == kFamNl && nl_dehoog(c)) return group_workspace_bytes(c, fam, M, N);
   return (int64_t)M * eval_ws_layout(N).total * (int64_t)sizeof(double);
 }
 
@@ -433,6 +501,19 @@ int group_eval_entry(nlc_ctx* c, Family fam, int M, int64_t data_rows, const dou
   if (!params || !obs || !window || (!ts && need_ts) || !target || !loss || !ws)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
+  if (fam == kFamNl && nl_dehoog(c)) {
+    // launches 1 .. 3 of the training step on its own workspace layout (the forward tapes needlessly here), then the
+    // evaluation's reduction over the member's tile losses
+    Plan p = family_plan(c, fam, N);
+    plan_group(p, M, N, data_rows);
+    const WsPtrs w = ws_ptrs(p, ws);
+    const Batch b{params, obs, window, ts, target, idx, N};
+    if (int rc = nl_dehoog_launches(c, b, B, p, w, false)) return rc;
+    EvalReduceArgs r{w.tile_loss, p.nblk, N, p.ws.total, p.d, loss};
+    ProfScope ps(c, "eval_reduce_kernel");
+    NLC_HIP(c, launch_eval_reduce(r, M, c->stream));
+    return NLC_OK;
+  }
   const EvalWsLayout w = eval_ws_layout(N);
   Plan p = family_plan(c, fam, N);
   p.M = M;

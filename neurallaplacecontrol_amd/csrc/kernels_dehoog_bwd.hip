@@ -31,6 +31,7 @@
 // Adjoint convention: for a real loss L and a complex intermediate w, wbar = dL/dRe(w) + i dL/dIm(w); then for
 // holomorphic w = f(u): ubar += wbar conj(f'(u)).
 #include "nlc_cplx.h"
+#include "nlc_dehoog_tape.h"
 #include "nlc_device.h"
 #include "nlc_kernels.h"
 
@@ -53,27 +54,8 @@ namespace {
 // MI355X at 3.3 M rows, M = 16: 8 -> 23.5 ms with 197 spilled VGPRs, 4 -> 21.5 ms with 93, no prefetch 25.6 ms)
 constexpr int kDhbGroup = 4;
 
-struct DhLayout {
-  int M;
-  // Round 5: the terms a_k and the odd e columns are not taped, and the slab is laid out without them: q columns | even e columns |
-  // first entry of every odd e column | A | B -- 466 entries per row at M = 16 instead of 627 (0.49 GB of scratch for 1024 resident
-  // wavefronts instead of 0.66).
-  // value tape
-  __host__ __device__ constexpr int q(int r, int i) const { return (r - 1) * (2 * M + 2 - r) + i; }                 // r = 1..M, i = 0..2(M-r)+1
-  __host__ __device__ constexpr int even_before(int n) const { return n * (2 * M + 1) - 2 * n * (n + 1); }            // entries of the even columns 2 .. 2n
-  __host__ __device__ constexpr int e(int r, int i) const {                                                          // r = 1..M, i = 0..2(M-r)
-    if ((r & 1) == 0) return M * (M + 1) + even_before((r - 2) / 2) + i;
-    return M * (M + 1) + even_before(M / 2) + (r - 1) / 2;  // odd column: only i == 0 is taped
-  }
-  __host__ __device__ constexpr int e_end() const { return M * (M + 1) + even_before(M / 2) + (M + 1) / 2; }
-  __host__ __device__ constexpr int A(int i) const { return e_end() + (i + 1); }                                     // i = -1..2M-1
-  __host__ __device__ constexpr int B(int i) const { return e_end() + (2 * M + 1) + (i + 1); }                       // i = -1..2M-1
-  __host__ __device__ constexpr int entries() const { return e_end() + 2 * (2 * M + 1); }
-};
-static_assert(DhLayout{16}.entries() == 466, "compact tape layout at M = 16");
-static_assert(DhLayout{16}.e(4, 0) - DhLayout{16}.e(2, 0) == 2 * 14 + 1 && DhLayout{16}.e(16, 0) + 1 == DhLayout{16}.e(1, 0) &&
-                  DhLayout{5}.e(5, 0) + 1 == DhLayout{5}.A(-1) && DhLayout{1}.entries() == 2 + 0 + 1 + 6,
-              "compact tape layout: columns are contiguous and disjoint");
+// (the tape's layout, DhLayout, and the launch's slab count are nlc_dehoog_tape.h's: the training workspace of de Hoog models
+// sizes this scratch too)
 
 // Tape accesses go through a wave-uniform (SGPR) slab pointer that is laundered at every access: the entry offsets are
 // compile-time constants of the unrolled sweeps, and left alone the compiler hoists ~1300 per-lane 64-bit addresses out of the
@@ -81,7 +63,6 @@ static_assert(DhLayout{16}.e(4, 0) - DhLayout{16}.e(2, 0) == 2 * 14 + 1 && DhLay
 // `global_load / store_dwordx4 v, v_lane_offset, s[base + const]`.
 // (a slab entry is (re, im) = 16 bytes per lane; the two scalar accesses below merge into one dwordx4)
 typedef __attribute__((address_space(1))) double* tape_ptr;
-constexpr int64_t kTapeElemBytes = 16;
 struct Tape {
   tape_ptr base;  // this wavefront's slab, [entry][lane][2]; wave-uniform
   int lane;
@@ -437,14 +418,9 @@ __global__ __launch_bounds__(64, M <= 8 ? 2 : 1) void ilt_dehoog_bwd_kernel(cons
 // two up to M = 8.  Every resident workgroup (= wavefront) holds a slab: at most 4 / 8 per CU, i.e. 1024 x 642 KB = 0.66 GB at 33
 // terms (round 3 took 2.5 GB from the stream-ordered pool: ADVICE r3).
 int64_t ilt_dehoog_bwd_scratch_bytes(int64_t N, int d, int S, unsigned* grid_out) {
-  const int64_t nblk = (N * d + 63) / 64;
-  // (slabs in flight, measured at 3.3 M rows, S = 33: 256 -> 36.3 ms, 512 -> 29.8, 768 -> 22.7, 1024 -> 19.8, 2048 (1024
-  // resident) -> 20.9: fewer slabs would fit the Infinity Cache but starve the latency hiding)
-  const int64_t cap = (S - 1) / 2 <= 8 ? 2048 : 1024;
-  const unsigned grid = (unsigned)(nblk < cap ? nblk : cap);
-  if (grid_out) *grid_out = grid;
-  const DhLayout L{(S - 1) / 2};
-  return (int64_t)grid * L.entries() * 64 * kTapeElemBytes;
+  // (the slab count and its measurements: nlc_dehoog_tape.h)
+  if (grid_out) *grid_out = dehoog_bwd_grid(N * d, S);
+  return dehoog_bwd_tape_bytes(N * d, S);
 }
 
 hipError_t launch_ilt_dehoog_bwd(const IltDehoogBwdArgs& a, hipStream_t s) {

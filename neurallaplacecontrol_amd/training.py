@@ -8,7 +8,8 @@
 a fixed-order reduction of the tile gradients, clip + Adam.  No host synchronisation inside, so ``run()`` walks a whole
 permutation with the weights, Adam moments and per-iteration losses on the device.
 
-Models the kernels do not take (de Hoog, widths other than 64 / 128 / 256, ...) train through
+Models the kernels do not take (de Hoog unless the trainer was built with ``dehoog="fused"``, widths other than 64 / 128 /
+256, ...) train through
 the reference's op sequence -- the model's grad-mode forward + ``clip_grad_norm_`` + ``torch.optim.Adam`` -- from
 construction on, with one warning.  A fused trainer sends a single call the library refuses (a window longer than 16, a
 model setting changed to one the kernels do not take) through the same op sequence, on the trainer's own Adam state, also
@@ -96,6 +97,9 @@ class _FusedTrainer:
         """What the family's entries take after the workspace pointer (NODE: ``row_times``)."""
         return ()
 
+    def _setup_ctx(self):
+        """Options of the trainer's fresh ctx (``NLTrainer(dehoog="fused")`` sets one)."""
+
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1):
         self._init([model], lr, betas, eps, weight_decay, clip_grad_norm)
 
@@ -132,6 +136,7 @@ class _FusedTrainer:
         why = self._unsupported(model)
         if why is None:
             self._ctx = _lib.Ctx(self._dev.index)
+            self._setup_ctx()
             self._model_key = None
             why = self._sync_model()
         if why is not None:
@@ -282,7 +287,11 @@ class _FusedTrainer:
                 raise
             why = str(err)
         self._model_key = (key, why)
+        self._descriptor_changed()
         return why
+
+    def _descriptor_changed(self):
+        """After a re-upload of the model descriptor (``NLTrainer(dehoog="fused")`` drops its workspace cache here)."""
 
     def _host_path(self, why):
         """A call the fused kernels do not take: warn once per trainer."""
@@ -913,13 +922,41 @@ class NLTrainer(_FusedTrainer):
     """``tr = NLTrainer(model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1)`` for a
     ``NeuralLaplaceModel``; the fused step takes Fourier, fixed Talbot and Stehfest models (``nlc_train_group_step``,
     M = 1).  ``model.ilt_algorithm`` may change on a live trainer: among those three the next call runs the other kernel
-    instance; set to ``"dehoog"`` the calls take the per-call grad-mode path on the trainer's Adam state."""
+    instance; set to ``"dehoog"`` the calls take the per-call grad-mode path on the trainer's Adam state.
+
+    ``dehoog="grad"`` (the default) is that behaviour: a de Hoog model trains through its grad-mode forward, with one
+    warning.  ``dehoog="fused"`` sets the ctx option ``train_dehoog``: a de Hoog model (odd ``s_recon_terms`` 3 .. 33) then
+    takes the fused step as the other algorithms do -- the step's forward half, the de Hoog ILT kernels, the loss, their
+    backward and the step's backward half (``csrc/nlc_train_dehoog.h``) -- at up to 2048 rows per call; a larger call runs the
+    per-call grad-mode path.  Switching ``model.ilt_algorithm`` to or from ``"dehoog"`` on such a trainer takes effect at the
+    next call, without a warning."""
 
     _entries = ("nlc_train_group_workspace_bytes", "nlc_train_group_loss_grad", "nlc_train_group_step")
     _eval_entries = ("nlc_train_group_eval_workspace_bytes", "nlc_train_group_eval")
+    _dehoog = "grad"
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1, dehoog="grad"):
+        self._dehoog = self._dehoog_mode(dehoog)
+        self._init([model], lr, betas, eps, weight_decay, clip_grad_norm)
+
+    def _dehoog_mode(self, dehoog):
+        if dehoog not in ("grad", "fused"):
+            raise ValueError(f"{type(self).__name__}: dehoog must be 'grad' or 'fused' (got {dehoog!r})")
+        return dehoog
+
+    def _setup_ctx(self):
+        if self._dehoog == "fused":
+            self._ctx.set_option("train_dehoog", 1)
+
+    def _descriptor_changed(self):
+        # with the option set a workspace's size depends on the descriptor's ILT algorithm, which may be switched on a live
+        # trainer: the cached workspaces (keyed by entry and N) are those of the previous descriptor
+        if self._dehoog == "fused":
+            self._ws = {}
 
     def _unsupported(self, model):
-        if model.ilt_algorithm not in ("fourier", "fixed_tablot", "stehfest"):
+        fused = ("fourier", "fixed_tablot", "stehfest") + (("dehoog",) if self._dehoog == "fused" else ())
+        if model.ilt_algorithm not in fused:
             return (f"ilt_algorithm {model.ilt_algorithm!r} has no fused training kernels (fourier, fixed_tablot and "
                     "stehfest have)")
         return None
@@ -1019,7 +1056,14 @@ class NLTrainerGroup(_Group, NLTrainer):
     The members must agree on all the descriptor holds (class, shapes, buffers by value, settings), at construction and at
     every call: ValueError names the first member and field that differ.  One betas, eps and step count.  With numbers for
     all three settings and no frozen member the group calls ``nlc_train_group_step`` as it always has; otherwise
-    ``nlc_train_group_step_members``, which reads the settings and the flags from device arrays."""
+    ``nlc_train_group_step_members``, which reads the settings and the flags from device arrays.
+
+    ``dehoog="fused"`` as for ``NLTrainer``: the M de Hoog members share every launch, the two ILT launches as one batch of
+    ``M x rows`` points."""
+
+    def __init__(self, models, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.1, dehoog="grad"):
+        self._dehoog = self._dehoog_mode(dehoog)
+        self._init(models, lr, betas, eps, weight_decay, clip_grad_norm)
 
 
 class RNNTrainerGroup(_Group, RNNTrainer):

@@ -55,6 +55,14 @@ turns in one child process per family: a warm-up run of --warmup iterations each
 min .. max, iterations / s).  Writes profiles/train_members_bench.json unless --out says otherwise.
 
     python tools/train_bench.py --members [--group 64] [--repeats 3] [--run-iters 10000]
+
+`--ilt-algorithm dehoog` times a de Hoog NL model (tamed weights, a narrow band of short times).  Only the grad-mode path
+(`--only ref`) can be timed without `--dehoog-fused`, which builds the trainers with ``dehoog="fused"``.  With `--group` the NL
+family alone is measured, every timed run in a child process of its own after that child's warm-up run: first (a) --repeats
+times, then run() of the single trainer and of each group size --repeats times; per M also member-iterations / s over (a).
+Writes profiles/train_bench_dehoog.json unless --out says otherwise.
+
+    python tools/train_bench.py --ilt-algorithm dehoog --terms 33 --dehoog-fused --batches 16 --group 1 8 64 [--run-iters 1000]
 """
 
 import argparse
@@ -78,6 +86,7 @@ RNN_H = 160  # rnn_hidden_units, config.py:43
 NODE_H, NODE_AUG = 270, 1  # node_hidden_units, node_augment_dim, config.py:41-42
 MODEL = "nl"
 ILT = "fourier"  # --ilt-algorithm (NL model)
+DEHOOG_FUSED = False  # --dehoog-fused: NL trainers are built with dehoog="fused"
 WORKLOADS = {"nl": "NeuralLaplaceModel training step, cartpole d=5 h=128 S=17 B=4, float64",
              "delta_t_rnn": "DeltaTRNN training step, cartpole d=5 H=160 B=4, float64",
              "node": "NODE training step, cartpole d=5 augment=1 H=270 (Euler, step 0.05, normalize_time), float64"}
@@ -85,8 +94,12 @@ TRAINERS = {"nl": ("NLTrainer", "NLTrainerGroup"), "delta_t_rnn": ("RNNTrainer",
             "node": ("NODETrainer", "NODETrainerGroup")}
 
 
+def trainer_kw():
+    return {"dehoog": "fused"} if MODEL == "nl" and DEHOOG_FUSED else {}
+
+
 def make_trainer(model):
-    tr = getattr(nlc, TRAINERS[MODEL][0])(model)
+    tr = getattr(nlc, TRAINERS[MODEL][0])(model, **trainer_kw())
     assert tr.fused, "the benchmark times the fused step"
     return tr
 
@@ -109,7 +122,9 @@ def make_model(seed=0):
                      action_std=np.array([1.0]), normalize=True, normalize_time=True, augment_dim=NODE_AUG).double()
         m.load_state_dict(sd)
         return m.to("cuda")
-    sd = onl.make_synthetic_state_dict(seed, D, NU, H, S, st["state_std"], [st["act_high"] / 2], tame=True)
+    # (de Hoog: weights whose terms sample a transform -- the table is ill-conditioned on a random network's)
+    sd = onl.make_synthetic_state_dict(seed, D, NU, H, S, st["state_std"], [st["act_high"] / 2],
+                                       tame="dehoog" if ILT == "dehoog" else True)
     m = nlc.NeuralLaplaceModel(D, NU, D, hidden_units=H, s_recon_terms=S, ilt_algorithm=ILT, state_mean=np.zeros(D),
                                state_std=np.ones(D), action_mean=np.array([0]), action_std=np.array([1.0]), normalize=True,
                                normalize_time=True).double()
@@ -125,6 +140,8 @@ def dataset(M, seed=0):
     a0 = (torch.rand(M, B, NU, dtype=torch.float64, generator=g) * 2 - 1) * st["act_high"]
     sn = s0 + torch.randn(M, D, dtype=torch.float64, generator=g) * 0.05 * std
     ts = torch.rand(M, 1, dtype=torch.float64, generator=g) * 0.08 + 0.02
+    if MODEL == "nl" and ILT == "dehoog":  # a narrow band of short times (5e-3 .. 7.5e-3 before the model's normalisation)
+        ts = (torch.rand(M, 1, dtype=torch.float64, generator=g) * 0.05 + 0.1) * 0.05
     return [t.cuda() for t in (s0, a0, sn, ts)]
 
 
@@ -200,7 +217,7 @@ def time_group(bs, iters, warm, M, repeats):
     if M == 0:
         tr, perms = make_trainer(models[0]), perms[0]
     else:
-        tr = getattr(nlc, TRAINERS[MODEL][1])(models)
+        tr = getattr(nlc, TRAINERS[MODEL][1])(models, **trainer_kw())
     assert tr.fused
     tr.run(s0, a0, sn, ts, perms[..., : bs * warm], batch_size=bs)
     torch.cuda.synchronize()
@@ -380,7 +397,7 @@ def flops_per_iter(bs):
 
 
 def main():
-    global MODEL, ILT, S
+    global MODEL, ILT, S, DEHOOG_FUSED
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 256])
     ap.add_argument("--ref-iters", type=int, default=200)
@@ -390,8 +407,12 @@ def main():
     ap.add_argument("--only", choices=["ref", "step", "run"], default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--model", choices=sorted(WORKLOADS), default="nl")
-    ap.add_argument("--ilt-algorithm", choices=["fourier", "fixed_tablot", "stehfest"], default="fourier",
-                    help="--model nl: the ILT algorithm of the model (the fused step has an instance for each of these)")
+    ap.add_argument("--ilt-algorithm", choices=["fourier", "fixed_tablot", "stehfest", "dehoog"], default="fourier",
+                    help="--model nl: the ILT algorithm of the model (the fused step has an instance for each of the first three; "
+                         "dehoog: with --dehoog-fused)")
+    ap.add_argument("--dehoog-fused", action="store_true",
+                    help="--ilt-algorithm dehoog: trainers are built with dehoog='fused' (singles and --group); without it only "
+                         "the grad-mode path (--only ref) can be timed")
     ap.add_argument("--terms", type=int, default=S, help="--model nl: ilt_reconstruction_terms (stehfest: even, 2 .. 20)")
     ap.add_argument("--kernel-ms", action="store_true")
     ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds each child measurement may take")
@@ -406,7 +427,7 @@ def main():
     ap.add_argument("--members", action="store_true", help="time a group with per-member learning rates against the scalar group")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    MODEL, ILT, S = args.model, args.ilt_algorithm, args.terms
+    MODEL, ILT, S, DEHOOG_FUSED = args.model, args.ilt_algorithm, args.terms, args.dehoog_fused
     if MODEL == "nl" and (ILT, S) != ("fourier", 17):
         WORKLOADS["nl"] = f"NeuralLaplaceModel training step, cartpole d=5 h=128 {ILT} S={S} B=4, float64"
     torch.manual_seed(0)
@@ -429,11 +450,11 @@ def main():
         print("RESULT " + json.dumps(fn()))
         return
 
-    def measure(bs, variant):
+    def measure(bs, variant, repeats=None):
         cmd = [sys.executable, os.path.abspath(__file__), "--model", MODEL, "--ilt-algorithm", ILT, "--terms", str(S),
                "--ref-iters", str(args.ref_iters), "--step-iters",
                str(args.step_iters), "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--repeats",
-               str(args.repeats), "--child", str(bs), variant]
+               str(repeats or args.repeats), *(["--dehoog-fused"] if DEHOOG_FUSED else []), "--child", str(bs), variant]
         out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
         return json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
 
@@ -504,10 +525,15 @@ def main():
         res = {"device": torch.cuda.get_device_name(0), "batch": bs, "run_iters": args.run_iters, "repeats": args.repeats,
                "families": {}}
         # --model node: that family alone, at its own batch size; else the two families the tool has always timed together
-        for MODEL in (["node"] if args.model == "node" else ["delta_t_rnn", "nl"]):
+        for MODEL in (["node"] if args.model == "node" else ["nl"] if ILT == "dehoog" else ["delta_t_rnn", "nl"]):
             fam = {"workload": WORKLOADS[MODEL], "groups": {}}
+            if ILT == "dehoog":  # the path the fused step replaces, in the same session: a child process per timed run
+                fam["grad_mode_ref"] = spread([measure(bs, "ref") for _ in range(args.repeats)])
+                print(f"# {MODEL} grad-mode: {fam['grad_mode_ref']}", file=sys.stderr, flush=True)
             for M in [0] + list(args.group):  # 0: the single trainer, in the same session
-                r = spread(measure(bs, f"group{M}"))
+                # (dehoog: every timed run in a child process of its own, after that child's warm-up run)
+                r = spread([measure(bs, f"group{M}", repeats=1)[0] for _ in range(args.repeats)] if ILT == "dehoog"
+                           else measure(bs, f"group{M}"))
                 if M == 0:
                     fam["single"] = r
                     if args.parent_tree:
@@ -516,6 +542,8 @@ def main():
                 else:
                     r["member_it_s"] = M * r["it_s"]
                     r["aggregate_over_single"] = r["member_it_s"] / fam["single"]["it_s"]
+                    if "grad_mode_ref" in fam:
+                        r["member_it_s_over_grad_mode"] = r["member_it_s"] / fam["grad_mode_ref"]["it_s"]
                     if args.parent_tree:
                         r["aggregate_over_parent"] = r["member_it_s"] / fam["parent_single"]["it_s"]
                         if M == 1:
@@ -525,7 +553,8 @@ def main():
             res["families"][MODEL] = fam
         line = json.dumps(res)
         print(line)
-        default = "train_bench_node_group.json" if args.model == "node" else "train_bench_group.json"
+        default = ("train_bench_node_group.json" if args.model == "node" else
+                   "train_bench_dehoog.json" if ILT == "dehoog" else "train_bench_group.json")
         with open(args.out or os.path.join(REPO, "profiles", default), "w") as f:
             f.write(line + "\n")
         return
