@@ -37,7 +37,7 @@ __device__ __forceinline__ cplx csqrt_(cplx z) {
   // principal branch
   const double mag = hypot(z.re, z.im);
   double re = sqrt(0.5 * (mag + fabs(z.re)));
-  double im = (re == 0.0) ? 0.0 : 0.5 * z.im / re;
+  double im = (re == 0.0) ? copysign(0.0, z.im) : 0.5 * z.im / re;  // (z = +-0 - 0i: -0, as the principal branch has it)
   if (z.re < 0.0) {
     const double t = re;
     re = fabs(im);

@@ -5,7 +5,8 @@
 // blow the unroll budget of the fused kernels, so the kernels use these instead: every argument here has
 // a known bounded range (tanh outputs scaled by pi, gate pre-activations, ...).  Accuracy target is a few
 // ulp; tests/test_math_host.py checks them against libm on dense grids (this header also compiles as
-// plain C++ for that purpose).
+// plain C++ for that purpose), and tests/test_gpu_math_device.py runs the same grids and bounds on the device
+// build (tools/math_dev_check.hip), where rcp_refined, div_fast and min_abs are other code.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -237,7 +238,8 @@ NLC_HD void sincos_bounded(double x, double* s, double* c) {
   const double sy = sin_poly(y), cy = cos_poly(y);
   const double ss = (k & 1) ? cy : sy;
   const double cc = (k & 1) ? sy : cy;
-  *s = (k & 2) ? -ss : ss;
+  // (x = -0.0: the reduction and the polynomial each add a +0 to the -0 and lose its sign; sin is odd, so hand the zero back)
+  *s = x == 0.0 ? x : ((k & 2) ? -ss : ss);
   *c = ((k + 1) & 2) ? -cc : cc;
 }
 
@@ -371,7 +373,17 @@ NLC_HD void tan_parts_short(const IltTrigK& K, double x, double* num, double* de
   for (int i = 2; i < 6; ++i) c = fma(c, z, K.c4[i]);
   const double ca = fma(c, z, 1.0);
   *num = ca + sa;
-  *den = fmax(ca - sa, K.den_min);
+  // At x = the double nearest pi/2 (a saturated phi) the true cos a - sin a is 4.3e-17, below the polynomials' own rounding: they
+  // give 2^-52 there, ABOVE den_min, and the clamp would never engage (|F| = 6.37e15 instead of the reference's 1.633e16;
+  // tests/test_gpu_math_device.py).  So the saturated argument is recognised itself: its difference loses its high word (a
+  // denormal then, which the clamp replaces) -- one compare and one 32-bit select.
+  uint64_t db;
+  const double d = ca - sa;
+  __builtin_memcpy(&db, &d, sizeof(db));
+  db &= x >= K.pio2_hi ? 0xffffffffull : ~0ull;
+  double dd;
+  __builtin_memcpy(&dd, &db, sizeof(dd));
+  *den = fmax(dd, K.den_min);
 }
 
 // ---- round 6: forms of the row-per-lane Fourier ILT kernel (kernels_ilt.hip: ilt_fourier_rows_kernel), where the term index --

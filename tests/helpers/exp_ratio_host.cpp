@@ -1,11 +1,12 @@
 // Host build of the rational exponential of neurallaplacecontrol_amd/csrc/nlc_math.h (exp_ratio_parts) and of the gate forms
-// built on it, for tests/test_exp_ratio_host.py (g++, no GPU).  The device forms differ only in the reciprocal (v_rcp_f64 +
-// one cubic refinement step, <= 1 ulp, instead of a division) and in spelling the clamps as single v_min_f64 instructions.
+// built on it, for tests/test_exp_ratio_host.py (g++, no GPU).  What the device build computes -- the shipped sigmoid_pair2 / tanh2
+// themselves, the two-wide instantiation, v_rcp_f64 + refinement, the v_min_f64 clamps -- is measured by
+// tests/test_gpu_math_device.py, which runs the same tests on tools/math_dev_check.hip's build of these symbols.
 #include "../../neurallaplacecontrol_amd/csrc/nlc_math.h"
 using namespace nlc::m;
 extern "C" {
 // e^y = 2^n num / den: m[i] = 2^n num, d[i] = den (HALF = 0), or from the half argument y / 2 (HALF = 1, tanh's form)
-void nlc_t_exp_ratio(const double* y, double* m, double* d, long n, int half) {
+int nlc_t_exp_ratio(const double* y, double* m, double* d, long n, int half) {
   for (long i = 0; i < n; ++i) {
     double num, den, sh;
     if (half)
@@ -15,9 +16,10 @@ void nlc_t_exp_ratio(const double* y, double* m, double* d, long n, int half) {
     m[i] = ldexp(num, exp_shift_int(sh));
     d[i] = den;
   }
+  return 0;
 }
 // sigmoid_pair2 of nlc_gru_tile.h on (x[i], x[i + 1]) as (a, b) of one hidden unit and (x[i + 2], x[i + 3]) as the other's
-void nlc_t_sigmoid_ratio(const double* x, double* y, long n) {
+int nlc_t_sigmoid_ratio(const double* x, double* y, long n) {
   for (long i = 0; i + 3 < n; i += 4) {
     double D[4], Q[4];
     for (int k = 0; k < 4; ++k) {
@@ -33,9 +35,11 @@ void nlc_t_sigmoid_ratio(const double* x, double* y, long n) {
     y[i + 2] = (D[2] * Q[3]) * inv1;
     y[i + 3] = (D[3] * Q[2]) * inv1;
   }
+  return 0;
 }
 // tanh_pair_fast (the rollout's hidden activation; tanh2 of nlc_gru_tile.h is the same arithmetic two-wide)
-void nlc_t_tanh_ratio(const double* x, double* y, long n) {
+int nlc_t_tanh_ratio(const double* x, double* y, long n) {
   for (long i = 0; i + 1 < n; i += 2) tanh_pair_fast(x[i], x[i + 1], &y[i], &y[i + 1]);
+  return 0;
 }
 }

@@ -6,7 +6,10 @@ Bounds: e^y relative 1.5e-14 (the minimax ratio's own 1.11e-14, tools/exp_ratio_
 plus |n| 2.4e-17 for y = n ln2 + r (the reduction's one ln2 constant is off by 2.3e-17: 1.4e-15 at |y| = 40, where the gates
 stop resolving anything).
 A relative error eps of e^{-x} moves sigmoid(x) by at most eps / 4 and tanh by at most eps / 2, so sigmoid and tanh are held
-to 5e-15 and 8e-15 absolute."""
+to 5e-15 and 8e-15 absolute.
+
+tests/test_gpu_math_device.py runs every test of this module again on the device build of the same symbols
+(tools/math_dev_check.hip), where the gate forms are the shipped sigmoid_pair2 / tanh2 of csrc/nlc_gru_tile.h themselves."""
 
 import ctypes
 import os
@@ -62,7 +65,9 @@ def exp_ratio(lib, y, half=False):
     d = np.empty_like(y)
     f = lib.nlc_t_exp_ratio
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int]
-    f(y.ctypes.data, m.ctypes.data, d.ctypes.data, y.size, int(half))
+    f.restype = ctypes.c_int
+    # (the device build also runs the two-wide instantiation and returns non-zero unless it agrees with the scalar one bit for bit)
+    assert f(y.ctypes.data, m.ctypes.data, d.ctypes.data, y.size, int(half)) == 0
     return m, d
 
 
@@ -71,7 +76,8 @@ def call(lib, name, x):
     y = np.full_like(x, np.nan)
     f = getattr(lib, name)
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long]
-    f(x.ctypes.data, y.ctypes.data, x.size)
+    f.restype = ctypes.c_int
+    assert f(x.ctypes.data, y.ctypes.data, x.size) == 0, name
     return y
 
 
@@ -104,6 +110,7 @@ def test_exp_ratio_relative_error(lib, half):
     assert np.all(np.isfinite(m)) and np.all(d > 0.8) and np.all(d < 1.2)
     err = _exp_rel_err(m, d, y)
     bound = 1.5e-14 + np.abs(np.round(y / _LN2)) * 2.4e-17
+    print(f"exp_ratio_parts half={half}: max rel err {err.max():.3e}, max err / bound {np.max(err / bound):.3f}")
     assert np.all(err <= bound), (err.max(), y[np.argmax(err - bound)])
     assert err[np.abs(y) <= 0.5 * _LN2].max() <= 1.3e-14
 
@@ -136,6 +143,7 @@ def test_sigmoid_gate_form(lib):
     y = call(lib, "nlc_t_sigmoid_ratio", x)
     ref = _sigmoid_ref(x)
     assert np.all(np.isfinite(y)) and np.all(y >= 0) and np.all(y <= 1.0 + 2.3e-16)
+    print(f"sigmoid gate form: max abs err {np.abs(y - ref).max():.3e}")
     assert np.abs(y - ref).max() <= 5e-15
     far = x < -170  # clamped: ~1e-74 instead of the true value, never 0 (the product of four denominators stays finite)
     assert np.all((y[far] > 0) & (y[far] < 1e-73))
@@ -154,8 +162,18 @@ def test_tanh_gate_form(lib):
                         [372.5, -372.5, np.nextafter(372.5, 0), 745.0, -745.0, 1e300, -1e300, 0.0, -0.0]])
     x = np.concatenate([x, np.zeros(x.size % 2)])
     y = call(lib, "nlc_t_tanh_ratio", x)
+    print(f"tanh gate form: max abs err {np.abs(y - _tanh_ref(x)).max():.3e}")
     assert np.abs(y - _tanh_ref(x)).max() <= 8e-15
     assert np.all(np.abs(y) <= 1.0 + 2.3e-16)
     assert np.array_equal(call(lib, "nlc_t_tanh_ratio", -x), -y)
     y = call(lib, "nlc_t_tanh_ratio", np.array([np.inf, -np.inf, np.nan, -np.nan]))
     assert np.all(np.abs(np.abs(y) - 1.0) <= 2.3e-16)
+
+
+def test_tanh_gate_form_keeps_the_sign_of_zero(lib):
+    """tanh_pair_fast / tanh2: -0.0 for -0.0 and +0.0 for +0.0, whatever the other value of the pair is (the comparisons above use
+    ==, which does not see the sign of a zero)."""
+    x = np.array([-0.0, 0.0, 0.0, -0.0, -0.0, -0.0, 0.0, 0.0, -0.0, 0.5, 0.5, -0.0, 0.0, -19.0, 400.0, -0.0])
+    y = call(lib, "nlc_t_tanh_ratio", x)
+    zero = x == 0.0
+    assert np.all(y[zero] == 0.0) and np.array_equal(np.signbit(y[zero]), np.signbit(x[zero])), y
