@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 19
+#define NLC_ABI_VERSION 20
 
 #define NLC_OK 0
 #define NLC_ERR_BAD_ARG (-1)
@@ -183,6 +183,11 @@ int nlc_synchronize(nlc_ctx* ctx);
  *                        NLC_ERR_UNSUPPORTED; an even term count likewise.  The workspace sizes the *_workspace_bytes entries
  *                        return (nlc_train_group_eval_workspace_bytes included) are then the de Hoog layout's.  Other
  *                        algorithms are not affected
+ *   "node_method"        the NODE's fixed-grid solver (train_utils.py:101-125 --node_method, :717-723 odeint(method=...)): 0
+ *                        (default) euler, 1 midpoint, 2 rk4 -- torchdiffeq's 3/8 rule; tableaus in csrc/nlc_node_rk.h.  Any other
+ *                        value: NLC_ERR_BAD_ARG.  Every NODE entry of the ctx reads it at the call: nlc_node_forward,
+ *                        nlc_mppi_configure / the NLC_DYN_NODE rollout, and the nlc_node_train_group_* entries.  nlc_node_desc
+ *                        does not carry it (its size is unchanged)
  *   "fused_keep_sync"    tools only: the merge kernel does not zero the fused body's sync block (tools/fused_debug.py reads
  *                        the launch's progress counters / timeline from it); the next command pays a memset instead
  *   "test_lin_coeff_scale"  tests only: the largest coefficient of the LIN rollout instances' folded w_re / t fragment is
@@ -475,9 +480,12 @@ int nlc_train_keep_best(nlc_ctx* ctx, int M, int64_t P, const double* loss_dev, 
 /* ---- baseline model: NODE (train_utils.py:664-724; ODE function xOdeFuncInXAndU :637-661; factory :101-125;
  * node_hidden_units 270, node_augment_dim 1, node_method "euler": config.py:40-42).
  *   x = cat((obs - mean)/std, zeros(augment_dim)); u = window[:, -1, :] (raw);
- *   out = odeint(f(., u), x, [0, ts_pred[0] / time_div], method="euler", step_size)[-1][:, :d]
- * torchdiffeq's fixed-grid Euler solver is restated (grid t_k = k*step_size, last point = the end time):
- * PARITY UNPINNED vs upstream torchdiffeq (absent offline); everything else is pinned against the reference classes. */
+ *   out = odeint(f(., u), x, [0, ts_pred[0] / time_div], method, step_size)[-1][:, :d]
+ * torchdiffeq's fixed-grid solvers are restated (grid t_k = k*step_size, last point = the end time; method = the ctx option
+ * "node_method": euler, midpoint, or rk4 = the 3/8 rule; one sub-step Y_i = y + h sum_j a_ij k_j, k_i = f(Y_i),
+ * y' = y + h sum_i b_i k_i, csrc/nlc_node_rk.h): grid and solvers alike
+ * PARITY UNPINNED vs upstream torchdiffeq (absent offline); everything else is pinned against the reference classes.
+ * A prediction time may need at most 8 sub-steps in nlc_node_forward and the planner, whatever the method. */
 typedef struct {
   int32_t d;           /* state_dim */
   int32_t nu;          /* action_dim */
@@ -503,9 +511,12 @@ int nlc_node_forward(nlc_ctx* ctx, const double* obs_dev, const double* action_d
  *   window_dev (rows, B, nu): the newest action window[:, B-1, :] is read, raw.  ts_dev (rows): raw prediction times.
  *   row_times == 0: every row of a member's batch integrates to the time of its first row, ts[idx[0]] (:719, what NODE.forward
  *   does); != 0: each row to its own ts[idx[r]].  The sub-step counts are formed on the device (torchdiffeq's fixed grid:
- *   ceil(t / step_size + 1) points); nothing reads ts on the host.  A row takes at most 256 sub-steps: the workspace is a
- *   function of (M, N) and the model's shape alone, and a row whose time is not positive, is NaN, or needs more sub-steps gets
- *   a NaN squared error (so the member's loss is NaN) and touches no memory outside the workspace.
+ *   ceil(t / step_size + 1) points); nothing reads ts on the host.  A row takes at most 256 evaluations of the ODE function
+ *   (256 euler, 128 midpoint, 64 rk4 sub-steps; the stage inputs are taped where Euler tapes its states): the workspace is a
+ *   function of (M, N) and the model's shape alone and the same for every method, and a row whose time is not positive, is NaN,
+ *   or needs more sub-steps gets a NaN squared error (so the member's loss is NaN) and touches no memory outside the workspace.
+ *   The backward of a sub-step: kbar_i = h b_i ybar'; for i = s .. 1: Ybar_i = J_f(Y_i)^T kbar_i, kbar_j += h a_ij Ybar_i (j < i);
+ *   ybar = ybar' + sum_i Ybar_i.
  *   The single-model forms are M = 1, data_row_stride = 0.  Three launches (training) or two (evaluation) on the ctx's stream,
  *   no atomics, no host synchronisation. */
 /* train_utils.py:388-408, run_exp_multi.py:105-110 */

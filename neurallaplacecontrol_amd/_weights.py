@@ -154,6 +154,17 @@ class HipModelMirror(WeightsKeyMixin):
         ctx.check(getattr(ctx.lib, self._set_model_symbol)(ctx.h, C.byref(desc), _lib.ptr(blob), blob.numel()))
         return key
 
+    def _ctx_options(self):
+        """``nlc_set_option`` settings that belong to the model's descriptor without being part of its struct (NODE: the
+        solver).  ``sync_to`` sets them with every upload."""
+        return {}
+
+    def sync_to(self, ctx):
+        """``upload(ctx)`` after the model's ctx options: what the model's own ctx, planners and trainers call."""
+        for name, value in self._ctx_options().items():
+            ctx.set_option(name, value)
+        return self.upload(ctx)
+
     def hip_ctx(self, device=None):
         """The model's own ``nlc_ctx`` (its forward's) with its current weights uploaded."""
         dev = compute_device(next(self.parameters())) if device is None else torch.device(device)
@@ -161,7 +172,7 @@ class HipModelMirror(WeightsKeyMixin):
             self._ctx = _lib.Ctx(dev.index)
             self._uploaded_key = None
         if self._weights_key() != self._uploaded_key:
-            self._uploaded_key = self.upload(self._ctx)
+            self._uploaded_key = self.sync_to(self._ctx)
         return self._ctx
 
     # ------------------------------------------------------------------ guards

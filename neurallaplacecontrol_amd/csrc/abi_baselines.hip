@@ -302,7 +302,7 @@ extern "C" int nlc_node_forward(nlc_ctx* c, const double* obs, const double* act
   f.action = action;
   f.out = out;
   ProfScope ps(c, "node_forward_kernel");
-  NLC_HIP(c, launch_node_forward(f, c->nodem.node_ht, c->stream));
+  NLC_HIP(c, launch_node_forward(f, c->nodem.node_ht, c->opt.node_method, c->stream));
   return NLC_OK;
   NLC_GUARD_END(c)
 }

@@ -167,6 +167,9 @@ extern "C" int nlc_set_option(nlc_ctx* c, const char* name, double value) {
   } else if (n == "train_dehoog") {
     if (value != 0 && value != 1) return fail(c, NLC_ERR_BAD_ARG, "train_dehoog must be 0 or 1");
     c->opt.train_dehoog = (int)value;
+  } else if (n == "node_method") {
+    if (value != 0 && value != 1 && value != 2) return fail(c, NLC_ERR_BAD_ARG, "node_method must be 0 (euler), 1 (midpoint) or 2 (rk4)");
+    c->opt.node_method = (int)value;
   } else if (n == "test_lin_coeff_scale") {
     c->opt.test_lin_coeff_scale = value;
     c->has_mppi = false;  // folded at nlc_mppi_configure

@@ -57,7 +57,7 @@ extern "C" int nlc_mppi_configure(nlc_ctx* c, const nlc_mppi_desc* d) {
       return fail(c, NLC_ERR_BAD_SHAPE, "model state/action dims differ from the planner's");
     double h[8];
     if (node_substeps(d->ts_pred / c->nodem.nd.time_div, c->nodem.nd.step_size, h, 8) < 0)
-      return fail(c, NLC_ERR_UNSUPPORTED, "ts_pred needs more than 8 Euler sub-steps (or is <= 0)");
+      return fail(c, NLC_ERR_UNSUPPORTED, "ts_pred needs more than 8 sub-steps of the solver's grid (or is <= 0)");
   } else {
     return fail(c, NLC_ERR_UNSUPPORTED, "unknown dynamics id");
   }
@@ -416,7 +416,7 @@ static int rollout_baseline(nlc_ctx* c, RolloutCall& call) {
     r.net = c->nodem.node;
     r.net.nsub = node_substeps(d.ts_pred / c->nodem.nd.time_div, c->nodem.nd.step_size, r.net.hsub, 8);
     ProfScope ps(c, "node_rollout_kernel");
-    NLC_HIP(c, launch_node_rollout(r, c->nodem.node_ht, c->stream));
+    NLC_HIP(c, launch_node_rollout(r, c->nodem.node_ht, c->opt.node_method, c->stream));
   } else if (d.dynamics == NLC_DYN_DTRNN) {
     RnnArgs g = c->rnnm.rnn;
     g.mode = 1;

@@ -79,7 +79,8 @@ Plan rnn_plan_of(const nlc_ctx* c, int64_t N) {
   return p;
 }
 
-// (the slab is a function of the shape alone: it holds the state tape of kNodeTrainMaxSub sub-steps, whatever ts says)
+// (the slab is a function of the shape alone: it holds the tape of kNodeTrainMaxSub ODE-function inputs, whatever ts says and
+// whichever method the ctx option "node_method" names)
 Plan node_plan_of(const nlc_ctx* c, int64_t N) {
   Plan p{};
   const nlc_node_desc& nd = c->nodem.nd;
@@ -407,16 +408,16 @@ int node_fwd_bwd(nlc_ctx* c, const Batch& b, int B, const Plan& p, const WsPtrs&
   fill_train_ws(a, p, w);
   a.L = node_act_layout(a.H, a.d + a.aug + a.nu);
   ProfScope ps(c, "node_train_fwd_bwd_kernel");
-  NLC_HIP(c, launch_node_train_fwd_bwd(a, p.nblk, p.M, c->stream));
+  NLC_HIP(c, launch_node_train_fwd_bwd(a, c->opt.node_method, p.nblk, p.M, c->stream));
   return NLC_OK;
 }
 
 int node_eval(nlc_ctx* c, const Batch& b, int B, const Plan& p, double* tile_loss) {
   NodeTrainArgs a = node_args(c, b, B, p);
   a.tile_loss = tile_loss;
-  const int per_cu = eval_per_cu(node_lds_doubles(false) * (int64_t)sizeof(double));
+  const int per_cu = eval_per_cu(node_lds_doubles(false, nlc::node_rk_stages(c->opt.node_method)) * (int64_t)sizeof(double));
   ProfScope ps(c, "node_eval_kernel");
-  NLC_HIP(c, launch_node_eval(a, eval_grid(a.ntiles, c->prop.multiProcessorCount, per_cu, p.M), p.M, c->stream));
+  NLC_HIP(c, launch_node_eval(a, c->opt.node_method, eval_grid(a.ntiles, c->prop.multiProcessorCount, per_cu, p.M), p.M, c->stream));
   return NLC_OK;
 }
 

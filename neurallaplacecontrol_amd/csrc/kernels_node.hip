@@ -10,6 +10,9 @@
 // in exactly the accumulator layout of the last layer's output tile (row 4r + q), so an Euler sub-step is
 // y_r += h * o_r with no lane movement, and y_r is directly the layer-1 B fragment of the next sub-step.
 //
+// The other two fixed-grid solvers torchdiffeq offers with a step_size, midpoint and rk4 (the 3/8 rule), are instances of the
+// same kernels: the tableau of nlc_node_rk.h is a template parameter (ctx option "node_method"), see node_integrate.
+//
 // Hidden activations: the short tanh pair of nlc_math.h (tanh_pair_fast: absolute error <= 1.5e-13, one reciprocal per
 // pair; round 3: 6.39 -> 6.31 ms per K = 16384, T = 40 rollout, every test at its tolerance).
 // Roofline: FP64 MFMA.  Per 16 samples and Euler sub-step: 3 HT + 4 HT^2 + 4 HT MFMAs (HT = ceil(H/16) = 17 for
@@ -17,6 +20,7 @@
 #include "nlc_device.h"
 #include "nlc_envcost.h"
 #include "nlc_kernels.h"
+#include "nlc_node_rk.h"
 
 namespace nlc {
 
@@ -57,23 +61,63 @@ __device__ __forceinline__ v4d node_eval(const NodeNetArgs& n, int lane, int q, 
   return o[0];
 }
 
-// Euler integration of the augmented normalised state for the wave's samples.  y0/y1: rows q and 4+q of
+// Fixed-grid integration of the augmented normalised state for the wave's samples.  y0/y1: rows q and 4+q of
 // [x_norm | aug]; ua/ub/uc: this lane's u entries for input indices q, 4+q, 8+q (0 where the index is not an action).
-template <int HT>
+// METHOD picks the tableau of nlc_node_rk.h at compile time; the Euler instance (one stage) is the loop it has always been.
+// With more stages the slopes k_i live in two registers per lane each, in y's layout (the accumulator layout of the output
+// tile), so a stage input y + h sum_j a_ij k_j is formed with no lane movement, as the Euler update is.
+template <int HT, int METHOD>
 __device__ __forceinline__ void node_integrate(const NodeNetArgs& n, int lane, int q, double& y0, double& y1, double ua,
                                                double ub, double uc) {
+  constexpr const NodeRk& T = NodeRkOf<METHOD>::T;
   const int dy = n.d + n.aug;
-  for (int s = 0; s < n.nsub; ++s) {
-    const double in0 = (q < dy) ? y0 : ua;
-    const double in1 = (4 + q < dy) ? y1 : ub;
-    const v4d o = node_eval<HT>(n, lane, q, in0, in1, uc);
-    const double h = n.hsub[s];
-    if (q < dy) y0 = y0 + h * o[0];
-    if (4 + q < dy) y1 = y1 + h * o[1];
+  if constexpr (T.s == 1) {
+    for (int s = 0; s < n.nsub; ++s) {
+      const double in0 = (q < dy) ? y0 : ua;
+      const double in1 = (4 + q < dy) ? y1 : ub;
+      const v4d o = node_eval<HT>(n, lane, q, in0, in1, uc);
+      const double h = n.hsub[s];
+      if (q < dy) y0 = y0 + h * o[0];
+      if (4 + q < dy) y1 = y1 + h * o[1];
+    }
+  } else {
+    // One loop over the nsub * s evaluations of the ODE function, the stage number i a run-time value: one copy of the
+    // function's body whatever s is (unrolled over the stages, two weight streams interleave and the widest instance
+    // spills).  Every sum runs over all s slopes with the tableau's zeros for j >= i; those slopes are zero then, too.
+    double k0[T.s], k1[T.s];
+#pragma unroll
+    for (int j = 0; j < T.s; ++j) k0[j] = k1[j] = 0.0;
+    int i = 0, s = 0;
+    for (int e = 0; e < n.nsub * T.s; ++e) {
+      const double h = n.hsub[s];
+      double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+      for (int j = 0; j < T.s - 1; ++j) {
+        a0 += T.a[i][j] * k0[j];
+        a1 += T.a[i][j] * k1[j];
+      }
+      const double Y0 = i == 0 ? y0 : y0 + h * a0, Y1 = i == 0 ? y1 : y1 + h * a1;
+      const double in0 = (q < dy) ? Y0 : ua;
+      const double in1 = (4 + q < dy) ? Y1 : ub;
+      const v4d o = node_eval<HT>(n, lane, q, in0, in1, uc);
+#pragma unroll
+      for (int j = 0; j < T.s; ++j) {
+        k0[j] = j == i ? o[0] : k0[j];
+        k1[j] = j == i ? o[1] : k1[j];
+      }
+      if (++i == T.s) {
+        if (q < dy) y0 = node_rk_combine(T, y0, h, k0);
+        if (4 + q < dy) y1 = node_rk_combine(T, y1, h, k1);
+#pragma unroll
+        for (int j = 0; j < T.s; ++j) k0[j] = k1[j] = 0.0;
+        i = 0;
+        ++s;
+      }
+    }
   }
 }
 
-template <int HT>
+template <int HT, int METHOD>
 __global__ __launch_bounds__(256) void node_rollout_kernel(const NodeRolloutArgs a) {
   const NodeNetArgs& n = a.net;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -108,7 +152,7 @@ __global__ __launch_bounds__(256) void node_rollout_kernel(const NodeRolloutArgs
     };
     double y0 = (i0 < d) ? (x0 - m0) / s0 : 0.0;  // augmented rows start at zero (:705-708)
     double y1 = (i1 < d) ? (x1 - m1) / s1 : 0.0;
-    node_integrate<HT>(n, lane, q, y0, y1, upick(i0), upick(i1), upick(i2));
+    node_integrate<HT, METHOD>(n, lane, q, y0, y1, upick(i0), upick(i1), upick(i2));
     // state + model(state, window, ts_pred): the model's output is the INTEGRATED normalised state (:724)
     if (i0 < d) x0 = x0 + y0;
     if (i1 < d) x1 = x1 + y1;
@@ -137,7 +181,7 @@ __global__ __launch_bounds__(256) void node_rollout_kernel(const NodeRolloutArgs
 }
 
 // NODE.forward: obs (N, d), newest action (N, nu) -> integrated normalised state (N, d)
-template <int HT>
+template <int HT, int METHOD>
 __global__ __launch_bounds__(256) void node_forward_kernel(const NodeForwardArgs a) {
   const NodeNetArgs& n = a.net;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -153,34 +197,55 @@ __global__ __launch_bounds__(256) void node_forward_kernel(const NodeForwardArgs
     const int j = i - dy;
     return (j >= 0 && j < n.nu) ? a.action[rc * n.nu + j] : 0.0;
   };
-  node_integrate<HT>(n, lane, q, y0, y1, upick(i0), upick(i1), upick(i2));
+  node_integrate<HT, METHOD>(n, lane, q, y0, y1, upick(i0), upick(i1), upick(i2));
   if (valid) {
     if (i0 < d) a.out[r * d + i0] = y0;
     if (i1 < d) a.out[r * d + i1] = y1;
   }
 }
 
-hipError_t launch_node_rollout(const NodeRolloutArgs& a, int ht, hipStream_t s) {
-  if (a.K <= 0) return hipSuccess;
-  const unsigned grid = (unsigned)((a.K + 63) / 64);
+namespace {
+template <int METHOD>
+hipError_t node_rollout_of(const NodeRolloutArgs& a, int ht, unsigned grid, hipStream_t s) {
   switch (ht) {
-    case 4: hipLaunchKernelGGL((node_rollout_kernel<4>), dim3(grid), dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((node_rollout_kernel<8>), dim3(grid), dim3(256), 0, s, a); break;
-    case 17: hipLaunchKernelGGL((node_rollout_kernel<17>), dim3(grid), dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((node_rollout_kernel<4, METHOD>), dim3(grid), dim3(256), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((node_rollout_kernel<8, METHOD>), dim3(grid), dim3(256), 0, s, a); break;
+    case 17: hipLaunchKernelGGL((node_rollout_kernel<17, METHOD>), dim3(grid), dim3(256), 0, s, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-hipError_t launch_node_forward(const NodeForwardArgs& a, int ht, hipStream_t s) {
-  if (a.N <= 0) return hipSuccess;
-  const unsigned grid = (unsigned)((a.N + 63) / 64);
+template <int METHOD>
+hipError_t node_forward_of(const NodeForwardArgs& a, int ht, unsigned grid, hipStream_t s) {
   switch (ht) {
-    case 4: hipLaunchKernelGGL((node_forward_kernel<4>), dim3(grid), dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((node_forward_kernel<8>), dim3(grid), dim3(256), 0, s, a); break;
-    case 17: hipLaunchKernelGGL((node_forward_kernel<17>), dim3(grid), dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((node_forward_kernel<4, METHOD>), dim3(grid), dim3(256), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((node_forward_kernel<8, METHOD>), dim3(grid), dim3(256), 0, s, a); break;
+    case 17: hipLaunchKernelGGL((node_forward_kernel<17, METHOD>), dim3(grid), dim3(256), 0, s, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_node_rollout(const NodeRolloutArgs& a, int ht, int method, hipStream_t s) {
+  if (a.K <= 0) return hipSuccess;
+  const unsigned grid = (unsigned)((a.K + 63) / 64);
+  switch (method) {
+    case 0: return node_rollout_of<0>(a, ht, grid, s);
+    case 1: return node_rollout_of<1>(a, ht, grid, s);
+    case 2: return node_rollout_of<2>(a, ht, grid, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_node_forward(const NodeForwardArgs& a, int ht, int method, hipStream_t s) {
+  if (a.N <= 0) return hipSuccess;
+  const unsigned grid = (unsigned)((a.N + 63) / 64);
+  switch (method) {
+    case 0: return node_forward_of<0>(a, ht, grid, s);
+    case 1: return node_forward_of<1>(a, ht, grid, s);
+    case 2: return node_forward_of<2>(a, ht, grid, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace nlc

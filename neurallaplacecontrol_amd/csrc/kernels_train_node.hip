@@ -12,6 +12,10 @@
 //                               Backward: a sub-step's two hidden layers are rebuilt from x_k; its deltas and activations go to
 //                               the slab, and every kNodeChunk sub-steps one pass adds their outer products to the workgroup's
 //                               partial in blob order (wgrad_mfma: the samples are the MFMA's k).
+//   node_train_fwd_bwd_rk_kernel<METHOD>, node_eval_rk_kernel<METHOD>
+//                               the same template for the midpoint and rk4 tableaus of nlc_node_rk.h (ctx option "node_method"):
+//                               the stage inputs Y_i are taped where Euler tapes x_k, and the backward walks a sub-step's stages
+//                               last to first (kbar_i = h b_i ybar', Ybar_i = J_f(Y_i)^T kbar_i, kbar_j += h a_ij Ybar_i).
 //   node_eval_kernel            the forward half: nothing taped, no slab; the tile's sum of squared errors to tile_loss[tile].
 //
 // Few live rows (the reference trains NODE at batch 1): the 2.weight products put the lanes along the contiguous input index of
@@ -121,8 +125,16 @@ __device__ __forceinline__ void hidden_fwd(const NodeW& w, const double* xS, con
   __syncthreads();
 }
 
-template <bool kTrain>
-__device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
+// METHOD: the tableau of nlc_node_rk.h, its stage count S a compile-time constant; the Euler instances (S = 1) are the code
+// they have always been.  S > 1: rkS (LDS of the kernel's own) holds y, the slopes k_i and, in training, their adjoints
+// kbar_i, kRows * LX doubles each; the tape holds the stage inputs Y_i (entry k S + i) and a weight-gradient chunk kNodeChunk / S
+// sub-steps.
+template <bool kTrain, int METHOD>
+__device__ __forceinline__ void node_tiles(const NodeTrainArgs& a, double* rkS) {
+  constexpr const NodeRk& T = NodeRkOf<METHOD>::T;
+  constexpr int S = T.s;
+  constexpr int RK = kRows * LX;              // one small per-row array
+  constexpr int kMaxSub = kNodeTrainMaxSub / S;  // node_train_max_sub(METHOD)
   static_assert(kSlots * 64 >= kNodeMaxH, "a lane's column slots cover the widest layer");
   __shared__ double a1S[kRows * LH];  // tanh of layer 0; backward: its delta, in place
   __shared__ double a2S[kRows * LH];  // tanh of layer 2; backward: its delta, in place
@@ -178,7 +190,7 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
         const int64_t tsrc = a.row_times ? src : (idx ? idx[0] : 0);
         int bad = 0;
         const double te = valid ? tsp[tsrc] / a.time_div : 0.0;
-        const int ns = valid ? node_euler_count(te, a.step_size, &bad) : 0;
+        const int ns = !valid ? 0 : S == 1 ? node_euler_count(te, a.step_size, &bad) : node_rk_count(te, a.step_size, kMaxSub, &bad);
         teS[r] = te;
         nsS[r] = ns;
         badS[r] = valid ? bad : 0;
@@ -187,10 +199,11 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
     __syncthreads();
     int kmax = 0;
     for (int r = 0; r < kRows; ++r) kmax = nsS[r] > kmax ? nsS[r] : kmax;
-    kmax = kmax < kNodeTrainMaxSub ? kmax : kNodeTrainMaxSub;  // node_euler_count already holds this; the slab relies on it
+    kmax = kmax < kMaxSub ? kmax : kMaxSub;  // node_euler_count / node_rk_count already hold this; the slab relies on it
     const int r16 = threadIdx.x >> 4, q16 = threadIdx.x & 15;
 
     // ---- forward Euler
+    if constexpr (S == 1) {
     for (int k = 0; k < kmax; ++k) {
       if (kTrain && threadIdx.x < kRows * LX) ws[L.Xt + (int64_t)k * kRows * LX + threadIdx.x] = xS[threadIdx.x];
       hidden_fwd(w, xS, uS, a1S, a2S, nlive);
@@ -202,6 +215,35 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
           if (q16 == 0 && k < ns) xS[r16 * LX + i] += hk * f;
         }
       }
+      __syncthreads();
+    }
+    } else {
+      // ---- forward, S stages a sub-step: xS is the stage input Y_i, y and the slopes stay in rkS.  Thread t < RK owns
+      // component t = r * LX + c of y, Y_i and every k_i; the slopes of a row are written by its lane q16 = 0
+      double* yS = rkS;
+      double* kS = rkS + RK;
+      const int t = threadIdx.x;
+      if (t < RK) yS[t] = xS[t];
+      for (int k = 0; k < kmax; ++k) {
+        const int nsr = t < RK ? nsS[t >> 3] : 0;
+        const double hk = (t < RK && k < nsr) ? node_euler_width(teS[t >> 3], a.step_size, nsr, k) : 0.0;
+        for (int st = 0; st < S; ++st) {
+          if (t < RK) {
+            const double Y = node_rk_stage_input(T, st, yS[t], hk, kS + t, RK);
+            xS[t] = Y;
+            if (kTrain) ws[L.Xt + ((int64_t)k * S + st) * RK + t] = Y;
+          }
+          __syncthreads();
+          hidden_fwd(w, xS, uS, a1S, a2S, nlive);
+          for (int i = 0; i < dy; ++i) {
+            const double f = dot16(w.W4 + (int64_t)i * H, 1, a2S + r16 * LH, H) + w.b4[i];
+            if (q16 == 0) kS[st * RK + r16 * LX + i] = f;
+          }
+          __syncthreads();
+        }
+        if (t < RK && k < nsr && (t & 7) < dy) yS[t] = node_rk_combine(T, yS[t], hk, kS + t, RK);
+      }
+      if (t < RK) xS[t] = yS[t];
       __syncthreads();
     }
     // ---- squared error of the first d columns (the augmented ones are dropped: their adjoint is 0) and dL/dx at the end
@@ -222,14 +264,28 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
         tile_loss[tile] = s;
     }
     if constexpr (kTrain) {
-      // ---- backward through the sub-steps, kNodeChunk at a time: sample (kk, r) of a chunk is s = kk * nlive + r
+      // ---- backward through the sub-steps, kNodeChunk evaluations of the ODE function at a time (CS sub-steps of S stages,
+      // last stage first): sample (kk, r) of a chunk is s = kk * nlive + r
+      constexpr int CS = kNodeChunk / S;
+      double* kbS = rkS + (1 + S) * RK;  // S > 1: kbar_i, component t = r * LX + c
       const int Q = (H + kWaves - 1) / kWaves;
       const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-      for (int kend = kmax; kend > 0; kend -= kNodeChunk) {
-        const int kbeg = kend > kNodeChunk ? kend - kNodeChunk : 0;
+      for (int kend = kmax; kend > 0; kend -= CS) {
+        const int kbeg = kend > CS ? kend - CS : 0;
         for (int k = kend - 1; k >= kbeg; --k) {
-          const int64_t s0 = (int64_t)(kend - 1 - k) * nlive;
-          if (threadIdx.x < kRows * LX) xS[threadIdx.x] = ws[L.Xt + (int64_t)k * kRows * LX + threadIdx.x];
+          if constexpr (S > 1) {
+            // kbar_i = h b_i ybar' (zero where the row has no sub-step k); the stage's first barrier orders it
+            if (threadIdx.x < RK) {
+              const int r = threadIdx.x >> 3, i = threadIdx.x & 7;
+              const int ns = nsS[r];
+              const bool on = r < nlive && i < dy && k < ns;
+              const double hk = on ? node_euler_width(teS[r], a.step_size, ns, k) : 0.0;
+              for (int st = 0; st < S; ++st) kbS[st * RK + threadIdx.x] = on ? node_rk_kbar_init(T, st, hk, xbS[threadIdx.x]) : 0.0;
+            }
+          }
+          for (int st = S - 1; st >= 0; --st) {
+          const int64_t s0 = ((int64_t)(kend - 1 - k) * S + (S - 1 - st)) * nlive;
+          if (threadIdx.x < kRows * LX) xS[threadIdx.x] = ws[L.Xt + ((int64_t)k * S + st) * kRows * LX + threadIdx.x];
           __syncthreads();
           hidden_fwd(w, xS, uS, a1S, a2S, nlive);
           // the sample's activations, its input and dL/df; a row past its own count adds zeros
@@ -246,7 +302,11 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
             const int r = threadIdx.x >> 3, i = threadIdx.x & 7;
             const int ns = nsS[r];
             const bool on = r < nlive && i < dy && k < ns;
-            const double v = on ? node_out_delta(node_euler_width(teS[r], a.step_size, ns, k), xbS[r * LX + i]) : 0.0;
+            double v;
+            if constexpr (S == 1)
+              v = on ? node_out_delta(node_euler_width(teS[r], a.step_size, ns, k), xbS[r * LX + i]) : 0.0;
+            else
+              v = on ? kbS[st * RK + threadIdx.x] : 0.0;
             d3S[r * LX + i] = v;
             if (r < nlive) ws[L.D3 + (s0 + r) * LX + i] = v;
           }
@@ -306,15 +366,28 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
             }
             __syncthreads();
           }
-          // dL/dx_k = dL/dx_{k+1} + W0[:, :dy]^T d1
+          // dL/dx_k = dL/dx_{k+1} + W0[:, :dy]^T d1 (S > 1: ybar += Ybar_i, and kbar_j += h a_ij Ybar_i for j < i)
+          if constexpr (S == 1) {
           for (int i = 0; i < dy; ++i) {
             const double g = dot16(w.W0 + i, in, a1S + r16 * LH, H);
             if (q16 == 0 && r16 < nlive) xbS[r16 * LX + i] += g;
           }
+          } else {
+            const int nsr = nsS[r16];
+            const double hk = k < nsr ? node_euler_width(teS[r16], a.step_size, nsr, k) : 0.0;
+            for (int i = 0; i < dy; ++i) {
+              const double g = dot16(w.W0 + i, in, a1S + r16 * LH, H);
+              if (q16 == 0 && r16 < nlive) {
+                xbS[r16 * LX + i] += g;
+                for (int j = 0; j < st; ++j) kbS[j * RK + r16 * LX + i] += node_rk_kbar_add(T, st, j, hk, g);
+              }
+            }
+          }
           __syncthreads();
+          }
         }
-        // ---- the chunk's weight gradients: one pass over the partial, sums over its (sub-step, row) samples
-        const int ns = (kend - kbeg) * nlive;
+        // ---- the chunk's weight gradients: one pass over the partial, sums over its (evaluation, row) samples
+        const int ns = (kend - kbeg) * S * nlive;
         const bool first = !summed;
         wgrad_mfma(part + a.off[0], H, in, ns, ws + L.D1, H, ws + L.Z, in, first);
         bgrad(part + a.off[1], H, ns, ws + L.D1, H, first);
@@ -337,16 +410,37 @@ __device__ __forceinline__ void node_tiles(const NodeTrainArgs& a) {
 
 }  // namespace
 
-__global__ __launch_bounds__(kThreads) void node_train_fwd_bwd_kernel(const NodeTrainArgs a) { node_tiles<true>(a); }
-__global__ __launch_bounds__(kThreads) void node_eval_kernel(const NodeTrainArgs a) { node_tiles<false>(a); }
+__global__ __launch_bounds__(kThreads) void node_train_fwd_bwd_kernel(const NodeTrainArgs a) { node_tiles<true, 0>(a, nullptr); }
+__global__ __launch_bounds__(kThreads) void node_eval_kernel(const NodeTrainArgs a) { node_tiles<false, 0>(a, nullptr); }
+// the multi-stage methods' instances
+template <int METHOD>
+__global__ __launch_bounds__(kThreads) void node_train_fwd_bwd_rk_kernel(const NodeTrainArgs a) {
+  __shared__ double rkS[node_rk_lds_doubles(true, node_rk_stages(METHOD))];
+  node_tiles<true, METHOD>(a, rkS);
+}
+template <int METHOD>
+__global__ __launch_bounds__(kThreads) void node_eval_rk_kernel(const NodeTrainArgs a) {
+  __shared__ double rkS[node_rk_lds_doubles(false, node_rk_stages(METHOD))];
+  node_tiles<false, METHOD>(a, rkS);
+}
 
-hipError_t launch_node_train_fwd_bwd(const NodeTrainArgs& a, int nblk, int M, hipStream_t s) {
-  hipLaunchKernelGGL(node_train_fwd_bwd_kernel, dim3(nblk, M), dim3(kThreads), 0, s, a);
+hipError_t launch_node_train_fwd_bwd(const NodeTrainArgs& a, int method, int nblk, int M, hipStream_t s) {
+  switch (method) {
+    case 0: hipLaunchKernelGGL(node_train_fwd_bwd_kernel, dim3(nblk, M), dim3(kThreads), 0, s, a); break;
+    case 1: hipLaunchKernelGGL(node_train_fwd_bwd_rk_kernel<1>, dim3(nblk, M), dim3(kThreads), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(node_train_fwd_bwd_rk_kernel<2>, dim3(nblk, M), dim3(kThreads), 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_node_eval(const NodeTrainArgs& a, int G, int M, hipStream_t s) {
-  hipLaunchKernelGGL(node_eval_kernel, dim3(G, M), dim3(kThreads), 0, s, a);
+hipError_t launch_node_eval(const NodeTrainArgs& a, int method, int G, int M, hipStream_t s) {
+  switch (method) {
+    case 0: hipLaunchKernelGGL(node_eval_kernel, dim3(G, M), dim3(kThreads), 0, s, a); break;
+    case 1: hipLaunchKernelGGL(node_eval_rk_kernel<1>, dim3(G, M), dim3(kThreads), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(node_eval_rk_kernel<2>, dim3(G, M), dim3(kThreads), 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

@@ -72,6 +72,7 @@ struct PlannerOptions {
   int dehoog_streams = 0;           // staged de Hoog planner: parts of the population on streams of their own (0 auto)
   int linear_fused = 1;             // fixed Talbot / Stehfest models: LIN instances of the rollout kernels (0: the staged path)
   int train_dehoog = 0;             // training entries: 1 = de Hoog NL models take the fused step (kernels_train_dehoog.hip); 0: refused
+  int node_method = 0;              // every NODE entry: the fixed-grid solver (nlc_node_rk.h): 0 euler, 1 midpoint, 2 rk4
   int host_spin = 1;                // nlc_mppi_finish with a host action pointer: 1 spin on a pinned word the merge kernel
                                     // stores, 2 sleep through the predicted wait first, 0 hipStreamSynchronize
   double host_spin_margin_us = 150.0;  // host_spin 2: the host wakes this long (or 15 % of the predicted wait) before the predicted end

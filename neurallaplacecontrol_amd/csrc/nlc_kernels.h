@@ -414,7 +414,7 @@ struct NodeNetArgs {
   const double* W3p;   // [4*HT][1][64]   rows 0 .. d+aug-1
   const double* b3;    // (16)
   double state_mean[NLC_MAX_D], state_std[NLC_MAX_D];  // (0, 1) if !normalize
-  int nsub;            // Euler sub-steps of the fixed grid over [0, ts_pred / time_div] (step_size 0.05)
+  int nsub;            // sub-steps of the fixed grid over [0, ts_pred / time_div] (step_size 0.05)
   double hsub[8];
 };
 struct NodeRolloutArgs : SampleCostArgs {
@@ -428,8 +428,9 @@ struct NodeForwardArgs {
   const double* action;  // (N, nu): window[:, -1, :]
   double* out;           // (N, d)
 };
-hipError_t launch_node_rollout(const NodeRolloutArgs& a, int ht, hipStream_t s);
-hipError_t launch_node_forward(const NodeForwardArgs& a, int ht, hipStream_t s);
+// method: the fixed-grid solver (nlc_node_rk.h; the ctx option "node_method"), its stage count a template parameter
+hipError_t launch_node_rollout(const NodeRolloutArgs& a, int ht, int method, hipStream_t s);
+hipError_t launch_node_forward(const NodeForwardArgs& a, int ht, int method, hipStream_t s);
 
 // ------------------------------------------------------------------ env side of the evaluation loop
 // step_env (mppi_with_model.py:193-216) for E independent envs: get_action (delay buffer, :25-28), one Euler step of

@@ -5,10 +5,16 @@
 action_mean action_std dt``), so checkpoints written by the reference load unchanged.
 
 ``forward`` is one HIP launch (``nlc_node_forward``): the ODE function's three layers on FP64 matrix cores inside the
-fixed-grid Euler loop; behind ``NLDynamics`` the planner runs it inside the horizon loop (``NLC_DYN_NODE``).
-``torchdiffeq.odeint(method="euler", options={"step_size": 0.05})`` is restated (grid ``k * step_size``, last point =
-the end time): **parity unpinned vs upstream torchdiffeq**, which is absent offline.  The HIP path is inference-only
-and float64; in grad mode ``forward`` is the same op sequence in torch ops on PyTorch-ROCm (trainable).
+fixed-grid solver's loop; behind ``NLDynamics`` the planner runs it inside the horizon loop (``NLC_DYN_NODE``).
+``torchdiffeq.odeint(method=..., options={"step_size": 0.05})`` is restated (grid ``k * step_size``, last point =
+the end time) for the three fixed-grid solvers used with a ``step_size``: ``method="euler"`` (the default,
+``--node_method``), ``"midpoint"`` and ``"rk4"`` -- torchdiffeq's fixed-grid ``rk4`` is the 3/8 rule, not the classic
+tableau.  Grid and solvers alike: **parity unpinned vs upstream torchdiffeq**, which is absent offline.  Any other
+``method`` raises ``NotImplementedError``.  The tableaus are ``csrc/nlc_node_rk.h``'s (``RK_TABLEAUS`` here restates them
+for the grad-mode path); the method reaches the library as the ctx option ``node_method`` with every upload of the
+descriptor (``sync_to``), and ``model.method`` may be reassigned: planners and trainers pick the change up at their next call.  The
+HIP path is inference-only and float64; in grad mode ``forward`` is the same op sequence in torch ops on PyTorch-ROCm
+(trainable).
 
 The plumbing every mirror shares (normalisation buffers and constants, ``upload`` / ``hip_ctx``, the guards) is
 ``_weights.HipModelMirror``; NODE uses the state half of the constants only.
@@ -47,6 +53,15 @@ class xOdeFuncInXAndU(nn.Module):  # noqa: N801  (reference class name, train_ut
         return self.linear_tanh_stack(torch.cat((x, self.u), 1))
 
 
+# method -> (ctx option "node_method", a_ij rows below the diagonal, b_i): csrc/nlc_node_rk.h.  One sub-step of width h:
+# Y_i = y + h sum_j a_ij k_j, k_i = f(Y_i), y' = y + h sum_i b_i k_i
+RK_TABLEAUS = {
+    "euler": (0, ((),), (1.0,)),
+    "midpoint": (1, ((), (0.5,)), (0.0, 1.0)),
+    "rk4": (2, ((), (1.0 / 3.0,), (-1.0 / 3.0, 1.0), (1.0, -1.0, 1.0)), (0.125, 0.375, 0.375, 0.125)),
+}
+
+
 class NODE(HipModelMirror, nn.Module):
     _dyn_id = _lib.DYN_NODE
     _BLOB_KEYS = [f"x_ode_func_in_x_and_u.linear_tanh_stack.{i}.{p}" for i in (0, 2, 4) for p in ("weight", "bias")]
@@ -72,9 +87,7 @@ class NODE(HipModelMirror, nn.Module):
         dt=0.05,
     ):
         super().__init__()
-        if method != "euler":
-            raise NotImplementedError("NODE on the HIP path integrates with the fixed-grid Euler solver only "
-                                      "(config.py:40 node_method='euler')")
+        self._tableau(method)
         self.x_ode_func_in_x_and_u = xOdeFuncInXAndU(
             state_dim=state_dim, action_dim=action_dim, augment_dim=augment_dim, nhidden=hidden_units
         )
@@ -99,9 +112,27 @@ class NODE(HipModelMirror, nn.Module):
             method=ref.method, augment_dim=ref.augment_dim, action_high=ref.action_high,
         )._take_over(ref)
 
+    @staticmethod
+    def _tableau(method):
+        if method not in RK_TABLEAUS:
+            raise NotImplementedError(f"NODE integrates with the fixed-grid solvers {sorted(RK_TABLEAUS)} only "
+                                      f"(config.py:40 node_method='euler'); got method={method!r}")
+        return RK_TABLEAUS[method]
+
+    @property
+    def stages(self):
+        """ODE-function evaluations per sub-step of ``method``."""
+        return len(self._tableau(self.method)[2])
+
     # ------------------------------------------------------------------ HIP plumbing
+    _weights_key_names = ("normalize", "normalize_time", "step_size", "method")
+
     def _weights_key_extra(self):
-        return (self.normalize, self.normalize_time, self.step_size)
+        return (self.normalize, self.normalize_time, self.step_size, self.method)
+
+    def _ctx_options(self):
+        """The solver travels beside the descriptor (``nlc_node_desc`` keeps its size): ctx option ``node_method``."""
+        return {"node_method": self._tableau(self.method)[0]}
 
     def model_desc(self):
         d = self.state_dim
@@ -114,7 +145,8 @@ class NODE(HipModelMirror, nn.Module):
 
     def _forward_train(self, in_batch_obs, in_batch_action, ts_pred):
         """Grad-mode forward for training: the reference's op sequence (``train_utils.py:696-724``) with the restated
-        fixed-grid Euler ``odeint`` in torch ops on PyTorch-ROCm; the HIP kernels serve inference / planning."""
+        fixed-grid ``odeint`` (``method``'s tableau) in torch ops on PyTorch-ROCm; the HIP kernels serve inference /
+        planning and the fused trainers."""
         dev = self._train_device()
         obs, act = in_batch_obs.to(dev), in_batch_action.to(dev)
         desc = self.model_desc()
@@ -129,8 +161,17 @@ class NODE(HipModelMirror, nn.Module):
         niters = int(math.ceil(t_end / self.step_size + 1))
         grid = [k * self.step_size for k in range(niters)]
         grid[-1] = t_end
+        _, a, b = self._tableau(self.method)
+        f = self.x_ode_func_in_x_and_u
         for k in range(niters - 1):
-            x = x + (grid[k + 1] - grid[k]) * self.x_ode_func_in_x_and_u(None, x)
+            h = grid[k + 1] - grid[k]
+            if len(b) == 1:
+                x = x + h * f(None, x)
+                continue
+            ks = []
+            for row in a:
+                ks.append(f(None, x + h * sum(aij * kj for aij, kj in zip(row, ks)) if row else x))
+            x = x + h * sum(bi * ki for bi, ki in zip(b, ks))
         return x[:, : x.shape[-1] - self.augment_dim].to(in_batch_obs.device)
 
     def forward(self, in_batch_obs, in_batch_action, ts_pred):

@@ -439,7 +439,7 @@ class MPPIDelay:
                 if self._buf is not None:  # nlc_set_model drops the planner configuration: carry U over
                     self._pending_U, self._buf, self._B = self.U, None, None
                 try:
-                    self._model_key = model.upload(self.ctx)
+                    self._model_key = model.sync_to(self.ctx)
                 except _lib.NlcError as err:
                     if err.code != _lib.NLC_ERR_UNSUPPORTED:
                         raise

@@ -250,7 +250,13 @@ class _FusedTrainer:
                 return f"buffer {k}"
         if len(bb) != len(ba):
             return "its set of buffers"
-        if tuple(a._weights_key_extra()) != tuple(b._weights_key_extra()):
+        ea, eb = tuple(a._weights_key_extra()), tuple(b._weights_key_extra())
+        if ea != eb:
+            # a mirror that names its settings (NODE: the solver ``method`` among them) has the first differing one named
+            names = getattr(a, "_weights_key_names", ())
+            which = next((i for i, (x, y) in enumerate(zip(ea, eb)) if x != y), None)
+            if which is not None and which < len(names):
+                return f"its settings (_weights_key_extra()): {names[which]} ({eb[which]!r} against {ea[which]!r})"
             return "its settings (_weights_key_extra())"
         return None
 
@@ -281,7 +287,7 @@ class _FusedTrainer:
             return self._model_key[1]
         why = None
         try:
-            self.model.upload(self._ctx)
+            self.model.sync_to(self._ctx)
         except _lib.NlcError as err:
             if err.code != _lib.NLC_ERR_UNSUPPORTED:
                 raise
@@ -984,8 +990,10 @@ class NODETrainer(_FusedTrainer):
     row (``train_utils.py:719``; what ``model.forward`` does), which is why the reference trains NODE at batch size 1.
     ``row_times=True`` integrates each row to its own time; on the grad-mode fallback that loops the rows one by one.
 
-    A row takes at most ``MAX_SUBSTEPS`` Euler sub-steps.  The first call with a given ``ts`` tensor reads it once on the host
-    and raises ``ValueError`` if a time is not positive or needs more; after that the tensor is not read again."""
+    A row takes at most ``MAX_SUBSTEPS`` evaluations of the ODE function: that many Euler sub-steps, half as many midpoint
+    and a quarter as many rk4 sub-steps (``max_substeps()``).  The first call with a given ``ts`` tensor reads it once on the
+    host and raises ``ValueError`` if a time is not positive or needs more; after that the tensor is not read again (a changed
+    ``model.method`` reads it again)."""
 
     _entries = ("nlc_node_train_group_workspace_bytes", "nlc_node_train_group_loss_grad", "nlc_node_train_group_step")
     _eval_entries = ("nlc_node_train_group_eval_workspace_bytes", "nlc_node_train_group_eval")
@@ -996,10 +1004,9 @@ class NODETrainer(_FusedTrainer):
         self._ts_seen = {}
         self._init([model], lr, betas, eps, weight_decay, clip_grad_norm)
 
-    def _unsupported(self, model):
-        if getattr(model, "method", "euler") != "euler":
-            return f"method {model.method!r} has no fused training kernels (the fixed-grid Euler solver has)"
-        return None
+    def max_substeps(self):
+        """Sub-steps a row may take under the model's current ``method`` (csrc/nlc_train_node.h node_train_max_sub)."""
+        return self.MAX_SUBSTEPS // self.model.stages
 
     def _extra_args(self):
         return (int(self.row_times),)
@@ -1008,14 +1015,15 @@ class NODETrainer(_FusedTrainer):
         """One host read per dataset tensor: every time positive and within ``MAX_SUBSTEPS`` sub-steps of the model's grid
         (torchdiffeq's ``ceil(t / step_size + 1)`` points), else ValueError -- before any launch."""
         ts = torch.as_tensor(ts)
-        key = (ts.data_ptr(), ts._version, ts.numel(), self._model_key[0])
+        key = (ts.data_ptr(), ts._version, ts.numel(), self._model_key[0], self.model.method)
         if key in self._ts_seen:
             return
         t_end = ts.detach().to(torch.float64).reshape(-1) / self.model._time_div()
-        ok = (t_end > 0) & (torch.ceil(t_end / float(self.model.step_size) + 1.0) <= self.MAX_SUBSTEPS + 1)
+        cap = self.max_substeps()
+        ok = (t_end > 0) & (torch.ceil(t_end / float(self.model.step_size) + 1.0) <= cap + 1)
         if not bool(ok.all()):
-            raise ValueError(f"{self._name}: every prediction time must be positive and need at most {self.MAX_SUBSTEPS} "
-                             f"Euler sub-steps of {self.model.step_size} (after normalize_time); ts holds one that does not")
+            raise ValueError(f"{self._name}: every prediction time must be positive and need at most {cap} "
+                             f"{self.model.method} sub-steps of {self.model.step_size} (after normalize_time); ts holds one that does not")
         if len(self._ts_seen) >= 64:
             self._ts_seen.clear()
         self._ts_seen[key] = True

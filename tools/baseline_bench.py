@@ -1,14 +1,19 @@
 """Planning steps/s with a baseline model as the dynamics -- MODEL=dtrnn: the Delta-t RNN (train_utils.py:589-631,
 rnn_hidden_units=160); MODEL=node: the NODE (train_utils.py:637-738, node_hidden_units=270, augment 1, Euler) -- at
 BASELINE configs[1] sizes (cartpole, K=16384, T=40, B=4), device Philox noise, plus the CPU oracle on a bounded
-sample.  Prints one JSON line (profiles/r1j_dtrnn_planner.json, profiles/r1j_node_planner.json)."""
-import json, os, sys, time
+sample.  --node-method euler | midpoint | rk4 picks the NODE's fixed-grid solver.  Prints one JSON line
+(profiles/r1j_dtrnn_planner.json, profiles/r1j_node_planner.json)."""
+import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import neurallaplacecontrol_amd as nlc
 from oracle import envs as oenvs, mppi as omppi, nl_model as onl, node_model as onode, rnn_model as ornn
 
 MODEL = os.environ.get("MODEL", "dtrnn")
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--node-method", choices=["euler", "midpoint", "rk4"], default="euler", help="MODEL=node: the fixed-grid solver")
+_ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle sample")
+ARGS = _ap.parse_args()
 
 env, K, T, B = "oderl-cartpole", int(os.environ.get("K", 16384)), 40, 4
 H = int(os.environ.get("H", 160 if MODEL == "dtrnn" else 270))
@@ -25,11 +30,17 @@ if MODEL == "dtrnn":
 else:
     sd = onode.make_synthetic_state_dict(0, d, nu, H, 1, st["state_std"], [A / 2.0])
     model = nlc.NODE(d, nu, d, hidden_units=H, state_mean=np.zeros(d), state_std=np.ones(d), action_mean=np.array([0]),
-                     action_std=np.array([1.0]), normalize=True, normalize_time=True, method="euler",
+                     action_std=np.array([1.0]), normalize=True, normalize_time=True, method=ARGS.node_method,
                      augment_dim=1).double()
-    make_dyn, kern = onode.make_dynamics, "node_rollout_kernel"
+    if ARGS.node_method == "euler":
+        make_dyn = onode.make_dynamics
+    else:  # the CPU restatement of the other solvers is the tests' (tests/node_rk_reference.py)
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import node_rk_reference
+        make_dyn = lambda sd_: node_rk_reference.make_dynamics(sd_, ARGS.node_method)  # noqa: E731
+    kern = "node_rollout_kernel"
     HT = 4 if H <= 64 else (8 if H <= 128 else 17)
-    nsub = len(onode.euler_substeps(0.05 / (float(sd["dt"]) * 8.0)))
+    nsub = len(onode.euler_substeps(0.05 / (float(sd["dt"]) * 8.0))) * model.stages  # evaluations of the ODE function
     mfma_per_tile_task = nsub * (3 * HT + 4 * HT * HT + 4 * HT)  # per 16 samples and horizon step
     tile_tasks = K * T / 16
 model.load_state_dict(sd)
@@ -54,17 +65,20 @@ enc_ms = prof[kern]
 # CPU oracle (reference op sequence) on a bounded sample: K/16 samples of the same problem
 Kc = max(K // 16, 64)
 torch.set_num_threads(min(32, os.cpu_count() or 1))
-dyn, cost = make_dyn(sd), oenvs.RUNNING_COST[env]
-U = torch.zeros(T, nu, dtype=torch.float64)
-noise = torch.randn(Kc, T, nu, dtype=torch.float64)
-t0 = time.perf_counter()
-omppi.mppi_command(U, torch.as_tensor(state), ab, noise, dyn, cost, d, torch.inverse(nlc.noise_sigma(nu)), 1.0, A,
-                   torch.tensor(-A), torch.tensor(A))
-cpu_s = time.perf_counter() - t0
+cpu_s = float("nan")
+if not ARGS.no_cpu:
+    dyn, cost = make_dyn(sd), oenvs.RUNNING_COST[env]
+    U = torch.zeros(T, nu, dtype=torch.float64)
+    noise = torch.randn(Kc, T, nu, dtype=torch.float64)
+    t0 = time.perf_counter()
+    omppi.mppi_command(U, torch.as_tensor(state), ab, noise, dyn, cost, d, torch.inverse(nlc.noise_sigma(nu)), 1.0, A,
+                       torch.tensor(-A), torch.tensor(A))
+    cpu_s = time.perf_counter() - t0
 print(json.dumps({
     "metric": "MPPI planning steps/sec, %s dynamics (hidden_units=%d)" % ({"dtrnn": "Delta-t RNN", "node": "NODE"}[MODEL], H), "value": 1.0 / dt,
     "unit": "planning steps/s", "ms_per_step": dt * 1e3, "dtype": "f64",
-    "config": {"workload": f"oderl-cartpole, K={K}, H=40, action_buffer_size=4, {MODEL} hidden {H}", "noise": "device Philox"},
+    "config": {"workload": f"oderl-cartpole, K={K}, H=40, action_buffer_size=4, {MODEL} hidden {H}", "noise": "device Philox",
+               **({"node_method": ARGS.node_method} if MODEL == "node" else {})},
     "kernels_avg_ms": prof,
     "roofline": {"bound": "mfma", "kernel": kern, "avg_launch_ms": enc_ms, "flops_per_launch": flops,
                  "achieved": flops / enc_ms / 1e9, "peak": 78.6, "unit": "TFLOP/s", "frac": flops / enc_ms / 1e9 / 78.6},

@@ -84,6 +84,7 @@ from oracle import nl_model as onl  # noqa: E402
 ENV, D, NU, H, S, B = "oderl-cartpole", 5, 1, 128, 17, 4
 RNN_H = 160  # rnn_hidden_units, config.py:43
 NODE_H, NODE_AUG = 270, 1  # node_hidden_units, node_augment_dim, config.py:41-42
+NODE_METHOD = "euler"  # --node-method: the NODE's fixed-grid solver
 MODEL = "nl"
 ILT = "fourier"  # --ilt-algorithm (NL model)
 DEHOOG_FUSED = False  # --dehoog-fused: NL trainers are built with dehoog="fused"
@@ -119,7 +120,8 @@ def make_model(seed=0):
 
         sd = ond.make_synthetic_state_dict(seed, D, NU, NODE_H, NODE_AUG, st["state_std"], None)
         m = nlc.NODE(D, NU, D, hidden_units=NODE_H, state_mean=np.zeros(D), state_std=np.ones(D), action_mean=np.array([0]),
-                     action_std=np.array([1.0]), normalize=True, normalize_time=True, augment_dim=NODE_AUG).double()
+                     action_std=np.array([1.0]), normalize=True, normalize_time=True, augment_dim=NODE_AUG,
+                     method=NODE_METHOD).double()
         m.load_state_dict(sd)
         return m.to("cuda")
     # (de Hoog: weights whose terms sample a transform -- the table is ill-conditioned on a random network's)
@@ -397,7 +399,7 @@ def flops_per_iter(bs):
 
 
 def main():
-    global MODEL, ILT, S, DEHOOG_FUSED
+    global MODEL, ILT, S, DEHOOG_FUSED, NODE_METHOD
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 256])
     ap.add_argument("--ref-iters", type=int, default=200)
@@ -425,9 +427,14 @@ def main():
     ap.add_argument("--fit-iters", type=int, default=2000, help="--fit: iterations per timed run (one epoch)")
     ap.add_argument("--eval-every", type=int, default=100, help="--fit: iterations between checks")
     ap.add_argument("--members", action="store_true", help="time a group with per-member learning rates against the scalar group")
+    ap.add_argument("--node-method", choices=["euler", "midpoint", "rk4"], default="euler",
+                    help="--model node: the fixed-grid solver (profiles/train_bench_node_rk.json: --batches 1 --only run)")
     ap.add_argument("--child", nargs=2, metavar=("BATCH", "VARIANT"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     MODEL, ILT, S, DEHOOG_FUSED = args.model, args.ilt_algorithm, args.terms, args.dehoog_fused
+    NODE_METHOD = args.node_method
+    if MODEL == "node" and NODE_METHOD != "euler":
+        WORKLOADS["node"] = WORKLOADS["node"].replace("Euler", NODE_METHOD)
     if MODEL == "nl" and (ILT, S) != ("fourier", 17):
         WORKLOADS["nl"] = f"NeuralLaplaceModel training step, cartpole d=5 h=128 {ILT} S={S} B=4, float64"
     torch.manual_seed(0)
@@ -454,7 +461,8 @@ def main():
         cmd = [sys.executable, os.path.abspath(__file__), "--model", MODEL, "--ilt-algorithm", ILT, "--terms", str(S),
                "--ref-iters", str(args.ref_iters), "--step-iters",
                str(args.step_iters), "--run-iters", str(args.run_iters), "--warmup", str(args.warmup), "--repeats",
-               str(repeats or args.repeats), *(["--dehoog-fused"] if DEHOOG_FUSED else []), "--child", str(bs), variant]
+               str(repeats or args.repeats), *(["--dehoog-fused"] if DEHOOG_FUSED else []),
+               *(["--node-method", NODE_METHOD] if NODE_METHOD != "euler" else []), "--child", str(bs), variant]
         out = subprocess.run(cmd, timeout=args.step_timeout, check=True, capture_output=True, text=True).stdout
         return json.loads([ln for ln in out.splitlines() if ln.startswith("RESULT ")][-1][7:])
 
@@ -560,6 +568,8 @@ def main():
         return
 
     res = {"workload": WORKLOADS[MODEL], "device": torch.cuda.get_device_name(0), "batches": {}}
+    if MODEL == "node":
+        res["node_method"] = NODE_METHOD
     if MODEL == "nl":
         res["ilt_algorithm"], res["terms"] = ILT, S
     for bs in args.batches:
