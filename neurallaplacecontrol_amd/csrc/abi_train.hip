@@ -26,8 +26,7 @@ enum Family { kFamNl, kFamRnn, kFamNode };
 struct Plan {
   int g, S, nblk, chunks, d;
   int64_t P, A, ntiles;
-  int64_t off[kTensors + 1];
-  int cstart[kTensors + 1];
+  ChunkTable ct;         // the blob's tensors and their reduce / Adam chunks
   TrainWsLayout ws;      // one member's workspace region
   GroupStrides gs;  // for a group whose gradient lives in the workspace (a step); loss_grad overrides gs.grad
   int M;
@@ -36,12 +35,12 @@ struct Plan {
   DehoogWsLayout dh;  // (set by plan_group: the ILT arrays hold the M members back to back)
 };
 
-// workgroups, partial size and the reduce / Adam chunking of a call with N rows, once p.off, p.A and p.d are set
+// workgroups, partial size and the reduce / Adam chunking of a call with N rows, once p.ct.off, p.A and p.d are set
 void plan_rows(Plan& p, int64_t N) {
-  p.P = p.off[kTensors];
+  p.P = p.ct.off[kTensors];
   p.ntiles = (N + kRows - 1) / kRows;
   p.nblk = (int)(p.ntiles < kMaxBlocks ? p.ntiles : kMaxBlocks);
-  p.chunks = chunk_starts(p.off, p.cstart);
+  p.chunks = chunk_starts(p.ct);
   p.ws = train_ws_layout(p.nblk, p.P, p.A, p.chunks);
 }
 
@@ -62,7 +61,7 @@ Plan plan_of(const nlc_ctx* c, int64_t N) {
   p.g = md.h / 2;
   p.S = md.ilt.terms;
   p.d = md.d;
-  blob_offsets(md.d, md.nin, p.g, md.h, p.S, p.off);
+  blob_offsets(md.d, md.nin, p.g, md.h, p.S, p.ct.off);
   p.A = act_layout(md.d, md.nin, p.g, md.h, p.S, kMaxB).total;
   p.dehoog = nl_dehoog(c);
   plan_rows(p, N);
@@ -73,7 +72,7 @@ Plan rnn_plan_of(const nlc_ctx* c, int64_t N) {
   Plan p{};
   const nlc_rnn_desc& rd = c->rnnm.rd;
   p.d = rd.d;
-  rnn_blob_offsets(rd.d, rd.nin, rd.hidden, rd.time_input, p.off);
+  rnn_blob_offsets(rd.d, rd.nin, rd.hidden, rd.time_input, p.ct.off);
   p.A = rnn_act_layout(rd.nin, rd.hidden, kMaxB).total;
   plan_rows(p, N);
   return p;
@@ -85,7 +84,7 @@ Plan node_plan_of(const nlc_ctx* c, int64_t N) {
   Plan p{};
   const nlc_node_desc& nd = c->nodem.nd;
   p.d = nd.d;
-  node_blob_offsets(nd.d, nd.augment_dim, nd.nu, nd.hidden, p.off);
+  node_blob_offsets(nd.d, nd.augment_dim, nd.nu, nd.hidden, p.ct.off);
   p.A = node_act_layout(nd.hidden, nd.d + nd.augment_dim + nd.nu).total;
   plan_rows(p, N);
   return p;
@@ -108,6 +107,9 @@ WsPtrs ws_ptrs(const Plan& p, void* base) {
   double* b = (double*)base;
   return WsPtrs{b + p.ws.partial, b + p.ws.tile_loss, b + p.ws.act, b + p.ws.grad, b + p.ws.sq, b};
 }
+
+// whether the family's kernels read ts: all but an RNN without time input
+bool need_ts(const nlc_ctx* c, Family fam) { return fam == kFamRnn ? c->rnnm.rd.time_input != 0 : true; }
 
 // the NL model the kernels take: uploaded, and with one of the three ILT algorithms they are written for (fixed Talbot /
 // Stehfest: fixed nodes and weights from linear_tables, the <true> instance of train_fwd_bwd_kernel); with option
@@ -161,10 +163,7 @@ int reduce(nlc_ctx* c, int64_t N, double* grad, int64_t grad_stride, double* los
   r.grad = grad;
   r.sq = w.sq;
   r.loss = loss;
-  for (int i = 0; i <= kTensors; ++i) {
-    r.off[i] = p.off[i];
-    r.cstart[i] = p.cstart[i];
-  }
+  r.ct = p.ct;
   r.gs = p.gs;
   r.gs.grad = grad_stride;
   ProfScope ps(c, "train_reduce_kernel");
@@ -172,10 +171,21 @@ int reduce(nlc_ctx* c, int64_t N, double* grad, int64_t grad_stride, double* los
   return NLC_OK;
 }
 
+// the scalars of torch.optim.Adam's foreach step that a group shares at one step count (python floats there: beta ** step,
+// bc2 ** 0.5); step_size needs a learning rate, see adam and adam_members
+struct StepScalars {
+  double omb1, beta2, omb2, eps, bc1, bc2_sqrt;
+};
+StepScalars step_scalars(const nlc_train_desc* desc, int64_t step) {
+  const double bc1 = 1.0 - std::pow(desc->beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(desc->beta2, (double)step);
+  return StepScalars{1.0 - desc->beta1, desc->beta2, 1.0 - desc->beta2, desc->eps, bc1, std::pow(bc2, 0.5)};
+}
+
 // clip_grad_norm_ + Adam.step() on the summed gradients in the workspace, per member
 int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, double* v, int64_t step, double* gradnorm,
          const Plan& p, const WsPtrs& w) {
-  // the host-side scalars of torch.optim.Adam's foreach step (python floats there: beta ** step, (lr / bc1) * -1, bc2 ** 0.5)
+  const StepScalars s = step_scalars(desc, step);
   AdamArgs a{};
   a.params = params;
   a.m = m;
@@ -183,20 +193,10 @@ int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, doub
   a.grad = w.grad;
   a.sq = w.sq;
   a.max_norm = desc->max_grad_norm;
-  const double bc1 = 1.0 - std::pow(desc->beta1, (double)step);
-  const double bc2 = 1.0 - std::pow(desc->beta2, (double)step);
-  a.k.wd = desc->weight_decay;
-  a.k.omb1 = 1.0 - desc->beta1;
-  a.k.beta2 = desc->beta2;
-  a.k.omb2 = 1.0 - desc->beta2;
-  a.k.step_size = (desc->lr / bc1) * -1.0;
-  a.k.bc2_sqrt = std::pow(bc2, 0.5);
-  a.k.eps = desc->eps;
+  // step_size on the host, as python's (lr / bc1) * -1
+  a.k = AdamScalars{desc->weight_decay, s.omb1, s.beta2, s.omb2, (desc->lr / s.bc1) * -1.0, s.bc2_sqrt, s.eps};
   a.gradnorm = gradnorm;
-  for (int i = 0; i <= kTensors; ++i) {
-    a.off[i] = p.off[i];
-    a.cstart[i] = p.cstart[i];
-  }
+  a.ct = p.ct;
   a.gs = p.gs;
   ProfScope ps(c, "train_adam_kernel");
   NLC_HIP(c, launch_train_adam(a, p.M, c->stream));
@@ -204,9 +204,11 @@ int adam(nlc_ctx* c, const nlc_train_desc* desc, double* params, double* m, doub
 }
 
 // the same launch with lr, weight decay, clip norm and the active flag per member, from device arrays (kernels_train_members.hip);
-// desc gives the betas and eps, its lr / weight_decay / max_grad_norm are not read
+// desc gives the betas and eps, its lr / weight_decay / max_grad_norm are not read; step_size is formed on the device, as
+// -(lr[m] / bc1) (nlc_train_members.h member_step_size: the bits of the host's expression above)
 int adam_members(nlc_ctx* c, const nlc_train_desc* desc, const nlc_train_members* mem, double* params, double* m, double* v,
                  int64_t step, double* gradnorm, const Plan& p, const WsPtrs& w) {
+  const StepScalars s = step_scalars(desc, step);
   MembersAdamArgs a{};
   a.params = params;
   a.m = m;
@@ -217,18 +219,14 @@ int adam_members(nlc_ctx* c, const nlc_train_desc* desc, const nlc_train_members
   a.wd = mem->wd_dev;
   a.max_norm = mem->max_norm_dev;
   a.active = mem->active_dev;
-  const double bc2 = 1.0 - std::pow(desc->beta2, (double)step);
-  a.omb1 = 1.0 - desc->beta1;
-  a.beta2 = desc->beta2;
-  a.omb2 = 1.0 - desc->beta2;
-  a.eps = desc->eps;
-  a.bc1 = 1.0 - std::pow(desc->beta1, (double)step);
-  a.bc2_sqrt = std::pow(bc2, 0.5);
+  a.omb1 = s.omb1;
+  a.beta2 = s.beta2;
+  a.omb2 = s.omb2;
+  a.eps = s.eps;
+  a.bc1 = s.bc1;
+  a.bc2_sqrt = s.bc2_sqrt;
   a.gradnorm = gradnorm;
-  for (int i = 0; i <= kTensors; ++i) {
-    a.off[i] = p.off[i];
-    a.cstart[i] = p.cstart[i];
-  }
+  a.ct = p.ct;
   a.gs = p.gs;
   ProfScope ps(c, "train_adam_members_kernel");
   NLC_HIP(c, launch_train_adam_members(a, p.M, c->stream));
@@ -259,7 +257,7 @@ void fill_call(Args& a, const Desc& m, int B, const Batch& b, const Plan& p) {
   fill_norm(a.norm, m);
   a.batch = b;
   a.ntiles = (decltype(a.ntiles))p.ntiles;
-  for (size_t i = 0; i < std::size(a.off); ++i) a.off[i] = p.off[i];
+  for (size_t i = 0; i < std::size(a.off); ++i) a.off[i] = p.ct.off[i];
   a.gs = p.gs;
 }
 
@@ -439,8 +437,7 @@ int group_loss_grad(nlc_ctx* c, Family fam, int M, int64_t data_rows, const doub
                     bool more_null = false) {
   if (int rc = check_call(c, fam, M, data_rows, N, B)) return rc;
   if (step && *step < 1) return fail(c, NLC_ERR_BAD_ARG, "Adam step count must be >= 1");
-  const bool need_ts = fam == kFamRnn ? c->rnnm.rd.time_input != 0 : true;
-  if (!params || !obs || !window || (!ts && need_ts) || !target || !idx || (!step && !grad) || !loss || !ws || more_null)
+  if (!params || !obs || !window || (!ts && need_ts(c, fam)) || !target || !idx || (!step && !grad) || !loss || !ws || more_null)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
   Plan& p = *plan;
@@ -498,32 +495,33 @@ int group_eval_entry(nlc_ctx* c, Family fam, int M, int64_t data_rows, const dou
   if (!c) return NLC_ERR_BAD_ARG;
   NLC_GUARD_BEGIN
   if (int rc = check_call(c, fam, M, data_rows, N, B)) return rc;
-  const bool need_ts = fam == kFamRnn ? c->rnnm.rd.time_input != 0 : true;
-  if (!params || !obs || !window || (!ts && need_ts) || !target || !loss || !ws)
+  if (!params || !obs || !window || (!ts && need_ts(c, fam)) || !target || !loss || !ws)
     return fail(c, NLC_ERR_BAD_ARG, "NULL device pointer");
   NLC_HIP(c, hipSetDevice(c->device));
-  if (fam == kFamNl && nl_dehoog(c)) {
-    // launches 1 .. 3 of the training step on its own workspace layout (the forward tapes needlessly here), then the
-    // evaluation's reduction over the member's tile losses
-    Plan p = family_plan(c, fam, N);
+  Plan p = family_plan(c, fam, N);
+  const Batch b{params, obs, window, ts, target, idx, N};
+  // the forward launch, and where it left member 0's tile losses: how many, and the doubles to the next member's
+  EvalReduceArgs r{nullptr, 0, N, 0, p.d, loss};
+  if (p.dehoog) {
+    // launches 1 .. 3 of the training step on its own workspace layout (the forward tapes needlessly here)
     plan_group(p, M, N, data_rows);
     const WsPtrs w = ws_ptrs(p, ws);
-    const Batch b{params, obs, window, ts, target, idx, N};
     if (int rc = nl_dehoog_launches(c, b, B, p, w, false)) return rc;
-    EvalReduceArgs r{w.tile_loss, p.nblk, N, p.ws.total, p.d, loss};
-    ProfScope ps(c, "eval_reduce_kernel");
-    NLC_HIP(c, launch_eval_reduce(r, M, c->stream));
-    return NLC_OK;
+    r.tile_loss = w.tile_loss;
+    r.ntiles = p.nblk;
+    r.ws = p.ws.total;
+  } else {
+    const EvalWsLayout w = eval_ws_layout(N);
+    p.M = M;
+    p.row_times = row_times;
+    p.gs = GroupStrides{p.P, w.total, 0, N, data_rows};
+    double* tile_loss = (double*)ws + w.tile_loss;
+    if (int rc = (fam == kFamRnn ? rnn_eval : fam == kFamNode ? node_eval : nl_eval)(c, b, B, p, tile_loss)) return rc;
+    r.tile_loss = tile_loss;
+    r.ntiles = w.ntiles;
+    r.ws = w.total;
   }
-  const EvalWsLayout w = eval_ws_layout(N);
-  Plan p = family_plan(c, fam, N);
-  p.M = M;
-  p.row_times = row_times;
-  p.gs = GroupStrides{p.P, w.total, 0, N, data_rows};
-  double* tile_loss = (double*)ws + w.tile_loss;
-  const Batch b{params, obs, window, ts, target, idx, N};
-  if (int rc = (fam == kFamRnn ? rnn_eval : fam == kFamNode ? node_eval : nl_eval)(c, b, B, p, tile_loss)) return rc;
-  EvalReduceArgs r{tile_loss, w.ntiles, N, w.total, p.d, loss};
+  // one reduction over each member's tile losses
   ProfScope ps(c, "eval_reduce_kernel");
   NLC_HIP(c, launch_eval_reduce(r, M, c->stream));
   return NLC_OK;

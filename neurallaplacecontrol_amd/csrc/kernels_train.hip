@@ -17,7 +17,9 @@
 //                         in state_dict blob order.
 //   train_reduce_kernel   partials summed in workgroup order (no atomics: bit-reproducible), per-chunk sums of squares,
 //                         the loss.
-//   train_adam_kernel     per-tensor norms, their norm, clip_grad_norm_'s coefficient, torch.optim.Adam's update.
+//   train_adam_kernel     per-tensor norms, their norm, clip_grad_norm_'s coefficient, torch.optim.Adam's update: clip_adam
+//                         (nlc_train_dev.h) with the settings of its arguments.
+// The reduce and Adam grids are the chunks of nlc_train.h's ChunkTable, walked by chunk_range.
 //
 // Elementary functions: gates and hidden activations use nlc_math.h's sigmoid_d / tanh_d (<= 4 ulp against libm on the
 // whole line, tests/test_math_host.py); the sphere map's tanh is tanh_d; tan / sin / cos / exp / atan2 / asin of the query
@@ -248,30 +250,21 @@ __global__ __launch_bounds__(kThreads) void train_fwd_bwd_kernel(const TrainArgs
 }
 
 __global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs a) {
-  __shared__ double red[kThreads];
   const int b = blockIdx.x;
   const int64_t mi = blockIdx.y;  // member of the group: its own partials, tile losses, gradient, chunk sums and loss
   const double* partial = a.partial + mi * a.gs.ws;
   double* grad = a.grad + mi * a.gs.grad;
-  int t = 0;
-  while (t + 1 < kTensors && a.cstart[t + 1] <= b) ++t;
-  const int64_t e0 = a.off[t] + (int64_t)(b - a.cstart[t]) * kChunk;
-  const int64_t e1 = e0 + kChunk < a.off[t + 1] ? e0 + kChunk : a.off[t + 1];
+  const ChunkRange r = chunk_range(a.ct, b);
   double s = 0.0;
-  for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
+  for (int64_t e = r.e0 + threadIdx.x; e < r.e1; e += kThreads) {
     double gsum = 0.0;
     for (int k = 0; k < a.nblk; ++k) gsum += partial[(int64_t)k * a.P + e];
     grad[e] = gsum;
     s += gsum * gsum;
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = kThreads / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
+  s = block_sum(s);
   if (threadIdx.x == 0) {
-    a.sq[mi * a.gs.ws + b] = red[0];
+    a.sq[mi * a.gs.ws + b] = s;
     if (b == 0) {
       const double* tile_loss = a.tile_loss + mi * a.gs.ws;
       double l = 0.0;
@@ -282,42 +275,7 @@ __global__ __launch_bounds__(kThreads) void train_reduce_kernel(const ReduceArgs
 }
 
 __global__ __launch_bounds__(kThreads) void train_adam_kernel(const AdamArgs a) {
-  __shared__ double coef_s;
-  const int b = blockIdx.x;
-  const int64_t mi = blockIdx.y;  // member of the group: its own chunk sums, clip coefficient and slices of params / m / v
-  const double* sq = a.sq + mi * a.gs.ws;
-  const double* grad = a.grad + mi * a.gs.grad;
-  double* params = a.params + mi * a.gs.params;
-  double* mom = a.m + mi * a.gs.params;
-  double* var = a.v + mi * a.gs.params;
-  int t = 0;
-  while (t + 1 < kTensors && a.cstart[t + 1] <= b) ++t;
-  if (threadIdx.x == 0) {
-    // clip_grad_norm_: total = || (||g_0||, ..., ||g_15||) ||, every workgroup from the same sums in the same order
-    double tot2 = 0.0;
-    for (int i = 0; i < kTensors; ++i) {
-      double s = 0.0;
-      for (int c = a.cstart[i]; c < a.cstart[i + 1]; ++c) s += sq[c];
-      const double n = sqrt(s);
-      tot2 += n * n;
-    }
-    const double total = sqrt(tot2);
-    coef_s = a.max_norm > 0.0 ? clip_coef(a.max_norm, total) : 1.0;
-    if (b == 0 && a.gradnorm) a.gradnorm[mi] = total;
-  }
-  __syncthreads();
-  const double coef = coef_s;
-  const int64_t e0 = a.off[t] + (int64_t)(b - a.cstart[t]) * kChunk;
-  const int64_t e1 = e0 + kChunk < a.off[t + 1] ? e0 + kChunk : a.off[t + 1];
-  for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) {
-    double gv = grad[e];
-    if (a.max_norm > 0.0) gv = gv * coef;
-    double p = params[e], mm = mom[e], vv = var[e];
-    adam_element(&p, &mm, &vv, gv, a.k);
-    params[e] = p;
-    mom[e] = mm;
-    var[e] = vv;
-  }
+  clip_adam(a.params, a.m, a.v, a.grad, a.sq, a.gradnorm, a.ct, a.gs, a.max_norm, a.k, true);
 }
 
 hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, int M, hipStream_t s) {
@@ -326,11 +284,11 @@ hipError_t launch_train_fwd_bwd(const TrainArgs& a, int nblk, int M, hipStream_t
   return hipGetLastError();
 }
 hipError_t launch_train_reduce(const ReduceArgs& a, int M, hipStream_t s) {
-  hipLaunchKernelGGL(train_reduce_kernel, dim3(a.cstart[kTensors], M), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(train_reduce_kernel, dim3(a.ct.cstart[kTensors], M), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_train_adam(const AdamArgs& a, int M, hipStream_t s) {
-  hipLaunchKernelGGL(train_adam_kernel, dim3(a.cstart[kTensors], M), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(train_adam_kernel, dim3(a.ct.cstart[kTensors], M), dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
 

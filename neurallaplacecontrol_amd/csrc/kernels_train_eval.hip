@@ -352,19 +352,13 @@ __global__ __launch_bounds__(kThreads) void rnn_eval_kernel(const RnnEvalArgs a)
 }
 
 // loss[m] = sum of the member's tile losses / (N d): thread i sums tiles i, i + 256, ... in order, then the 256 sums meet in
-// a fixed tree -- an order the tile count alone decides
+// a fixed tree (block_sum, nlc_train_dev.h) -- an order the tile count alone decides
 __global__ __launch_bounds__(kThreads) void eval_reduce_kernel(const EvalReduceArgs a) {
-  __shared__ double red[kThreads];
   const double* tile_loss = a.tile_loss + (int64_t)blockIdx.y * a.ws;
   double s = 0.0;
   for (int64_t k = threadIdx.x; k < a.ntiles; k += kThreads) s += tile_loss[k];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = kThreads / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.loss[blockIdx.y] = red[0] / ((double)a.N * (double)a.d);
+  s = block_sum(s);
+  if (threadIdx.x == 0) a.loss[blockIdx.y] = s / ((double)a.N * (double)a.d);
 }
 
 // more than 64 KB of dynamic LDS per workgroup needs hipFuncAttributeMaxDynamicSharedMemorySize, per function and per device

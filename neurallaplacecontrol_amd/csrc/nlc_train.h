@@ -10,6 +10,7 @@
 //   Adam (foreach)       g += wd p;  m.lerp_(g, 1 - b1);  v = v*b2 + (1 - b2)*(g*g);  p += -(lr/bc1) * (m / (sqrt(v)/sqrt(bc2) + eps))
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #include "../../include/nlc.h"  // NLC_MAX_D, NLC_MAX_NIN
 #include "nlc_math.h"
@@ -213,6 +214,41 @@ inline int chunk_starts(const int64_t off[kTensors + 1], int cstart[kTensors + 1
   return cstart[kTensors];
 }
 
+// the blob's tensors and their chunks, as the plan and the reduce / Adam launches carry them: the one place the pair is
+// declared, and chunk_range / clip_total_norm the one place it is walked
+struct ChunkTable {
+  int64_t off[kTensors + 1];
+  int cstart[kTensors + 1];  // first chunk of each tensor
+};
+inline int chunk_starts(ChunkTable& c) { return chunk_starts(c.off, c.cstart); }
+
+// chunk b of the grid's x axis: its tensor t and its elements [e0, e1) of the blob
+struct ChunkRange {
+  int t;
+  int64_t e0, e1;
+};
+NLC_HD ChunkRange chunk_range(const ChunkTable& c, int b) {
+  int t = 0;
+  while (t + 1 < kTensors && c.cstart[t + 1] <= b) ++t;
+  const int64_t e0 = c.off[t] + (int64_t)(b - c.cstart[t]) * kChunk;
+  const int64_t e1 = e0 + kChunk < c.off[t + 1] ? e0 + kChunk : c.off[t + 1];
+  return ChunkRange{t, e0, e1};
+}
+
+// clip_grad_norm_'s total = || (||g_0||, ..., ||g_15||) || from the chunk sums of squares sq[0 .. cstart[kTensors]): tensor
+// i's chunks summed in order, its norm squared again as torch does.  An empty tensor adds sqrt(0)^2 = +0, which changes no
+// bit of the sum: a table padded with empty tensors gives the total of the table without them
+NLC_HD double clip_total_norm(const double* sq, const ChunkTable& c) {
+  double tot2 = 0.0;
+  for (int i = 0; i < kTensors; ++i) {
+    double s = 0.0;
+    for (int k = c.cstart[i]; k < c.cstart[i + 1]; ++k) s += sq[k];
+    const double n = sqrt(s);
+    tot2 += n * n;
+  }
+  return sqrt(tot2);
+}
+
 // ---- DeltaTRNN / RNN (kernels_train_rnn.hip): one GRU layer of width H and linear_out over [h_B | obs_n | ts_n]
 constexpr int kRnnTensors = 6;  // W_ih, W_hh, b_ih, b_hh, linear_out.weight, linear_out.bias (nlc_set_rnn_model's order)
 
@@ -333,9 +369,8 @@ struct ReduceArgs {
   double* grad;  // (P) summed gradient
   double* sq;    // (chunks) sum of squares of each chunk
   double* loss;  // 0-dim
-  int64_t off[kTensors + 1];
-  int cstart[kTensors + 1];  // first chunk of each tensor
-  GroupStrides gs;           // partial / tile_loss / sq by ws, grad by grad; loss is [gridDim.y]
+  ChunkTable ct;
+  GroupStrides gs;  // partial / tile_loss / sq by ws, grad by grad; loss is [gridDim.y]
 };
 
 struct AdamArgs {
@@ -345,10 +380,14 @@ struct AdamArgs {
   double max_norm;  // <= 0: no clipping
   AdamScalars k;
   double* gradnorm;  // [gridDim.y]; may be NULL
-  int64_t off[kTensors + 1];
-  int cstart[kTensors + 1];
+  ChunkTable ct;
   GroupStrides gs;  // params / m / v by params, grad by grad, sq by ws
 };
+
+// the table sits where off[] and cstart[] sat: no byte of a kernel argument moved
+static_assert(sizeof(ChunkTable) == 208, "ChunkTable");
+static_assert(sizeof(ReduceArgs) == 312 && offsetof(ReduceArgs, ct) == 64 && offsetof(ReduceArgs, gs) == 272, "ReduceArgs");
+static_assert(sizeof(AdamArgs) == 360 && offsetof(AdamArgs, ct) == 112 && offsetof(AdamArgs, gs) == 320, "AdamArgs");
 
 }  // namespace train
 }  // namespace nlc

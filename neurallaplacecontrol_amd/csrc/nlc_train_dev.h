@@ -1,6 +1,7 @@
 // Device-side pieces the training and evaluation kernels share (kernels_train.hip, kernels_train_rnn.hip,
 // kernels_train_eval.hip): weight / bias gradients as sums over a tile's samples, the layer-0 GRU gate element of the
-// evaluation kernels, the Fourier series' quarter turn, and the launch dispatch over the RNN widths.
+// evaluation kernels, the Fourier series' quarter turn, the fixed-order block sum of the two reduce kernels, the clip + Adam
+// body of the two Adam kernels (kernels_train.hip, kernels_train_members.hip), and the launch dispatch over the RNN widths.
 #pragma once
 #include "nlc_device.h"
 #include "nlc_train.h"
@@ -91,6 +92,52 @@ __device__ __forceinline__ void quarter(double th, int k, double* c, double* cp)
     case 1: *c = -sn; *cp = -cs; break;
     case 2: *c = -cs; *cp = sn; break;
     default: *c = sn; *cp = cs; break;
+  }
+}
+
+// the sum of s over the workgroup's kThreads threads in a fixed tree (pairs i, i + w for w = 128 .. 1), on every thread
+__device__ __forceinline__ double block_sum(double s) {
+  __shared__ double red[kThreads];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// clip_grad_norm_ + Adam.step() of chunk blockIdx.x of member blockIdx.y: what train_adam_kernel and
+// train_adam_members_kernel do once they have the member's settings (params / m / v / grad / sq / gradnorm are member 0's).
+// Every workgroup forms the total norm from the same chunk sums in the same order (clip_total_norm); workgroup 0 reports it.
+// active == false (uniform over the workgroup): the norm is reported, params / m / v are neither read nor written
+__device__ __forceinline__ void clip_adam(double* params, double* m, double* v, const double* grad, const double* sq,
+                                          double* gradnorm, const ChunkTable& ct, const GroupStrides& gs, double max_norm,
+                                          const AdamScalars& k, bool active) {
+  __shared__ double coef_s;
+  const int b = blockIdx.x;
+  const int64_t mi = blockIdx.y;  // member of the group: its own chunk sums, clip coefficient and slices of params / m / v
+  if (threadIdx.x == 0) {
+    const double total = clip_total_norm(sq + mi * gs.ws, ct);
+    coef_s = max_norm > 0.0 ? clip_coef(max_norm, total) : 1.0;
+    if (b == 0 && gradnorm) gradnorm[mi] = total;
+  }
+  if (!active) return;
+  __syncthreads();
+  const double coef = coef_s;
+  grad += mi * gs.grad;
+  params += mi * gs.params;
+  m += mi * gs.params;
+  v += mi * gs.params;
+  const ChunkRange r = chunk_range(ct, b);
+  for (int64_t e = r.e0 + threadIdx.x; e < r.e1; e += kThreads) {
+    double gv = grad[e];
+    if (max_norm > 0.0) gv = gv * coef;
+    double p = params[e], mm = m[e], vv = v[e];
+    adam_element(&p, &mm, &vv, gv, k);
+    params[e] = p;
+    m[e] = mm;
+    v[e] = vv;
   }
 }
 

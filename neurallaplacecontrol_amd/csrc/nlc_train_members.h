@@ -6,6 +6,7 @@
 // A header of its own: the training, evaluation and selection kernels do not include it.  The element math is nlc_train.h's
 // adam_element and clip_coef, called unchanged.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "nlc_train.h"
@@ -49,10 +50,11 @@ struct MembersAdamArgs {
   const int32_t* active;   // [M]; 0: the member's rows of params / m / v are neither read nor written
   double omb1, beta2, omb2, eps, bc1, bc2_sqrt;
   double* gradnorm;  // [M]; may be NULL; written for frozen members too
-  int64_t off[kTensors + 1];
-  int cstart[kTensors + 1];
+  ChunkTable ct;
   GroupStrides gs;  // params / m / v by params, grad by grad, sq by ws
 };
+static_assert(sizeof(MembersAdamArgs) == 376 && offsetof(MembersAdamArgs, ct) == 128 && offsetof(MembersAdamArgs, gs) == 336,
+              "MembersAdamArgs: the table sits where off[] and cstart[] sat");
 
 struct PatienceArgs {
   const int32_t* improved;  // [M]

@@ -41,6 +41,49 @@ void nlc_t_blob_offsets(int d, int nin, int g, int h, int S, long long* out) {
   blob_offsets(d, nin, g, h, S, off);
   for (int i = 0; i <= kTensors; ++i) out[i] = (long long)off[i];
 }
+// rnn_blob_offsets(d, nin, H, time_input): off[0..16] (six tensors, ten empty)
+void nlc_t_rnn_blob_offsets(int d, int nin, int H, int time_input, long long* out) {
+  int64_t off[kTensors + 1];
+  rnn_blob_offsets(d, nin, H, time_input, off);
+  for (int i = 0; i <= kTensors; ++i) out[i] = (long long)off[i];
+}
+static ChunkTable table_of(const long long* off) {
+  ChunkTable c;
+  for (int i = 0; i <= kTensors; ++i) c.off[i] = off[i];
+  chunk_starts(c);
+  return c;
+}
+// the ChunkTable of off[0..16]: cstart[0..16], and chunk_range of every chunk b: out (chunks, 3) [t, e0, e1]; out may be
+// NULL to get the chunk count alone
+int nlc_t_chunk_ranges(const long long* off, int* cstart, long long* out) {
+  const ChunkTable c = table_of(off);
+  for (int i = 0; i <= kTensors; ++i) cstart[i] = c.cstart[i];
+  for (int b = 0; out && b < c.cstart[kTensors]; ++b) {
+    const ChunkRange r = chunk_range(c, b);
+    out[3 * b] = r.t;
+    out[3 * b + 1] = (long long)r.e0;
+    out[3 * b + 2] = (long long)r.e1;
+  }
+  return c.cstart[kTensors];
+}
+// a gradient's chunk sums of squares as train_reduce_kernel forms them (thread i of 256 sums elements e0 + i, e0 + i + 256,
+// ... in order, then the fixed tree over the 256 sums): sq (chunks); then clip_total_norm of them
+double nlc_t_clip_total(const long long* off, const double* grad, double* sq) {
+  const ChunkTable c = table_of(off);
+  for (int b = 0; b < c.cstart[kTensors]; ++b) {
+    const ChunkRange r = chunk_range(c, b);
+    double red[kThreads];
+    for (int i = 0; i < kThreads; ++i) {
+      double s = 0.0;
+      for (int64_t e = r.e0 + i; e < r.e1; e += kThreads) s += grad[e] * grad[e];
+      red[i] = s;
+    }
+    for (int w = kThreads / 2; w > 0; w >>= 1)
+      for (int i = 0; i < w; ++i) red[i] += red[i + w];
+    sq[b] = red[0];
+  }
+  return clip_total_norm(sq, c);
+}
 // the Fourier series' query points and prediction factor: t (n), k (nk) -> theta_s, phi_s (n, nk), factor (n)
 void nlc_t_fourier(double alpha, double log_tol, const double* t, long n, const int* k, int nk, double* th, double* ph,
                    double* factor) {

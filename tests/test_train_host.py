@@ -274,6 +274,125 @@ def test_blob_offsets_match_the_state_dict(lib):
         assert list(np.diff(out)) == sizes, (d, nu, enc, h, S)
 
 
+_T, _CHUNK = 16, 1024  # kTensors, kChunk
+
+
+def _offsets(sizes):
+    assert len(sizes) == _T
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def _chunk_tables(lib):
+    """name -> off[0..16]: the NL table at d = 5, nin = 2, h = 64, S = 17; the RNN table (six tensors, ten empty) at H = 64;
+    a synthetic table over the sizes around the chunk length, the empty tensor first and the ten spare slots empty."""
+    out = np.zeros(_T + 1, dtype=np.int64)
+    tables = {}
+    f = lib.nlc_t_blob_offsets
+    f.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    f(5, 2, 32, 64, 17, out.ctypes.data)
+    tables["nl"] = out.copy()
+    f = lib.nlc_t_rnn_blob_offsets
+    f.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p]
+    f(5, 2, 64, 1, out.ctypes.data)
+    tables["rnn"] = out.copy()
+    assert (np.diff(tables["rnn"])[6:] == 0).all() and (np.diff(tables["rnn"])[:6] > 0).all()
+    tables["synthetic"] = _offsets([0, 1, 1023, 1024, 1025, 2049] + [0] * 10)
+    return tables
+
+
+def _chunk_ranges(lib, off):
+    f = lib.nlc_t_chunk_ranges
+    f.argtypes = [ctypes.c_void_p] * 3
+    f.restype = ctypes.c_int
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    cstart = np.zeros(_T + 1, dtype=np.int32)
+    n = f(off.ctypes.data, cstart.ctypes.data, None)
+    rng = np.zeros((n, 3), dtype=np.int64)
+    assert f(off.ctypes.data, cstart.ctypes.data, rng.ctypes.data) == n == cstart[_T]
+    return cstart, rng
+
+
+def _clip_total(lib, off, grad):
+    f = lib.nlc_t_clip_total
+    f.argtypes = [ctypes.c_void_p] * 3
+    f.restype = ctypes.c_double
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    grad = np.ascontiguousarray(grad, dtype=np.float64)
+    assert grad.size == off[_T]
+    sq = np.zeros(max(1, int(np.sum((np.diff(off) + _CHUNK - 1) // _CHUNK))), dtype=np.float64)
+    return f(off.ctypes.data, grad.ctypes.data, sq.ctypes.data), sq
+
+
+def test_chunk_range_tiles_the_blob_tensor_by_tensor(lib):
+    """nlc_train.h chunk_range over a ChunkTable (what train_reduce_kernel and both Adam kernels call): every chunk b in
+    [0, cstart[kTensors]) maps to one tensor; its range is non-empty and at most kChunk long; the ranges tile [0, P) in order
+    with no gap or overlap; none straddles a tensor; an empty tensor owns none."""
+    for name, off in _chunk_tables(lib).items():
+        cstart, rng = _chunk_ranges(lib, off)
+        sizes = np.diff(off)
+        assert list(np.diff(cstart)) == [int(-(-n // _CHUNK)) for n in sizes], name
+        P, pos, owners = int(off[_T]), 0, np.zeros(_T, dtype=np.int64)
+        for b, (t, e0, e1) in enumerate(rng):
+            where = f"{name} chunk {b}"
+            assert 0 <= t < _T and cstart[t] <= b < cstart[t + 1], where
+            assert 0 < e1 - e0 <= _CHUNK, where
+            assert e0 == pos, where  # in order, no gap, no overlap
+            assert off[t] <= e0 and e1 <= off[t + 1], where  # inside tensor t
+            pos = int(e1)
+            owners[t] += 1
+        assert pos == P, name
+        assert ((owners == 0) == (sizes == 0)).all(), name
+
+
+def test_clip_total_norm_vs_clip_grad_norm(lib):
+    """nlc_train.h clip_total_norm on chunk sums of squares formed as train_reduce_kernel forms them, against the total
+    torch.nn.utils.clip_grad_norm_ returns for the same tensors: 2 ulp, the bound of the clip coefficient above."""
+    rng = np.random.default_rng(5)
+    for name, off in _chunk_tables(lib).items():
+        grad = rng.standard_normal(int(off[_T])) * 10.0 ** rng.integers(-3, 2, int(off[_T]))
+        total, _ = _clip_total(lib, off, grad)
+        params = []
+        for i in range(_T):
+            p = torch.nn.Parameter(torch.zeros(int(off[i + 1] - off[i]), dtype=torch.float64))
+            p.grad = torch.from_numpy(grad[off[i] : off[i + 1]].copy())
+            params.append(p)
+        ref = float(torch.nn.utils.clip_grad_norm_(params, 1.0))
+        print(f"{name}: total {total!r} torch {ref!r} ulp {float(_ulp(np.float64(total), np.float64(ref)))}")
+        assert _ulp(np.float64(total), np.float64(ref)) <= 2, name
+
+
+def test_clip_total_norm_ignores_empty_tensors_bit_for_bit(lib):
+    """What the RNN and NODE tables' padding relies on: the total of a table with empty tensors has the bits of the total
+    without them -- the same tensors with the empty ones moved (between, in front, behind), and the same sums with no empty
+    tensor at all, restated here over the non-empty tensors only."""
+    rng = np.random.default_rng(6)
+    for name, off in _chunk_tables(lib).items():
+        sizes = [int(n) for n in np.diff(off)]
+        full = [n for n in sizes if n]
+        pad = _T - len(full)
+        grad = rng.standard_normal(int(off[_T]))
+        total, sq = _clip_total(lib, off, grad)
+        # the non-empty tensors alone: their chunks' sums in order, sqrt, squared again, summed in tensor order
+        tot2, c = np.float64(0.0), 0
+        for n in full:
+            s = np.float64(0.0)
+            for _ in range(-(-n // _CHUNK)):
+                s = s + sq[c]
+                c += 1
+            r = np.sqrt(s)
+            tot2 = tot2 + r * r
+        assert c == sq.size or not full
+        assert float(np.sqrt(tot2)).hex() == total.hex(), name
+        if not pad:
+            continue
+        # the same tensors in the same order, the empty ones elsewhere
+        for lay in (full + [0] * pad, [0] * pad + full, [x for n in full for x in (n, 0)][: 2 * pad] + full[pad:]):
+            lay = (lay + [0] * _T)[:_T]
+            assert [n for n in lay if n] == full, name
+            other, sq2 = _clip_total(lib, _offsets(lay), grad)
+            assert (sq2 == sq).all() and other.hex() == total.hex(), (name, lay)
+
+
 def test_blockwise_comparator_catches_what_the_per_tensor_scale_hides():
     """tests/train_compare.py: an autograd gradient of the oracle's loss for a model whose layer-0 reset gate is saturated
     (its input bias shifted by +8: r(1 - r) ~ 3e-4), so the r block of weight_ih_l0 is orders of magnitude below the n block.
