@@ -15,7 +15,8 @@ here, so this file follows the published algorithm:
 **Parity unpinned vs upstream torchlaplace**: the defaults ``alpha``, ``tol``,
 ``scale`` and the rep-func input order ``[theta_s | phi_s | p]`` are recalled,
 not verifiable offline.  They are parameters here and in the
-HIP path, with the same defaults on both sides.
+HIP path, with the same defaults on both sides.  The de Hoog recurrences themselves ARE pinned: tests/test_dehoog_mp_host.py
+holds a 60-digit restatement to mpmath's own ``deHoog.calc_time_domain_solution`` and measures this file against it.
 """
 
 import math

@@ -374,8 +374,17 @@ def test_ilt_single_point_wide(nlc):
         if algo == "fourier":
             np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=1e-9, atol=1e-9 * float(ref.abs().max()))
         else:
-            # random (non-smooth) F makes the QD table ill-conditioned: both sides are finite and agree loosely
-            assert torch.isfinite(got).all() == torch.isfinite(ref).all()
+            # random (non-smooth) F makes the QD table ill-conditioned, so the kernel is not compared with another float64
+            # rounding but, like both CPU roundings, with the 60-digit value of each of the six rows: its error may be 32 x
+            # the larger CPU rounding's worst (the forward margin of tests/test_dehoog_mp_host.py)
+            import dehoog_mp_reference as R
+
+            x_mp = R.mp_forward(theta, phi, t)
+            cpu_max = max(float(R.forward_errors(r, x_mp).max()) for r in R.cpu_forward_roundings(theta, phi, t))
+            err = R.forward_errors(got, x_mp)
+            print(f"single point wide dehoog S={S}: kernel max {err.max():.2e}, CPU roundings' max {cpu_max:.2e}")
+            assert torch.isfinite(got).all() and torch.isfinite(ref).all()
+            assert err.max() <= R.FWD_MARGIN_MAX * cpu_max, (S, err, cpu_max)
 
 
 @pytest.mark.parametrize("S", list(range(3, 34)))

@@ -433,6 +433,55 @@ def test_repfunc_split_kernel_agrees_with_wave_per_tile_planner(nlc):
             np.testing.assert_allclose(a.numpy(), b.numpy(), rtol=1e-9, atol=1e-10, err_msg=f"{env} S={S}")
 
 
+@pytest.mark.parametrize("S", [7, 11, 31])
+def test_dehoog_staged_planner_odd_half_term_counts(nlc, S):
+    """The staged planner's slot-major QD launch walks four diagonals of the table per pass (dehoog_row<M, CH, 4>); for odd
+    M = (S - 1) / 2 the 2M diagonals leave a TAIL pass of two, which no even-M term count (33, 17, 9, 21) reaches.  M = 3, 5, 15,
+    ragged K (a block of 13 samples): against the oracle at test_cfg5_dehoog_planner_staged_hip_path's bounds, and the first
+    step's states of all K samples against the model forward on the same windows -- the row-major launch, two diagonals per
+    pass and no tail; the two differ only in the rounding of the representation kernels."""
+    from oracle import envs as oenvs
+    from oracle import mppi as omppi
+    from oracle import nl_model as onl
+
+    env, K, T = "oderl-cartpole", 64 + 13, 3
+    st = onl.ENV_STATS[env]
+    d, nu, A = st["d"], st["nu"], st["act_high"]
+    sd = onl.make_synthetic_state_dict(6, d, nu, 128, S, st["state_std"], [A / 2], tame="dehoog")
+    model = build_model(nlc, sd, S=S, algo="dehoog")
+    sig = nlc.noise_sigma(nu)
+    g = torch.Generator().manual_seed(S)
+    raw = torch.randn(K, T, nu, dtype=torch.float64, generator=g)
+    U0 = torch.randn(T, nu, dtype=torch.float64, generator=g) * 0.2
+    ab = (torch.rand(4, nu, dtype=torch.float64, generator=g) * 2 - 1) * A / 2
+    state = nlc.initial_state(env)
+    mppi = nlc.MPPIDelay(nlc.NLDynamics(model, 0.05), nlc.EnvCost(env), d, sig, K, T, "cpu", lambda_=1.0,
+                         u_min=torch.tensor(-A), u_max=torch.tensor(A), u_scale=A, U_init=U0.clone(),
+                         planner_options={"dehoog_chain": 0})
+    assert mppi.fused
+    mppi.noise_dist = _Replay(raw)
+    mppi.ctx.profile(True)
+    with torch.no_grad():
+        act = mppi.command(state, ab)
+    mppi.ctx.profile(False)
+    prof = mppi.ctx.profile_read()
+    assert "ilt_dehoog_kernel" in prof and "nl_dehoog_chain_kernel" not in prof, sorted(prof)
+    ts = torch.full((K, 1), 0.05, dtype=torch.float64)
+    ref = omppi.mppi_command(U0.clone(), state, ab, raw.clone(), onl.nl_dynamics(sd, ts, S=S, ilt_algorithm="dehoog"),
+                             oenvs.RUNNING_COST[env], d, torch.inverse(sig), 1.0, A, torch.tensor(-A), torch.tensor(A))
+    np.testing.assert_allclose(mppi.states.numpy(), ref["states"].numpy(), rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(act.numpy(), ref["action"].numpy(), rtol=1e-5, atol=1e-6)
+    # step 0 of every sample through model.forward: the window is the buffer's last three actions and the sample's first one
+    window = torch.cat((ab[1:].view(1, -1, nu).repeat(K, 1, 1), A * ref["perturbed_action"][:, :1]), dim=1)
+    x0 = state.view(1, -1).repeat(K, 1)
+    with torch.no_grad():
+        fwd = x0 + model(x0.cuda(), window.cuda(), ts.cuda()).cpu().view(K, d)
+    got = mppi.states[:, 0]
+    print(f"staged planner S={S}: first-step states vs model forward, max |diff| {float((got - fwd).abs().max()):.2e}, "
+          f"max |diff| / (1e-9 + 1e-9 |x|) {float(((got - fwd).abs() / (1e-9 + 1e-9 * fwd.abs())).max()):.2e}")
+    np.testing.assert_allclose(got.numpy(), fwd.numpy(), **TOL)
+
+
 @pytest.mark.fp64_bit_identity
 def test_gru_cooperative_kernel_bit_identical(nlc):
     """gru_encode_coop_kernel (one 16-window tile per workgroup, one gate chunk per wavefront; what small launches and the
